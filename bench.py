@@ -1,8 +1,20 @@
 #!/usr/bin/env python3
 """bench.py -- Mrays/s of ReflaxMan's per-pixel trace loop on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--config c1..c5|shot|shot128]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--config c1..c5|shot|shot128] [--full] [--dump-outputs DIR]
     python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...
+
+A plain run does what the headline figure needs and no more: set up, the first frame, the clock ramp and (N > 1) the
+band balance, W warmup steps, K timed steps, one JSON line (metric, value, unit, ms_per_step, phases_ms, config).
+`--full` adds everything else described below to the same line: parity against the reference's hashes and against
+single-GPU renders, the counted frame (work per ray, roofline), end-to-end and first-view timings, c4_1gpu, the
+strong-scaling baseline, the RGB-gather timing and the CPU baselines.
+
+The random stream is set back to the reference's seeds before the warmup steps, so with the same arguments every run
+renders the same frames.  `--dump-outputs DIR` writes what the last timed step left in the caller's buffers, as
+float32 / float64 .npy files: rgb.npy (n x 3, the float image; N > 1: only with --gather-rgb), argb8.npy (n x 4, the
+A, R, G, B bytes of the ARGB8 image) and pixel_index.npy (n, the pixels' row-major indices) -- the whole frame up to
+2^20 pixels, else a fixed seeded sample of 2^20 of them.
 
 `--gpus N` (N > 1) without a launcher starts the N ranks itself (a torch.distributed.run child job, rendezvous on
 127.0.0.1) and exits with its code; under a launcher, --gpus must equal WORLD_SIZE (else exit 2).
@@ -88,6 +100,32 @@ CPU_BAND_ROWS = {"shot": (None, 160), "shot128": (0, 1)}
 PARITY_CASE = {"shot128": "pulse_screenshot_1920x1080_ss128"}
 # steps / warmup when not given: a shot128 frame takes ~1.5 s
 DEFAULT_STEPS = {"shot128": (3, 1)}
+
+
+# --dump-outputs: pixels kept per frame (36 B each over the three files: 36 MiB) and the seed of the sample
+DUMP_PIXELS = 1 << 20
+DUMP_SEED = 20130928
+
+
+def dump_pixels(n_px: int) -> np.ndarray:
+    """Row-major indices (ascending, int64) of the pixels --dump-outputs keeps of an n_px frame: all of them up to
+    DUMP_PIXELS, else a fixed seeded sample of DUMP_PIXELS (the same for every run and build)."""
+    if n_px <= DUMP_PIXELS:
+        return np.arange(n_px, dtype=np.int64)
+    return np.sort(np.random.default_rng(DUMP_SEED).choice(n_px, DUMP_PIXELS, replace=False)).astype(np.int64)
+
+
+def dump_outputs(out_dir: str, idx: np.ndarray, rgb, argb: np.ndarray) -> dict:
+    """Write the sampled outputs of the last timed step: rgb (n x 3 float32, or None: not gathered) and argb (n uint32)
+    at the pixels idx; returns {file: shape}."""
+    os.makedirs(out_dir, exist_ok=True)
+    files = {"pixel_index": idx.astype(np.float64),
+             "argb8": np.stack([(argb >> s) & 0xFF for s in (24, 16, 8, 0)], axis=1).astype(np.float32)}
+    if rgb is not None:
+        files["rgb"] = np.ascontiguousarray(rgb, dtype=np.float32).reshape(-1, 3)
+    for name, a in files.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+    return {name + ".npy": list(a.shape) for name, a in files.items()}
 
 
 def frame_size(n: int, w0: int, h0: int, scaling: str):
@@ -359,8 +397,13 @@ def main(argv=None):
     ap.add_argument("--height", type=int, default=None)
     ap.add_argument("--depth", type=int, default=None)
     ap.add_argument("--ss", type=int, default=None, help="samples per pixel ss x ss (SSAA; default: the config's)")
-    ap.add_argument("--no-first-view", action="store_true", help="N = 1: skip the first-view timing")
-    ap.add_argument("--no-c4", action="store_true", help="N = 1 (C3): skip the same-run C4 frame (c4_1gpu)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check everything beside the headline figure: parity, the counted frame and "
+                         "roofline, end-to-end and first-view timings, c4_1gpu, scaling baselines, CPU baselines")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's outputs (a fixed sample of large frames) as DIR/<name>.npy")
+    ap.add_argument("--no-first-view", action="store_true", help="--full, N = 1: skip the first-view timing")
+    ap.add_argument("--no-c4", action="store_true", help="--full, N = 1 (C3): skip the same-run C4 frame (c4_1gpu)")
     ap.add_argument("--gather-rgb", action="store_true", help="N > 1: gather the float RGB strips to rank 0 too")
     ap.add_argument("--regroup", type=int, default=None,
                     help="ray regrouping: park traces after n segments (0 off; default: the library's choice)")
@@ -393,6 +436,9 @@ def main(argv=None):
     d_steps, d_warmup = DEFAULT_STEPS.get(cfg_name, (50, 5))
     args.steps = d_steps if args.steps is None else args.steps
     args.warmup = d_warmup if args.warmup is None else args.warmup
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    full = args.full
     c_scene, c_w, c_h, c_depth, c_ss, c_desc = CONFIGS[cfg_name]
     custom = any(v is not None for v in (args.scene, args.width, args.height, args.depth, args.ss))
     args.scene = args.scene or c_scene
@@ -405,7 +451,7 @@ def main(argv=None):
     import torch
     import torch.distributed as dist
     from reflaxman_amd import _lib, metrics, scenes
-    from reflaxman_amd.render import Renderer, build_scene, make_frame
+    from reflaxman_amd.render import DEFAULT_JITTER_SEED, Renderer, build_scene, make_frame
 
     torch.cuda.set_device(local)
     dev = torch.device("cuda", local)
@@ -463,7 +509,7 @@ def main(argv=None):
     torch.cuda.synchronize()
     parity = {}
     one = None  # rank 0 at N > 1: a single-GPU renderer of the same frame (parity checks, strong-scaling baseline)
-    if world > 1 and rank == 0:
+    if full and world > 1 and rank == 0:
         # the assembled multi-rank frame must equal a single-GPU render of the same frame (untimed)
         one = SingleGpu(Renderer, scene, make_frame(cam, W, H, depth, ss), W, H, dev, stream)
         img1, argb1 = one.render(SEED)
@@ -481,7 +527,7 @@ def main(argv=None):
             np.save(os.path.join(os.environ["RFX_BENCH_DUMP"], "multi.npy"), full0.cpu().numpy())
             np.save(os.path.join(os.environ["RFX_BENCH_DUMP"], "single.npy"), argb1.view(H, W).cpu().numpy())
     first_rgb = first_argb = None
-    if world == 1:
+    if full and world == 1:
         first_rgb = img.view(H, W, 3).cpu().numpy()
         first_argb = argb[: H * W].view(H, W).cpu().numpy().view(np.uint32)
         man = json.load(open(os.path.join(ROOT, "tests", "golden", "manifest.json")))["cases"]
@@ -493,7 +539,7 @@ def main(argv=None):
             parity["full_frame_vs_reference_sha256"] = {"f32": ok_f, "argb8": ok_a, "case": key}
     # counted frames (the stats kernel) into scratch buffers at N > 1 (the step buffers may still be in pipelined
     # sends); each advances the random stream itself, on every rank
-    cimg, cargb = (torch.empty_like(img), torch.empty_like(argb)) if world > 1 else (img, argb)
+    cimg, cargb = (torch.empty_like(img), torch.empty_like(argb)) if full and world > 1 else (img, argb)
 
     def counted_frame():
         c = torch.zeros(_lib.RFX_NCOUNTERS, dtype=torch.int64, device=dev)
@@ -506,14 +552,16 @@ def main(argv=None):
         torch.cuda.synchronize()
         return c
 
-    counters = counted_frame()
-    cnt = counters.cpu().numpy().astype(np.uint64)
-    if world > 1:
-        c = torch.tensor(cnt.astype(np.int64), device=dev)
-        dist.all_reduce(c)
-        cnt = c.cpu().numpy().astype(np.uint64)
-    work = metrics.summary(cnt)
-    flops_frame = work["flops"]
+    work = flops_frame = None
+    if full:
+        counters = counted_frame()
+        cnt = counters.cpu().numpy().astype(np.uint64)
+        if world > 1:
+            c = torch.tensor(cnt.astype(np.int64), device=dev)
+            dist.all_reduce(c)
+            cnt = c.cpu().numpy().astype(np.uint64)
+        work = metrics.summary(cnt)
+        flops_frame = work["flops"]
 
     # ---- clock ramp: untimed frames for ~args.prewarm_ms before the W warmup steps (a few short frames leave the
     # GPU below its steady clock: C3 trace 0.766 ms after 2 warmup frames vs 0.721 ms after 50, same box).  The
@@ -537,9 +585,17 @@ def main(argv=None):
         # cut the bands from measured per-rank render times (rank 0's receive included), then keep them
         sf.balance(rounds=3, frames=8)
         log(f"rank {rank}: bands {sf.bounds}")
-        # this rank's work in its final band, for the per-launch roofline
-        flops_local = metrics.summary(counted_frame().cpu().numpy().astype(np.uint64))["flops"]
+        if full:
+            # this rank's work in its final band, for the per-launch roofline
+            flops_local = metrics.summary(counted_frame().cpu().numpy().astype(np.uint64))["flops"]
+    # ---- the random stream back at the reference's seeds: the frames before this point are a number that depends on
+    # the clock (prewarm), the frames from here on are the same in every run with the same arguments
+    if world > 1:
+        sf.drop_lookahead()
+    torch.cuda.synchronize()
+    rr.set_rng(SEED, DEFAULT_JITTER_SEED)
     # ---- warmup, then K timed steps (barrier + synchronize on both sides)
+    last = None
     for _ in range(args.warmup):
         step()
     torch.cuda.synchronize()
@@ -554,13 +610,25 @@ def main(argv=None):
     torch.cuda.synchronize()
     t0 = time.perf_counter()
     for _ in range(args.steps):
-        step()
+        last = step()
     torch.cuda.synchronize()
     if world > 1:
         dist.barrier()
     elapsed = time.perf_counter() - t0
     pre_ms, trace_ms, nfr = rr.get_timing()
     rr.set_timing(False)
+    dumped = None
+    if args.dump_outputs and rank == 0:
+        # what the last timed step handed its caller: one GPU, the float image and the ARGB8 image it rendered into;
+        # N > 1, the assembled ARGB8 frame on rank 0 (and the float image where --gather-rgb assembled it too)
+        idx = dump_pixels(W * H)
+        ix = torch.from_numpy(idx).to(dev)
+        d_rgb = img if world == 1 else (sf.rgb_full.reshape(-1) if args.gather_rgb else None)
+        d_argb = argb if world == 1 else last.reshape(-1)
+        h_rgb = d_rgb[: W * H * 3].view(-1, 3).index_select(0, ix).cpu().numpy() if d_rgb is not None else None
+        h_argb = d_argb[: W * H].index_select(0, ix).cpu().numpy().view(np.uint32)
+        dumped = dump_outputs(args.dump_outputs, idx, h_rgb, h_argb)
+        log(f"--dump-outputs: {dumped} in {args.dump_outputs} (last timed step, {len(idx)} of {W * H} px)")
     emit_side = None
     if world > 1:
         emit_side = sf.time_emits(False)  # ms per look-ahead emit on the side stream (None without emit-ahead)
@@ -573,7 +641,7 @@ def main(argv=None):
         trace_avg, pre_avg = trace_ms / max(nfr, 1), pre_ms / max(nfr, 1)
 
     steady = baseline = None
-    if world > 1:
+    if full and world > 1:
         # steady-state parity: one more step down the same path (look-aheads, masks, schedule, pipelined transfer),
         # against a single-GPU render of the same frame of the stream (its start state is the pending frame's)
         torch.cuda.synchronize()
@@ -594,7 +662,7 @@ def main(argv=None):
             one.close()
 
     e2e = None
-    if world == 1:
+    if full and world == 1:
         # end to end with the frame handed back to the host: reported beside `value`, never as it.
         # (1) the display path: the ARGB8 plane (what a window shows, Pulse.cpp:455-458) of frame i copied to pinned
         #     host memory on a copy stream while frame i + 1 renders into the other of two device frame sets;
@@ -640,7 +708,7 @@ def main(argv=None):
         del sets
 
     first_view = None
-    if world == 1 and not args.no_first_view:
+    if full and world == 1 and not args.no_first_view:
         # what a view pays before the per-view state exists (the headline value is a still camera's steady state):
         # per-view primary masks off (a camera that moves every frame never has them), then also the tile schedule
         # reset to raster order (the very first frame of a grid, before any tile cost was measured)
@@ -677,7 +745,7 @@ def main(argv=None):
                               "longest-first schedule from earlier frames' tile costs"}
 
     c4_1gpu = None
-    if times_c4_denominator(world, cfg_name, custom, args.no_c4):
+    if full and times_c4_denominator(world, cfg_name, custom, args.no_c4):
         # the denominator of a scaling curve: N > 1 lines render C4 (7680x4320), the N = 1 line C3 (3840x2160), so the
         # C4 frame is also timed here on this GPU, same steps and warmup, and checked against the reference's hash
         s4, w4, h4, d4, _, _ = CONFIGS["c4"]
@@ -696,7 +764,7 @@ def main(argv=None):
         del one4
 
     rgb_gather = None
-    if world > 1 and bands and not args.gather_rgb:
+    if full and world > 1 and bands and not args.gather_rgb:
         # the drop-in's path reads the float image (Render::imagePixel): the same bands with the f32 RGB plane sent to
         # rank 0 too (16 B/px instead of 4), timed the same way, reported beside the ARGB8-only value
         sf.set_gather_rgb(True)
@@ -730,34 +798,37 @@ def main(argv=None):
     # (bands: rank 0's counted work in its final band; strips: an equal share, the strips being balanced)
     if world > 1:
         rows = sf.rows
-    flops_launch = flops_local if flops_local is not None else flops_frame / world
-    achieved = flops_launch / (trace_avg * 1e-3) / 1e12
-    px_launch = rows * W
-    # HBM traffic and executed VALU work of the trace kernel: rocprofv3 --pmc passes of this very workload
-    # and library build (tools/prof_round.sh -> profiles/pmc/), per launch; null when no such record exists
-    pmc = metrics.pmc_record(os.path.join(ROOT, "profiles", "pmc"), [args.scene, W, H, depth, world, ss],
-                             _lib.lib_sha256(), _lib.device_sha256())
-    traffic = pmc["hbm_bytes_per_launch"] if pmc else None
     passes = len(sf.passes) if world > 1 and bands and sf.passes else 0
     launches = split_launches(W, H, ss) if world == 1 else max(1, passes)
     if launches > 1 and world == 1:
         # a frame of several launches on two overlapping streams: a launch's HIP-event span includes the other stream's
         # work, so the per-launch time is the frame's wall time shared out over its launches
         trace_avg = ms_step / launches
-        flops_launch = flops_frame / launches
-        px_launch = W * H // launches
-    elif launches > 1:
-        # row-span passes (N > 1): rank 0 traces one band per pass, each timed by HIP events on its stream
-        flops_launch = flops_launch / launches
-        px_launch = sf.rows * W // launches
-    executed = metrics.executed_work(pmc, trace_avg)
-    roofline = metrics.roofline(executed, traffic, flops_launch, trace_avg, px_launch)
-    if launches > 1:
-        roofline["launches_per_frame"] = launches
-        roofline["launch_time_kind"] = ("frame wall time / launches (the split frame's launches overlap on two streams)"
-                                        if world == 1 else "rank 0's band launch of each row-span pass (HIP events)")
-    roofline["kernel"] = ("rfx::trace_kernel (plain pixel mode, wave-bundle culling)" if ss == 1 else
-                          "rfx::trace_kernel (SSAA pixel mode, wave-bundle culling)")
+    roofline = None
+    if full:
+        flops_launch = flops_local if flops_local is not None else flops_frame / world
+        px_launch = rows * W
+        # HBM traffic and executed VALU work of the trace kernel: rocprofv3 --pmc passes of this very workload
+        # and library build (tools/prof_round.sh -> profiles/pmc/), per launch; null when no such record exists
+        pmc = metrics.pmc_record(os.path.join(ROOT, "profiles", "pmc"), [args.scene, W, H, depth, world, ss],
+                                 _lib.lib_sha256(), _lib.device_sha256())
+        traffic = pmc["hbm_bytes_per_launch"] if pmc else None
+        if launches > 1 and world == 1:
+            flops_launch = flops_frame / launches
+            px_launch = W * H // launches
+        elif launches > 1:
+            # row-span passes (N > 1): rank 0 traces one band per pass, each timed by HIP events on its stream
+            flops_launch = flops_launch / launches
+            px_launch = sf.rows * W // launches
+        executed = metrics.executed_work(pmc, trace_avg)
+        roofline = metrics.roofline(executed, traffic, flops_launch, trace_avg, px_launch)
+        if launches > 1:
+            roofline["launches_per_frame"] = launches
+            roofline["launch_time_kind"] = ("frame wall time / launches (the split frame's launches overlap on two "
+                                            "streams)" if world == 1 else
+                                            "rank 0's band launch of each row-span pass (HIP events)")
+        roofline["kernel"] = ("rfx::trace_kernel (plain pixel mode, wave-bundle culling)" if ss == 1 else
+                              "rfx::trace_kernel (SSAA pixel mode, wave-bundle culling)")
     if baseline is not None:
         baseline["efficiency"] = round(mrays / (world * baseline["value"]), 4)
     workload = (c_desc if not custom else f"{args.scene} scene") + f", {W}x{H}, depth {depth}, {ss * ss} spp"
@@ -775,7 +846,8 @@ def main(argv=None):
                                    + ("+count-ahead" if sf.count_ahead else "")
                                    + ("+emit-ahead" if sf.emit_ahead else "")
                                    + (f"+row-span-passes-x{passes}" if passes else "")) if world > 1 else "single-gpu"},
-        "roofline": roofline,
+        "full": full,
+        **({"roofline": roofline} if full else {}),
         "phases_ms": {"rng_prepass": round(pre_avg, 4), "trace": round(trace_avg, 4), "timed_every_nth_frame": timing_every,
                       **({"rng_prepass_kind": "look-ahead emit on the side stream, beside the previous trace (HIP "
                                               "events on that stream): off the critical path"}
@@ -785,15 +857,18 @@ def main(argv=None):
                                         "the chip (so it spans most of that trace, off the critical path); trace is "
                                         "the frame's wall time / launches"}
                          if launches > 1 else {})},
-        "work_per_ray": {k: round(v, 3) for k, v in work.items() if k != "flops"},
-        # SURVEY §8(d) secondary metric: bounce segments + shadow rays per second (counted, frame 0's rates)
-        "secondary_Msegments_per_s": round((work["segments_per_ray"] + work["shadow_rays_per_ray"]) * traces
-                                           * args.steps / elapsed / 1e6, 1),
-        "end_to_end_incl_d2h": e2e,
+        **({"outputs": {"dir": os.path.abspath(args.dump_outputs), "files": dumped, "pixels": W * H,
+                        "frame": f"timed step {args.steps} (the {args.warmup + args.steps}th frame of the random "
+                                 "stream from the reference's seeds)"}} if dumped else {}),
+        **({"work_per_ray": {k: round(v, 3) for k, v in work.items() if k != "flops"},
+            # SURVEY §8(d) secondary metric: bounce segments + shadow rays per second (counted, frame 0's rates)
+            "secondary_Msegments_per_s": round((work["segments_per_ray"] + work["shadow_rays_per_ray"]) * traces
+                                               * args.steps / elapsed / 1e6, 1),
+            "end_to_end_incl_d2h": e2e,
+            "parity": parity} if full else {}),
         **({"first_view": first_view} if first_view else {}),
         **({"c4_1gpu": c4_1gpu} if c4_1gpu else {}),
         **({"with_rgb_gather": rgb_gather} if rgb_gather else {}),
-        "parity": parity,
         **({"band_bounds": sf.bounds} if bands else {}),
         **({"steady_state_parity": steady,
             "efficiency": baseline["efficiency"] if baseline else None,
@@ -804,9 +879,9 @@ def main(argv=None):
             "scale_note": (f"N > 1 renders {cfg_name.upper()} ({W}x{H}); the driver's N = 1 bench point is C3 "
                            "(3840x2160), whose line carries c4_1gpu, the C4 frame on one GPU in that run: efficiency "
                            "here is against strong_scaling_baseline, the same frame on one GPU of this run")}
-           if world > 1 else {}),
+           if full and world > 1 else {}),
     }
-    if world == 1 and not args.no_cpu_baseline:
+    if full and world == 1 and not args.no_cpu_baseline:
         log("cpu_baseline: reference CPU path on a row sample of the same frame ...")
         if ss != 1:
             y0b, nrows = CPU_BAND_ROWS.get(cfg_name, (None, 16)) if not custom else (None, 16)

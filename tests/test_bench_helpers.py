@@ -104,6 +104,29 @@ def test_gpus_n_without_launcher_starts_the_ranks(monkeypatch):
     assert len(port) == 1 and 0 < int(port[0].split("=")[1]) < 65536
 
 
+def test_dump_sample_is_fixed_and_within_the_size_limit(tmp_path):
+    """--dump-outputs keeps a small frame whole and a fixed, seeded, ascending sample of a large one; the files are
+    float32 / float64 and together under 64 MB at the largest config's frame."""
+    import numpy as np
+    assert np.array_equal(bench.dump_pixels(96 * 54), np.arange(96 * 54))
+    n = 7680 * 4320
+    idx = bench.dump_pixels(n)
+    assert idx.dtype == np.int64 and len(idx) == bench.DUMP_PIXELS and np.array_equal(idx, bench.dump_pixels(n))
+    assert np.all(np.diff(idx) > 0) and 0 <= idx[0] and idx[-1] < n
+    rgb = np.arange(len(idx) * 3, dtype=np.float32).reshape(-1, 3)
+    argb = (np.arange(len(idx), dtype=np.uint64) * 2654435761 % (1 << 32)).astype(np.uint32)
+    shapes = bench.dump_outputs(str(tmp_path / "out"), idx, rgb, argb)
+    assert shapes == {"pixel_index.npy": [len(idx)], "argb8.npy": [len(idx), 4], "rgb.npy": [len(idx), 3]}
+    files = {f: np.load(tmp_path / "out" / f) for f in shapes}
+    assert sum(a.nbytes for a in files.values()) <= 64 * 1000 * 1000
+    assert all(a.dtype in (np.float32, np.float64) for a in files.values())
+    assert np.array_equal(files["pixel_index.npy"], idx) and np.array_equal(files["rgb.npy"], rgb)
+    a8 = files["argb8.npy"].astype(np.uint32)
+    assert np.array_equal(a8[:, 0] << 24 | a8[:, 1] << 16 | a8[:, 2] << 8 | a8[:, 3], argb)
+    # N > 1 without --gather-rgb: no float image on rank 0, so none is written
+    assert "rgb.npy" not in bench.dump_outputs(str(tmp_path / "argb_only"), idx[:8], None, argb[:8])
+
+
 def test_gpus_must_match_the_launchers_world(monkeypatch):
     """Under a launcher, --gpus must equal WORLD_SIZE: a mismatch exits 2 before anything is measured."""
     monkeypatch.setenv("WORLD_SIZE", "1")

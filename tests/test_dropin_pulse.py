@@ -7,9 +7,9 @@ librfx.so instead of the renderer's .cpp files (tools/pulse_build.py).  A headle
 
 * CPU (build container, needs /root/reference): Pulse.cpp and the caller's sources compile and link against
   the drop-in headers -- the compile-only proof a maintainer needs.
-* GPU: the drop-in Pulse binary (built in-tree by __graft_entry__.build()) writes a screenshot whose BMP file
-  equals, byte for byte, the one the reference's own Pulse + CPU renderer wrote (tests/golden/manifest.json
-  pulse_screenshot_800x600_ss2, tools/gen_golden.py).
+* GPU: the drop-in Pulse binary (oracle/_ref/pulse_dropin, built by __graft_entry__.build()) writes a screenshot
+  whose BMP file equals, byte for byte, the one the reference's own Pulse + CPU renderer wrote
+  (tests/golden/manifest.json pulse_screenshot_800x600_ss2, tools/gen_golden.py).
 """
 import hashlib
 import os
@@ -21,7 +21,9 @@ import pytest
 from helpers import manifest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-DROPIN = os.path.join(ROOT, "tests", "native", "_build", "pulse_dropin")
+# beside the other binaries built from the reference's sources (oracle/Makefile): a tree built where those sources
+# are carries oracle/_ref/ to hosts that lack them
+DROPIN = os.path.join(ROOT, "oracle", "_ref", "pulse_dropin")
 
 
 @pytest.mark.skipif(not os.path.isdir("/root/reference/src/common"), reason="needs the reference sources")
@@ -59,7 +61,7 @@ def test_dropin_scene_revisions_and_moved_handles(tmp_path):
 def test_pulse_screenshot_matches_reference(tmp_path):
     c = manifest()["cases"]["pulse_screenshot_800x600_ss2"]
     if not os.path.exists(DROPIN):
-        pytest.fail("tests/native/_build/pulse_dropin missing: run __graft_entry__.build() where /root/reference exists")
+        pytest.fail("oracle/_ref/pulse_dropin missing: __graft_entry__.build() makes it from the reference's sources")
     env = {**os.environ, "RFX_SPHERE_SEED": str(c["RFX_SPHERE_SEED"]), "RFX_JITTER_SEED": str(c["RFX_JITTER_SEED"])}
     out = str(tmp_path) + "/"
     r = subprocess.run([DROPIN, out, str(c["res_key"]), str(c["ss_key"])], capture_output=True, text=True, env=env,
@@ -78,7 +80,7 @@ def test_pulse_screenshot_on_a_device_group(tmp_path):
     device 0 on the one-GPU box): byte-identical BMP."""
     c = manifest()["cases"]["pulse_screenshot_800x600_ss2"]
     if not os.path.exists(DROPIN):
-        pytest.fail("tests/native/_build/pulse_dropin missing: run __graft_entry__.build() where /root/reference exists")
+        pytest.fail("oracle/_ref/pulse_dropin missing: __graft_entry__.build() makes it from the reference's sources")
     env = {**os.environ, "RFX_SPHERE_SEED": str(c["RFX_SPHERE_SEED"]), "RFX_JITTER_SEED": str(c["RFX_JITTER_SEED"]),
            "RFX_DEVICES": "0,0,0"}
     r = subprocess.run([DROPIN, str(tmp_path) + "/", str(c["res_key"]), str(c["ss_key"])], capture_output=True,
@@ -102,7 +104,7 @@ def test_pulse_screenshot_128x128_samples(tmp_path, case, devices, policy):
     BMP at 2x2)."""
     c = manifest()["cases"][case]
     if not os.path.exists(DROPIN):
-        pytest.fail("tests/native/_build/pulse_dropin missing: run __graft_entry__.build() where /root/reference exists")
+        pytest.fail("oracle/_ref/pulse_dropin missing: __graft_entry__.build() makes it from the reference's sources")
     env = {k: v for k, v in os.environ.items() if k != "RFX_DEVICES"}
     env.update({"RFX_SPHERE_SEED": str(c["RFX_SPHERE_SEED"]), "RFX_JITTER_SEED": str(c["RFX_JITTER_SEED"]),
                 "RFX_DROPIN_POLICY": policy, **({"RFX_DEVICES": devices} if devices else {})})
@@ -117,7 +119,7 @@ def test_pulse_screenshot_128x128_samples(tmp_path, case, devices, policy):
 def run_frames(tmp_path, c, devices=None, policy="frame"):
     """A non-Pulse caller of the drop-in Render: each frame of case c in one renderNext(W*H) call."""
     if not os.path.exists(DROPIN):
-        pytest.fail("tests/native/_build/pulse_dropin missing: run __graft_entry__.build() where /root/reference exists")
+        pytest.fail("oracle/_ref/pulse_dropin missing: __graft_entry__.build() makes it from the reference's sources")
     env = {k: v for k, v in os.environ.items() if k != "RFX_DEVICES"}
     env.update({"RFX_SPHERE_SEED": str(c["sphere_seed"]), "RFX_JITTER_SEED": str(c.get("jitter_seed", 0)),
                 "RFX_DROPIN_POLICY": policy, **({"RFX_DEVICES": devices} if devices else {})})
@@ -158,7 +160,7 @@ def test_single_call_additive_frames_on_a_device_group(tmp_path):
 def run_session(tmp_path, c, policy, hash_frames=True, devices=None):
     """The interactive session of tests/native/pulse_headless.cpp through the drop-in; returns the parsed frame lines."""
     if not os.path.exists(DROPIN):
-        pytest.fail("tests/native/_build/pulse_dropin missing: run __graft_entry__.build() where /root/reference exists")
+        pytest.fail("oracle/_ref/pulse_dropin missing: __graft_entry__.build() makes it from the reference's sources")
     env = {**os.environ, "RFX_SPHERE_SEED": str(c["RFX_SPHERE_SEED"]), "RFX_JITTER_SEED": str(c["RFX_JITTER_SEED"]),
            "RFX_DROPIN_POLICY": policy, **({"RFX_DEVICES": devices} if devices else {})}
     cmd = [DROPIN, str(tmp_path) + "/", "session", str(c["W"]), str(c["H"]), str(c["tick_us"])]

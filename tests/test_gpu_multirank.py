@@ -26,7 +26,7 @@ def test_bench_multirank_frame_matches_single_gpu(world, partition):
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", f"--nproc-per-node={world}",
            "--master-addr", "127.0.0.1", f"--master-port={_port()}", os.path.join(ROOT, "bench.py"),
            "--gpus", str(world), "--steps", "2", "--warmup", "1", "--width", "640", "--height", "360",
-           "--backend", "gloo", "--one-device", "--no-cpu-baseline", "--partition", partition]
+           "--backend", "gloo", "--one-device", "--full", "--no-cpu-baseline", "--partition", partition]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=600, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-3000:]
     line = [l for l in r.stdout.splitlines() if l.startswith("{")][-1]

@@ -3,7 +3,7 @@
 # Usage: bash tools/configs_round.sh <outdir under gpurun_out>
 O=$PWD/gpurun_out/${1:-configs}
 mkdir -p $O
-B="timeout -k 10 300 python -u bench.py"
+B="timeout -k 10 300 python -u bench.py --full"
 $B --config c1 --steps 50 --warmup 5 --cpu-stride 1 > $O/c1_default_640x480_d4.json 2> $O/c1.err || exit 1
 $B --config c2 --depth 1 --steps 30 --warmup 3 --cpu-stride 8 > $O/c2_default_1920x1080_d1.json 2> $O/c2a.err || exit 2
 $B --config c2 --steps 30 --warmup 3 --cpu-stride 4 > $O/c2_default_1920x1080_d4.json 2> $O/c2b.err || exit 3

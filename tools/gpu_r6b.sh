@@ -7,4 +7,4 @@ bash tools/gpu_step.sh $O \
  "150 ab_c5 python -u tools/ab.py run --only base,div0,divsingle --scene stress4096 --depth 12 --frames 4 --rounds 6" \
  "100 ab_c2 python -u tools/ab.py run --only base,div0,divsingle --scene default --width 1920 --height 1080 --depth 4 --frames 20 --rounds 10" \
  "150 ab_split python -u tools/ab.py run --only base,tiles0 --scene default --width 480 --height 270 --depth 20 --ss 128 --frames 2 --rounds 5 --later-frame 2" \
- "300 shot128_n2 python -u bench.py --gpus 2 --one-device --backend gloo --config shot128"
+ "300 shot128_n2 python -u bench.py --full --gpus 2 --one-device --backend gloo --config shot128"

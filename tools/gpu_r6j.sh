@@ -8,4 +8,4 @@ bash tools/gpu_step.sh $O \
  "200 ab_c3 python -u tools/ab.py run --only $V --rounds 10" \
  "120 ab_c1 python -u tools/ab.py run --only $V --rounds 12 --scene default --width 640 --height 480 --depth 4 --frames 30" \
  "120 ab_c2d1 python -u tools/ab.py run --only $V --rounds 12 --scene default --width 1920 --height 1080 --depth 1 --frames 30" \
- "300 prof_c3 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof_c3 -o run -- python3 $R/bench.py --steps 20 --warmup 3 --no-cpu-baseline --no-c4"
+ "300 prof_c3 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof_c3 -o run -- python3 $R/bench.py --full --steps 20 --warmup 3 --no-cpu-baseline --no-c4"

@@ -4,7 +4,7 @@
 # pre-pass (head), and the RNG kernels' issue counters.
 O=gpurun_out/${1:-r6l}
 R=$PWD
-P="python3 $R/bench.py --steps 10 --warmup 2 --no-cpu-baseline --no-c4 --no-first-view"
+P="python3 $R/bench.py --full --steps 10 --warmup 2 --no-cpu-baseline --no-c4 --no-first-view"
 AB="python -u tools/ab.py run"
 bash tools/gpu_step.sh $O \
  "600 gpu_tests python -u -m pytest tests -m gpu -x -q --timeout 300 --timeout-method thread" \

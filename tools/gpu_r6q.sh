@@ -9,4 +9,4 @@ bash tools/gpu_step.sh $O \
  "400 ab_c3 $AB --only $V --rounds 8 --frames 32" \
  "300 ab_c2d4 $AB --only $V --rounds 8 --scene default --width 1920 --height 1080 --depth 4 --frames 64" \
  "400 ab_shot $AB --only $V --rounds 6 --scene default --width 1920 --height 1080 --depth 20 --ss 4 --frames 16" \
- "300 prof_c3 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof_c3 -o run -- python3 $R/bench.py --steps 20 --warmup 3 --no-cpu-baseline --no-c4"
+ "300 prof_c3 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof_c3 -o run -- python3 $R/bench.py --full --steps 20 --warmup 3 --no-cpu-baseline --no-c4"

@@ -5,13 +5,13 @@ R=$PWD
 O=$R/gpurun_out/${1:-round}
 mkdir -p $O
 timeout -k 10 600 python -u -m pytest tests -m gpu -x -v --timeout 300 --timeout-method thread > $O/gpu_tests.log 2>&1 || exit 1
-timeout -k 10 300 python -u bench.py --steps 20 --warmup 3 > $O/bench.json 2> $O/bench.err || exit 2
+timeout -k 10 300 python -u bench.py --full --steps 20 --warmup 3 > $O/bench.json 2> $O/bench.err || exit 2
 timeout -k 10 200 python -u tools/regionprof.py > $O/regionprof.json 2>&1 || exit 3
 timeout -k 10 200 python -u tools/segstats.py > $O/segstats.txt 2>&1 || exit 4
 cd /tmp && export TMPDIR=/tmp
-C3="$R/bench.py --steps 3 --warmup 1 --no-cpu-baseline"
-C5="$R/bench.py --config c5 --steps 2 --warmup 1 --no-cpu-baseline"
-timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof -o run -- python3 $R/bench.py --steps 10 --warmup 2 --no-cpu-baseline > $O/bench_prof.json 2> $O/bench_prof.err || exit 5
+C3="$R/bench.py --full --steps 3 --warmup 1 --no-cpu-baseline"
+C5="$R/bench.py --full --config c5 --steps 2 --warmup 1 --no-cpu-baseline"
+timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof -o run -- python3 $R/bench.py --full --steps 10 --warmup 2 --no-cpu-baseline > $O/bench_prof.json 2> $O/bench_prof.err || exit 5
 timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof_c5 -o run -- python3 $C5 > $O/bench_prof_c5.json 2> $O/bench_prof_c5.err || exit 6
 for cfg in C3 C5; do
   args=${!cfg}

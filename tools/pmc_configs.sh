@@ -17,7 +17,7 @@ run_cfg() {  # name  scene W H depth ss  bench args...   (PMC_ONLY="c3 c5 ..": o
   fi
   shift 6
   # steady-state frames only: no first-view frames and no same-run C4 frames in the per-dispatch means
-  local args="$R/bench.py $* --no-cpu-baseline --no-first-view --no-c4"
+  local args="$R/bench.py --full $* --no-cpu-baseline --no-first-view --no-c4"
   timeout -s KILL ${PMC_T:-120} rocprofv3 --pmc SQ_WAVES SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_SMEM SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_ACTIVE_INST_VALU SQ_THREAD_CYCLES_VALU --output-format csv -d $O/pmc1_$name -o run -- python3 $args > $O/pmc1_$name.log 2>&1 || return 7
   timeout -s KILL ${PMC_T:-120} rocprofv3 --pmc FETCH_SIZE --output-format csv -d $O/pmc2_$name -o run -- python3 $args > $O/pmc2_$name.log 2>&1 || return 8
   timeout -s KILL ${PMC_T:-120} rocprofv3 --pmc WRITE_SIZE --output-format csv -d $O/pmc3_$name -o run -- python3 $args > $O/pmc3_$name.log 2>&1 || return 9

@@ -17,7 +17,7 @@ import statistics
 import subprocess
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-DROPIN = os.path.join(ROOT, "tests", "native", "_build", "pulse_dropin")
+DROPIN = os.path.join(ROOT, "oracle", "_ref", "pulse_dropin")
 
 
 def session(policy: str, tick: int, W: int, H: int, tmp: str):
