@@ -25,7 +25,7 @@
 extern "C" {
 #endif
 
-#define RFX_ABI_VERSION 3
+#define RFX_ABI_VERSION 4
 
 typedef enum {
   RFX_OK = 0,
@@ -62,6 +62,14 @@ int rfx_scene_add_sphere(rfx_scene *scene, const float center[3], float radius, 
 /* Scene::addTriangle(v1, v2, v3, material) -- Scene.cpp:41-46, Triangle.cpp:11-21.  Returns the object index. */
 int rfx_scene_add_triangle(rfx_scene *scene, const float v1[3], const float v2[3], const float v3[3],
                            int material_type, const float rgb[3], float reflectivity, float transparency);
+/* A triangle mesh in one call: n_triangles calls of rfx_scene_add_triangle, in index order, on the vertices
+ * (vertices[3 i .. 3 i + 2] = vertex i) named by indices[3 t .. 3 t + 2] = (v1, v2, v3) of triangle t, all with one
+ * material; the same host precompute, the same object order.  Returns the first triangle's object index (the
+ * others follow consecutively; rfx_triangle_set_texture works on each).  An index >= n_vertices: RFX_ERR_ARG, and
+ * nothing is added. */
+int rfx_scene_add_mesh(rfx_scene *scene, const float *vertices, uint32_t n_vertices, const uint32_t *indices,
+                       uint32_t n_triangles, int material_type, const float rgb[3], float reflectivity,
+                       float transparency);
 /* Plane(pos, norm, material) -- Plane.cpp:9-14, traced by Plane::trace (Plane.cpp:36-73).  The reference's
  * Scene cannot hold a Plane (no addPlane); this is its natural extension: the plane takes an
  * object index in insertion order like any other object (closest-hit ties, shadow self-skip).  The normal is
@@ -85,6 +93,19 @@ int rfx_scene_set_skybox_file(rfx_scene *scene, const char *path);
 /* same, from memory (NULL -> checker) */
 int rfx_scene_set_skybox_argb(rfx_scene *scene, uint32_t width, uint32_t height, const uint32_t *argb);
 int rfx_scene_counts(const rfx_scene *scene, int *spheres, int *triangles, int *lights, int *textures);
+/* The triangle BVH rfx_renderer_set_scene would build for this scene (rfx_renderer_set_tri_accel), on the host: no
+ * renderer, no device.  counts[5] = {nodes, leaves, residual triangles, triangles per leaf, depth (internal levels)}
+ * is always written; call with the arrays NULL to size them, then again to fill those given:
+ *   boxes    : nodes x 12 floats -- child 0's box (lo x y z, hi x y z) then child 1's, as built (before the widening
+ *              by the cull margin that the device copy gets);
+ *   children : nodes x 2 -- c >= 0 an internal node, c < 0 the leaf ~c; the root is node 0;
+ *   leaf_ids : leaves x (triangles per leaf) triangle indices in insertion order (0 = the scene's first triangle),
+ *              -1 padding a partly filled leaf;
+ *   residual : the triangles outside the tree (an ill-conditioned or singular basis), which every ray tests.
+ * Returns 1 with a tree, 0 without one (a small scene, or the depth / node limits cannot be met: counts are 0 but
+ * for the leaf size), < 0 on error. */
+int rfx_scene_tri_bvh_dump(const rfx_scene *scene, int32_t counts[5], float *boxes, int32_t *children,
+                           int32_t *leaf_ids, int32_t *residual);
 
 /* ---------------------------------------------------------------- Camera */
 /* Camera(eye, at, fov): view = [ox | oy | oz] columns, row-major _11.._33 -- Camera.cpp:24-38 */
@@ -128,8 +149,27 @@ int rfx_renderer_set_regroup(rfx_renderer *r, int park_after);
  * Changes the schedule, never a value. */
 int rfx_renderer_set_regroup_sort(rfx_renderer *r, int on);
 /* Which bounce kernel the last trace launch ran: 0 = none (not regrouped), 1 = the global-memory BVH form, 2 = the
- * LDS-staged BVH form (large scenes whose BVH fits the LDS; 1 when the runtime refused its LDS size). */
+ * LDS-staged BVH form (large scenes whose sphere BVH fits the LDS; 1 when the runtime refused its LDS size).  The
+ * form speaks of the sphere BVH alone: a scene's triangle BVH is read from global memory in either form (a mesh
+ * without a sphere BVH runs form 1), and only the lanes' traversal stacks are shared with it. */
 int rfx_renderer_bounce_form(const rfx_renderer *r);
+/* Triangle BVH of scenes with more than 32 spheres or more than 32 triangles (no pixel changes): -1 (default) = built
+ * for scenes of at least 128 triangles, 0 = off (every ray tests the triangles in 64-wide chunks, culled by the wave
+ * bundle only), 1 = built whenever the scene is not small and the tree meets the kernels' limits (16 levels, 32767
+ * nodes); 2 = as 1, and narrow bundles (a tile's primary rays) walk the tree too instead of culling every triangle's
+ * bound for the wave -- measured slower on all but one scene, kept for A/B timing and the tests.  Takes
+ * effect at the next rfx_renderer_set_scene. */
+int rfx_renderer_set_tri_accel(rfx_renderer *r, int mode);
+/* The hierarchies of the uploaded scene (RFX_ERR_STATE without one): all zero where none was built. */
+typedef struct {
+  int32_t tri_nodes, tri_depth;   /* triangle BVH: nodes, internal levels */
+  int32_t tri_leaf_size;          /* triangles per leaf of this build */
+  int32_t tri_in_leaves;          /* triangles the tree holds */
+  int32_t tri_residual;           /* triangles outside it, tested by every ray */
+  int32_t sph_nodes, sph_depth;   /* sphere-pair BVH */
+  int32_t narrow_tri_bvh;         /* 1: narrow bundles (a tile's primary rays) walk the triangle tree too */
+} rfx_accel_info;
+int rfx_renderer_accel_info(const rfx_renderer *r, rfx_accel_info *out);
 /* Primary-bundle cull masks of small-scene plain frames and of SSAA frames run one sample per lane (sampleNum 2, 4,
  * 8, and jittered sampleNum 1) (no pixel changes): the first segment's cull masks of every wave tile, computed by one
  * extra launch for a view (camera, frame geometry, sampling, scene) and reused while the view stays.  1 (default) = built when a view repeats (the second frame of a still camera on), so a camera that

@@ -13,7 +13,7 @@ from . import _build
 
 RFX_OK = 0
 RFX_NCOUNTERS = 40
-RFX_ABI_VERSION = 3
+RFX_ABI_VERSION = 4
 METAL, DIELECTRIC = 0, 1
 
 _fp = C.POINTER(C.c_float)
@@ -38,6 +38,14 @@ class Frame(C.Structure):
     ]
 
 
+class AccelInfo(C.Structure):
+    """rfx_accel_info (include/rfx.h)."""
+    _fields_ = [(n, C.c_int32) for n in ("tri_nodes", "tri_depth", "tri_leaf_size", "tri_in_leaves", "tri_residual",
+                                         "sph_nodes", "sph_depth", "narrow_tri_bvh")]
+
+
+_i32p = C.POINTER(C.c_int32)
+
 # (name, restype, argtypes) for every symbol of include/rfx.h
 SIGNATURES = [
     ("rfx_abi_version", C.c_int, []),
@@ -47,6 +55,8 @@ SIGNATURES = [
     ("rfx_scene_destroy", None, [C.c_void_p]),
     ("rfx_scene_add_sphere", C.c_int, [C.c_void_p, _fp, C.c_float, C.c_int, _fp, C.c_float, C.c_float]),
     ("rfx_scene_add_triangle", C.c_int, [C.c_void_p, _fp, _fp, _fp, C.c_int, _fp, C.c_float, C.c_float]),
+    ("rfx_scene_add_mesh", C.c_int, [C.c_void_p, _fp, C.c_uint32, _u32p, C.c_uint32, C.c_int, _fp, C.c_float, C.c_float]),
+    ("rfx_scene_tri_bvh_dump", C.c_int, [C.c_void_p, _i32p, _fp, _i32p, _i32p, _i32p]),
     ("rfx_scene_add_plane", C.c_int, [C.c_void_p, _fp, _fp, C.c_int, _fp, C.c_float, C.c_float]),
     ("rfx_scene_plane_count", C.c_int, [C.c_void_p]),
     ("rfx_triangle_set_texture", C.c_int, [C.c_void_p, C.c_int, C.c_int, _fp]),
@@ -100,6 +110,8 @@ SIGNATURES = [
     ("rfx_renderer_set_regroup_sort", C.c_int, [C.c_void_p, C.c_int]),
     ("rfx_renderer_set_launch_traces", C.c_int, [C.c_void_p, C.c_uint64]),
     ("rfx_renderer_bounce_form", C.c_int, [C.c_void_p]),
+    ("rfx_renderer_set_tri_accel", C.c_int, [C.c_void_p, C.c_int]),
+    ("rfx_renderer_accel_info", C.c_int, [C.c_void_p, C.POINTER(AccelInfo)]),
     ("rfx_renderer_get_timing", C.c_int, [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_double), _u64p]),
     ("rfx_device_alloc", C.c_int, [C.c_void_p, C.c_size_t, C.POINTER(C.c_void_p)]),
     ("rfx_device_free", C.c_int, [C.c_void_p, C.c_void_p]),

@@ -188,6 +188,25 @@ extern "C" int rfx_scene_add_triangle(rfx_scene *s, const float a[3], const floa
   return t.obj;
 }
 
+extern "C" int rfx_scene_add_mesh(rfx_scene *s, const float *vertices, uint32_t n_vertices, const uint32_t *indices,
+                                  uint32_t n_triangles, int type, const float rgb[3], float refl, float transp)
+{
+  if (!s || !rgb || (type != RFX_METAL && type != RFX_DIELECTRIC) || (n_triangles && (!vertices || !indices)))
+    return fail(RFX_ERR_ARG, "add_mesh: bad args");
+  for (size_t i = 0; i < 3 * (size_t)n_triangles; ++i)
+    if (indices[i] >= n_vertices)
+      return fail(RFX_ERR_ARG, "add_mesh: index %u of triangle %zu is not below %u vertices", indices[i], i / 3, n_vertices);
+  const int first = (int)s->obj_kind.size();
+  s->tris.reserve(s->tris.size() + n_triangles);
+  for (size_t i = 0; i < n_triangles; ++i)
+  {
+    const int rc = rfx_scene_add_triangle(s, vertices + 3 * (size_t)indices[3 * i], vertices + 3 * (size_t)indices[3 * i + 1],
+                                          vertices + 3 * (size_t)indices[3 * i + 2], type, rgb, refl, transp);
+    if (rc < 0) return rc;
+  }
+  return first;
+}
+
 extern "C" int rfx_scene_add_plane(rfx_scene *s, const float pos[3], const float norm[3], int type, const float rgb[3],
                                    float refl, float transp)                         // Plane.cpp:9-14
 {
@@ -478,6 +497,17 @@ constexpr size_t kPrimLargeWords = 12;  // per wave tile, large scenes (rfx_trac
 // above park-3 unsorted).  Park order keeps a tile's survivors together, which a coarse cell key cannot beat.
 #define RFX_QUEUE_SORT 0
 #endif
+#ifndef RFX_TRI_BVH_AUTO_MIN
+// rfx_renderer_set_tri_accel(-1): the triangle count from which a non-small scene gets the triangle BVH (DESIGN.md
+// "Triangle BVH": the smallest measured soup size at which the tree wins)
+#define RFX_TRI_BVH_AUTO_MIN 128
+#endif
+#ifndef RFX_TRI_BVH_NARROW_MIN
+// the triangle count from which narrow bundles (a tile's primary rays) walk the triangle BVH too instead of culling
+// every triangle's bound for the wave: never by default -- the bundle cull won on every soup from 64 to 100,000
+// triangles (0.8% to 15% less trace time) and lost 1% on a 2,560-triangle height field (DESIGN.md "Triangle BVH")
+#define RFX_TRI_BVH_NARROW_MIN (1 << 30)
+#endif
 #ifndef RFX_PARK_AFTER
 #define RFX_PARK_AFTER 2  // large-scene plain frames: segments before a live trace is parked for the bounce kernel
 #endif
@@ -582,6 +612,9 @@ struct rfx_renderer {
   std::vector<uint8_t> prim_seen;  // the view of the last plain small-scene launch
   uint64_t scene_gen = 0;  // bumped by every set_scene
   int prim_mode = 1;       // rfx_renderer_set_prim_masks
+  int tri_accel = -1;      // rfx_renderer_set_tri_accel: -1 automatic (RFX_TRI_BVH_AUTO_MIN triangles), 0 off, 1 on,
+                           // 2 on with the narrow bundles walking the tree too
+  rfx_accel_info accel{};  // the uploaded scene's hierarchies (rfx_renderer_accel_info)
   int bounce_form = 0;     // the last trace launch's bounce kernel: 0 none, 1 global-memory BVH, 2 LDS-staged BVH
   QRay *d_queue = nullptr;
   uint64_t queue_cap = 0;
@@ -836,7 +869,7 @@ namespace {
 struct PairBox { double lo[3], hi[3], c[3]; };
 
 int build_pair_bvh(std::vector<BvhNode> &nodes, std::vector<uint32_t> &pairs, size_t a, size_t b,
-                   const std::vector<PairBox> &box, const double *ref, int level, int &depth)
+                   const std::vector<PairBox> &box, const double *ref, int level, int &depth, bool widen = true)
 {
   if (b - a == 1) return ~(int)pairs[a];
   depth = std::max(depth, level + 1);
@@ -893,8 +926,8 @@ int build_pair_bvh(std::vector<BvhNode> &nodes, std::vector<uint32_t> &pairs, si
   std::nth_element(pairs.begin() + a, pairs.begin() + mid, pairs.begin() + b, [&](uint32_t x, uint32_t y) {
     return box[x].c[axis] < box[y].c[axis] || (box[x].c[axis] == box[y].c[axis] && x < y);
   });
-  const int kids[2] = {build_pair_bvh(nodes, pairs, a, mid, box, ref, level + 1, depth),
-                       build_pair_bvh(nodes, pairs, mid, b, box, ref, level + 1, depth)};
+  const int kids[2] = {build_pair_bvh(nodes, pairs, a, mid, box, ref, level + 1, depth, widen),
+                       build_pair_bvh(nodes, pairs, mid, b, box, ref, level + 1, depth, widen)};
   const size_t range[2][2] = {{a, mid}, {mid, b}};
   BvhNode &n = nodes[id];
   for (int c = 0; c < 2; ++c)
@@ -903,6 +936,7 @@ int build_pair_bvh(std::vector<BvhNode> &nodes, std::vector<uint32_t> &pairs, si
     for (size_t i = range[c][0]; i < range[c][1]; ++i)
       for (int k = 0; k < 3; ++k) { l[k] = fmin(l[k], box[pairs[i]].lo[k]); h[k] = fmax(h[k], box[pairs[i]].hi[k]); }
 #if RFX_BVH_PREWIDE
+    if (widen)  // (false: rfx_scene_tri_bvh_dump, the boxes as built)
     {
       // the box grown by the node part of the kernel's margin, kCullRel mt[c] (rfx_trace.h kCullRel = 2e-3), from the
       // float mt the kernel would have used, with a relative 1e-6 on top
@@ -940,11 +974,153 @@ int build_pair_bvh(std::vector<BvhNode> &nodes, std::vector<uint32_t> &pairs, si
   }
   return id;
 }
+
+// Triangle BVH of a non-small scene (rfx_types.h RFX_TRI_BVH).  The triangles with a well-conditioned basis
+// (cond < 300: their reported hits lie within the cull margin of their vertices, see the bounds in
+// rfx_renderer_set_scene) are put in spatial order -- recursive median splits of the centroids along their longest
+// axis, left parts a multiple of the leaf size -- so every aligned run of RFX_TRI_BVH_LEAF is a compact leaf; the
+// leaves' vertex boxes then take the pair builder above (SAH within its depth budget).  Every other triangle
+// (cond >= 300, a singular basis) goes to the residual list.  The scene's arrays are not reordered: order[] lists
+// insertion indices, leaf g = order[RFX_TRI_BVH_LEAF g ..], -1 padding the last leaf.
+struct TriTree {
+  std::vector<BvhNode> nodes;
+  std::vector<int32_t> order;  // leaves x RFX_TRI_BVH_LEAF insertion indices (-1: padding)
+  std::vector<int32_t> resid;
+  int depth = 0;
+  size_t leaves() const { return order.size() / RFX_TRI_BVH_LEAF; }
+};
+
+void tri_spatial_order(std::vector<int32_t> &idx, size_t a, size_t b, const std::vector<double> &cen)
+{
+  if (b - a <= RFX_TRI_BVH_LEAF) return;
+  double lo[3] = {INFINITY, INFINITY, INFINITY}, hi[3] = {-INFINITY, -INFINITY, -INFINITY};
+  for (size_t i = a; i < b; ++i)
+    for (int k = 0; k < 3; ++k) { lo[k] = fmin(lo[k], cen[3 * idx[i] + k]); hi[k] = fmax(hi[k], cen[3 * idx[i] + k]); }
+  int axis = 0;
+  for (int k = 1; k < 3; ++k)
+    if (hi[k] - lo[k] > hi[axis] - lo[axis]) axis = k;
+  const size_t groups = (b - a + RFX_TRI_BVH_LEAF - 1) / RFX_TRI_BVH_LEAF;
+  const size_t mid = a + RFX_TRI_BVH_LEAF * (groups / 2);
+  std::nth_element(idx.begin() + a, idx.begin() + mid, idx.begin() + b, [&](int32_t x, int32_t y) {
+    return cen[3 * x + axis] < cen[3 * y + axis] || (cen[3 * x + axis] == cen[3 * y + axis] && x < y);
+  });
+  tri_spatial_order(idx, a, mid, cen);
+  tri_spatial_order(idx, mid, b, cen);
+}
+
+// false: no tree (fewer than two leaves, deeper than the kernel's stack, or more nodes / leaves than an int16 stack
+// slot holds) -- the kernels keep their 64-triangle chunk loops
+bool build_tri_tree(const std::vector<HostTri> &tris, const double *ref, bool widen, TriTree &T)
+{
+  T = TriTree{};
+  std::vector<int32_t> idx;
+  for (size_t i = 0; i < tris.size(); ++i)
+    (tris[i].cond < 300.0 ? idx : T.resid).push_back((int32_t)i);
+  const size_t nleaf = (idx.size() + RFX_TRI_BVH_LEAF - 1) / RFX_TRI_BVH_LEAF;
+  if (nleaf < 2 || nleaf > 32768) { T.resid.clear(); return false; }
+  std::vector<double> cen(3 * tris.size(), 0.0);
+  for (int32_t i : idx)
+  {
+    const HostTri &t = tris[i];
+    cen[3 * i] = ((double)t.v0.x + t.v1.x + t.v2.x) / 3.0;
+    cen[3 * i + 1] = ((double)t.v0.y + t.v1.y + t.v2.y) / 3.0;
+    cen[3 * i + 2] = ((double)t.v0.z + t.v1.z + t.v2.z) / 3.0;
+  }
+  tri_spatial_order(idx, 0, idx.size(), cen);
+  T.order.assign(nleaf * RFX_TRI_BVH_LEAF, -1);
+  std::copy(idx.begin(), idx.end(), T.order.begin());
+  std::vector<PairBox> box(nleaf);
+  for (size_t g = 0; g < nleaf; ++g)
+  {
+    PairBox &b = box[g];
+    for (int k = 0; k < 3; ++k) { b.lo[k] = INFINITY; b.hi[k] = -INFINITY; }
+    for (int e = 0; e < RFX_TRI_BVH_LEAF; ++e)
+    {
+      const int32_t i = T.order[RFX_TRI_BVH_LEAF * g + e];
+      if (i < 0) continue;
+      for (const v3 &q : {tris[i].v0, tris[i].v1, tris[i].v2})
+      {
+        const double c[3] = {q.x, q.y, q.z};
+        for (int k = 0; k < 3; ++k) { b.lo[k] = fmin(b.lo[k], c[k]); b.hi[k] = fmax(b.hi[k], c[k]); }
+      }
+    }
+    for (int k = 0; k < 3; ++k) b.c[k] = 0.5 * (b.lo[k] + b.hi[k]);
+  }
+  std::vector<uint32_t> leaves(nleaf);
+  for (size_t g = 0; g < nleaf; ++g) leaves[g] = (uint32_t)g;
+  build_pair_bvh(T.nodes, leaves, 0, nleaf, box, ref, 0, T.depth, widen);
+  if (T.depth > RFX_BVH_STACK || T.nodes.size() > 32767) { T = TriTree{}; return false; }
+  return true;
+}
 }  // namespace
 
 #ifndef RFX_BVH_STACK
 #define RFX_BVH_STACK 16  // the kernel's per-lane traversal stack (rfx_trace.h kBvhStack)
 #endif
+
+// the margin reference point both trees measure from: the sphere BVH's root box centre, or -- no sphere BVH (at most
+// 32 spheres) -- the centre of the triangles' vertex box
+static void tri_ref_point(const std::vector<HostTri> &tris, double *ref)
+{
+  double lo[3] = {INFINITY, INFINITY, INFINITY}, hi[3] = {-INFINITY, -INFINITY, -INFINITY};
+  for (const HostTri &t : tris)
+  {
+    if (!(t.cond < 300.0)) continue;
+    for (const v3 &q : {t.v0, t.v1, t.v2})
+    {
+      const double c[3] = {q.x, q.y, q.z};
+      for (int k = 0; k < 3; ++k) { lo[k] = fmin(lo[k], c[k]); hi[k] = fmax(hi[k], c[k]); }
+    }
+  }
+  for (int k = 0; k < 3; ++k) ref[k] = lo[k] <= hi[k] ? (double)(float)(0.5 * (lo[k] + hi[k])) : 0.0;
+}
+
+extern "C" int rfx_scene_tri_bvh_dump(const rfx_scene *s, int32_t counts[5], float *boxes, int32_t *children,
+                                      int32_t *leaf_ids, int32_t *residual)
+{
+  if (!s || !counts) return fail(RFX_ERR_ARG, "tri_bvh_dump: bad args");
+  for (int k = 0; k < 5; ++k) counts[k] = 0;
+  counts[3] = RFX_TRI_BVH_LEAF;
+  if (s->spheres.size() <= 32 && s->tris.size() <= 32) return 0;  // a small scene: no tree
+  TriTree T;
+  double ref[3];
+  tri_ref_point(s->tris, ref);
+  if (!build_tri_tree(s->tris, ref, false, T)) return 0;
+  counts[0] = (int32_t)T.nodes.size();
+  counts[1] = (int32_t)T.leaves();
+  counts[2] = (int32_t)T.resid.size();
+  counts[4] = T.depth;
+  for (size_t i = 0; i < T.nodes.size(); ++i)
+  {
+    const BvhNode &n = T.nodes[i];
+    if (boxes)
+      for (int c = 0; c < 2; ++c)
+      {
+        float *b = boxes + 12 * i + 6 * c;
+        b[0] = n.lx[c]; b[1] = n.ly[c]; b[2] = n.lz[c]; b[3] = n.hx[c]; b[4] = n.hy[c]; b[5] = n.hz[c];
+      }
+    if (children) { children[2 * i] = n.child[0]; children[2 * i + 1] = n.child[1]; }
+  }
+  if (leaf_ids) std::copy(T.order.begin(), T.order.end(), leaf_ids);
+  if (residual) std::copy(T.resid.begin(), T.resid.end(), residual);
+  return 1;
+}
+
+extern "C" int rfx_renderer_set_tri_accel(rfx_renderer *r, int mode)
+{
+  if (!r || mode < -1 || mode > 2)
+    return fail(RFX_ERR_ARG, "renderer_set_tri_accel: -1 (automatic), 0 (off), 1 (on) or 2 (on, narrow bundles too)");
+  r->tri_accel = mode;
+  return RFX_OK;
+}
+
+extern "C" int rfx_renderer_accel_info(const rfx_renderer *r, rfx_accel_info *out)
+{
+  if (!r || !out) return fail(RFX_ERR_ARG, "renderer_accel_info: bad args");
+  if (!r->has_scene) return fail(RFX_ERR_STATE, "renderer_accel_info: no scene");
+  *out = r->accel;
+  return RFX_OK;
+}
 
 extern "C" int rfx_renderer_set_scene(rfx_renderer *r, const rfx_scene *s)
 {
@@ -1148,6 +1324,29 @@ extern "C" int rfx_renderer_set_scene(rfx_renderer *r, const rfx_scene *s)
     if (bvh_depth > RFX_BVH_STACK) { bvh.clear(); bvh_depth = 0; }  // deeper than the kernel's stack: chunk loops
     if (bvh.size() > 32767 || npairs > 32768) { bvh.clear(); bvh_depth = 0; }  // int16 stack slots (rfx_trace.h)
   }
+  // triangle BVH (rfx_types.h RFX_TRI_BVH), when rfx_renderer_set_tri_accel asks for it: the nodes, the leaves' copy
+  // of the triangle records and the residual list
+  TriTree tt;
+  std::vector<TriGeo> tleaf;
+  const bool want_tri = RFX_TRI_BVH && !small &&
+                        (r->tri_accel >= 1 || (r->tri_accel < 0 && s->tris.size() >= (size_t)RFX_TRI_BVH_AUTO_MIN));
+  if (want_tri)
+  {
+    if (nsph <= 32) tri_ref_point(s->tris, bvh_ref);
+    if (build_tri_tree(s->tris, bvh_ref, true, tt))
+    {
+      tleaf.assign(tt.order.size(), TriGeo{});
+      for (size_t q = 0; q < tt.order.size(); ++q)
+      {
+        const int32_t i = tt.order[q];
+        if (i < 0) continue;  // padding: all zero, never hit
+        tleaf[q] = tg[i];
+        const int32_t obj = s->tris[i].obj;
+        memcpy(&tleaf[q].pad[0], &i, 4);
+        memcpy(&tleaf[q].pad[1], &obj, 4);
+      }
+    }
+  }
   std::vector<PlaneGeo> pg;
   std::vector<MatRec> pm;
   for (const HostPlane &p : s->planes)
@@ -1183,8 +1382,22 @@ extern "C" int rfx_renderer_set_scene(rfx_renderer *r, const rfx_scene *s)
       (rc = upload(r, lr, &d.lights)) || (rc = upload(r, tr, &d.texs)) || (rc = upload(r, pool, &d.texels)) ||
       (rc = upload(r, bd, &d.bound)) || (rc = upload(r, cs, &d.cull_small)) || (rc = upload(r, ct, &d.cull_tri)) || (rc = upload(r, cb, &d.chunk_bound)) ||
       (rc = upload(r, pg, &d.pln_geo)) || (rc = upload(r, pm, &d.pln_mat)) || (rc = upload(r, loc, &d.obj_loc)) ||
-      (rc = upload(r, bvh, &d.bvh)))
+      (rc = upload(r, bvh, &d.bvh)) || (rc = upload(r, tt.nodes, &d.tri_bvh)) || (rc = upload(r, tleaf, &d.tri_leaf)) ||
+      (rc = upload(r, tt.resid, &d.tri_resid)))
     return rc;
+  d.n_tri_resid = (int32_t)tt.resid.size();
+  d.n_tri_bvh = (int32_t)tt.nodes.size();
+  d.tri_bvh_depth = tt.depth;
+  r->accel = rfx_accel_info{};
+  r->accel.tri_nodes = d.n_tri_bvh;
+  r->accel.tri_depth = tt.depth;
+  r->accel.tri_leaf_size = RFX_TRI_BVH_LEAF;
+  r->accel.tri_in_leaves = tt.nodes.empty() ? 0 : (int32_t)(s->tris.size() - tt.resid.size());
+  r->accel.tri_residual = d.n_tri_resid;
+  r->accel.sph_nodes = (int32_t)bvh.size();
+  r->accel.sph_depth = bvh_depth;
+  d.tri_bvh_narrow = !tt.nodes.empty() && (r->tri_accel == 2 || s->tris.size() >= (size_t)RFX_TRI_BVH_NARROW_MIN);
+  r->accel.narrow_tri_bvh = d.tri_bvh_narrow;
   {
     // the bounce kernel's LDS copy of the node links and margin terms (rfx_types.h DevScene::bvh_aux): mt rounded up
     // to a multiple of mstep (one step more than the ceiling, so the float decode stays above)
@@ -1638,7 +1851,8 @@ static int trace_frame(rfx_renderer *r, FramePlan &pl, const uint32_t *rd, float
     const uint64_t waves = (pl.traces + 63) / 64;
     const uint32_t groups = (uint32_t)std::min<uint64_t>((waves + 1) / 2, (uint64_t)r->cus * RFX_BOUNCE_GROUPS_PER_CU);
     const int cfg = 1 | (r->dev.n_light > 32 ? 2 : 0) | (small ? 4 : 0) | (r->dev.n_pln ? 8 : 0) |  // rfx_trace.h kCfg*
-                    (RFX_ONE_LIGHT && r->dev.n_light == 1 ? 32 : 0);  // kCfgOneLight (rfx_trace_plain_park.hip)
+                    (RFX_ONE_LIGHT && r->dev.n_light == 1 ? 32 : 0) |  // kCfgOneLight (rfx_trace_plain_park.hip)
+                    (RFX_TRI_BVH && r->dev.tri_bvh ? 64 : 0);            // kCfgTriBvh
     if (sort_queue) HIP_CHECK(launch_queue_sort(r->d_qctr, r->d_qkey, r->d_qctr + 2, r->d_qorder, st));
     // a BVH whose nodes fit the workgroup's LDS (56 B each beside the stacks: up to ~2,100 nodes, i.e. 4,200 spheres):
     // the LDS-staged bounce kernel, one 16-wave workgroup per CU (C5 trace + bounce -4..6%, tools/ab.py); else the

@@ -1310,7 +1310,8 @@ hipError_t launch_trace(const DevScene &S, const FrameParams &P, bool stats, hip
                                 trace_tiles(P) <= (uint32_t)RFX_NOCULL_MAX_TILES);
   const int cfg = (S.n_light > 32 ? kCfgManyLights : 0) | (cull ? kCfgCull : 0) |
                   (S.n_sph <= 32 && S.n_tri <= 32 ? kCfgSmall : 0) | (S.n_pln > 0 ? kCfgPlanes : 0) |
-                  (S.n_light == 1 && !stats && RFX_ONE_LIGHT ? kCfgOneLight : 0);
+                  (S.n_light == 1 && !stats && RFX_ONE_LIGHT ? kCfgOneLight : 0) |
+                  (RFX_TRI_BVH && S.tri_bvh != nullptr && !stats ? kCfgTriBvh : 0);
   launch_mode_cfg(stats, mode, cfg, grid, S, Pt, st);
   return hipGetLastError();
 }

@@ -1135,6 +1135,136 @@ __device__ __forceinline__ int occluded_spheres_bvh(const DevScene &S, v3 o, v3 
   }
 }
 
+#if RFX_TRI_BVH
+// ------------------------------------------------------------- non-small scenes: per-ray triangle BVH
+// The same walk over the triangle tree (rfx_types.h RFX_TRI_BVH, rfx_host.cpp build_tri_tree).  A child box is the
+// AABB of its triangles' vertices under the margin of the sphere boxes: a triangle in the tree (cond < 300) reports a
+// hit only where the ray passes within kCullRel |o - p| of a point p of the triangle (DESIGN.md "Triangle BVH"), and
+// the box grown by kCullRel (|o - centre| + half-diagonal) + 1e-6 per axis holds that neighbourhood of every p
+// inside it -- so a box the ray misses holds no triangle the reference could report, and a reported hit lies at or
+// beyond the entry distance of its box (the h.sq 1.001 reject).  Nodes are read from global memory in every kernel
+// form; the lane's stack is the sphere walk's (the two walks run one after the other).  Leaves run the exact test
+// with the (distance, object index) rule, so the visiting order changes no result; h.i is the insertion index.
+// The residual triangles (DevScene::tri_resid) are tested by every ray after the walk.
+__device__ __forceinline__ int tri_rec_int(float bits) { return __builtin_bit_cast(int, bits); }
+
+template <bool STATS, class NS>
+__device__ __forceinline__ void closest_tris_bvh(const DevScene &S, v3 origin, v3 ray, const RayConst &k, Hit &h,
+                                                 Cnt &cnt, const NS &ns)
+{
+  const RayInv ri = ray_inv(S, origin, ray);
+  const float a = 0.5f * k.a2;                // |ray|^2 (exact: a2 = 2a)
+  BvhSlot *stack = ns.stack();
+  int sp = 0, node = 0;
+  for (;;)
+  {
+    if (node >= 0)
+    {
+      const BvhNode n = S.tri_bvh[node];
+      float t0, t1;
+      // a child entered beyond the best hit cannot hold a closer (or tying) triangle
+      const bool h0 = bvh_box(n, 0, origin, ri, t0) && !(t0 * t0 * a > h.sq * 1.001f);
+      const bool h1 = bvh_box(n, 1, origin, ri, t1) && !(t1 * t1 * a > h.sq * 1.001f);
+      if (h0 && h1)
+      {
+        const bool first0 = !(t1 < t0);
+        stack[NS::kStride * sp++] = first0 ? n.child[1] : n.child[0];
+        node = first0 ? n.child[0] : n.child[1];
+        continue;
+      }
+      if (h0 || h1)
+      {
+        node = h0 ? n.child[0] : n.child[1];
+        continue;
+      }
+    }
+    else
+    {
+#pragma unroll
+      for (int e = 0; e < RFX_TRI_BVH_LEAF; ++e)
+      {
+        const TriGeo &g = S.tri_leaf[RFX_TRI_BVH_LEAF * ~node + e];
+        float t, u, v, sq;
+        if (tri_hit<STATS, false>(g, origin, ray, t, u, v, sq, cnt, k, h.sq))
+        {
+          const int obj = tri_rec_int(g.pad[1]);
+          const float key = hit_key(sq);
+          if (tri_takes(key, h.sq, obj, h.obj))
+          {
+            h.sq = key; h.obj = obj; h.kind = 1; h.i = tri_rec_int(g.pad[0]); h.t = t; h.u = u; h.v = v;
+          }
+        }
+      }
+    }
+    if (sp == 0) break;
+    node = stack[NS::kStride * --sp];
+  }
+  for (int q = 0; q < S.n_tri_resid; ++q)
+  {
+    const int i = S.tri_resid[q];
+    float t, u, v, sq;
+    if (tri_hit<STATS, false>(S.tri_geo[i], origin, ray, t, u, v, sq, cnt, k, h.sq))
+    {
+      const int obj = S.tri_shade[i].obj;
+      const float key = hit_key(sq);
+      if (tri_takes(key, h.sq, obj, h.obj))
+      {
+        h.sq = key; h.obj = obj; h.kind = 1; h.i = i; h.t = t; h.u = u; h.v = v;
+      }
+    }
+  }
+}
+
+// any triangle but skip_tri (an insertion index) occludes the shadow ray (Scene.cpp:129-141 restricted to the
+// triangles); the hit object is filtered out after its test, which does not change the boolean
+template <bool STATS, class NS>
+__device__ __forceinline__ bool occluded_tris_bvh(const DevScene &S, v3 o, v3 ray, const RayConst &k, int skip_tri,
+                                                  Cnt &cnt, const NS &ns)
+{
+  float t, u, v, sq;
+  const RayInv ri = ray_inv(S, o, ray);
+  BvhSlot *stack = ns.stack();
+  int sp = 0, node = 0;
+  for (;;)
+  {
+    if (node >= 0)
+    {
+      const BvhNode n = S.tri_bvh[node];
+      float t0, t1;
+      const bool h0 = bvh_box(n, 0, o, ri, t0), h1 = bvh_box(n, 1, o, ri, t1);
+      if (h0 && h1)
+      {
+        stack[NS::kStride * sp++] = n.child[1];
+        node = n.child[0];
+        continue;
+      }
+      if (h0 || h1)
+      {
+        node = h0 ? n.child[0] : n.child[1];
+        continue;
+      }
+    }
+    else
+    {
+#pragma unroll
+      for (int e = 0; e < RFX_TRI_BVH_LEAF; ++e)
+      {
+        const TriGeo &g = S.tri_leaf[RFX_TRI_BVH_LEAF * ~node + e];
+        if (tri_hit<STATS, true, true>(g, o, ray, t, u, v, sq, cnt, k) && tri_rec_int(g.pad[0]) != skip_tri) return true;
+      }
+    }
+    if (sp == 0) break;
+    node = stack[NS::kStride * --sp];
+  }
+  for (int q = 0; q < S.n_tri_resid; ++q)
+  {
+    const int i = S.tri_resid[q];
+    if (tri_hit<STATS, true, true>(S.tri_geo[i], o, ray, t, u, v, sq, cnt, k) && i != skip_tri) return true;
+  }
+  return false;
+}
+#endif  // RFX_TRI_BVH
+
 // The planes (Scene::addPlane extension, Plane.cpp:36-73) for one lane, after the other kinds: every lane that
 // traces tests every plane (an infinite plane has no bounding sphere to cull with).
 template <bool STATS>
@@ -1172,7 +1302,7 @@ __device__ __forceinline__ bool occluded_planes(const DevScene &S, v3 o, v3 ray,
 // Large scenes: the spheres are stored in spatial order (recursive median splits), 64 to a chunk with a bounding sphere;
 // the bundle culls whole chunks (one lane per chunk), then the spheres of the surviving chunks.  The
 // visiting order is then not the insertion order, so spheres take the general (distance, object) rule.
-template <bool STATS, bool PLANES, class NS = BvhGlobal>
+template <bool STATS, bool PLANES, bool TBVH = false, class NS = BvhGlobal>
 __device__ __forceinline__ void closest_hit(const DevScene &S, v3 origin, v3 ray, bool live, const Bundle *B, Hit &h,
                                             Cnt &cnt, const NS &ns = NS{}, const uint64_t *pl = nullptr)
 {
@@ -1240,7 +1370,17 @@ __device__ __forceinline__ void closest_hit(const DevScene &S, v3 origin, v3 ray
   RFX_CULL_STAT_LARGE(2, cull, __ballot(live), st_chunks, st_sph, st_pairs);
 #endif
   RFX_PROF_BEGIN(P_TRI);
-  for (int first = 0; first < S.n_tri; first += 64)
+  // the triangle tree, lane by lane (rfx_types.h RFX_TRI_BVH; TBVH: the kernel instantiations of scenes that have
+  // one): wide bundles, and narrow ones where the host says so (DevScene::tri_bvh_narrow)
+  bool use_tbvh = false;
+#if RFX_TRI_BVH
+  if constexpr (TBVH && !STATS)
+  {
+    use_tbvh = !listed && S.tri_bvh != nullptr && (S.tri_bvh_narrow || !(cull && B->cosa > kNarrowBundleCos));
+    if (use_tbvh && live) closest_tris_bvh<STATS>(S, origin, ray, k, h, cnt, ns);
+  }
+#endif
+  for (int first = 0; !use_tbvh && first < S.n_tri; first += 64)
   {
     const int n = min(64, S.n_tri - first);
     uint64_t m = listed ? pl[1] : (B && B->ok) ? cull_chunk(S.bound, S.n_sph + first, n, *B) : all_bits(n);
@@ -1385,7 +1525,7 @@ __device__ __forceinline__ bool occluded_small(const DevScene &S, v3 o, v3 ray, 
 // lane has one.  (Spheres precede triangles, the reference's order for scenes whose objects are added
 // spheres-first -- then even the event counters match it: the second sphere of a pair is counted only
 // when the first did not occlude.)
-template <bool STATS, bool PLANES, class NS = BvhGlobal>
+template <bool STATS, bool PLANES, bool TBVH = false, class NS = BvhGlobal>
 __device__ __forceinline__ bool occluded(const DevScene &S, v3 o, v3 ray, bool live, int skip_sph, int skip_tri,
                                          int skip_pln, const Bundle *B, Cnt &cnt, const NS &ns = NS{}, int *hint = nullptr)
 {
@@ -1444,7 +1584,15 @@ __device__ __forceinline__ bool occluded(const DevScene &S, v3 o, v3 ray, bool l
       }
     }
   }
-  for (int first = 0; first < S.n_tri; first += 64)
+  bool use_tbvh = false;
+#if RFX_TRI_BVH
+  if constexpr (TBVH && !STATS)
+  {
+    use_tbvh = S.tri_bvh != nullptr;
+    if (use_tbvh && live && !occ) occ = occluded_tris_bvh<STATS>(S, o, ray, k, skip_tri, cnt, ns);
+  }
+#endif
+  for (int first = 0; !use_tbvh && first < S.n_tri; first += 64)
   {
     if (__ballot(live && !occ) == 0) return occ;
     const int n = min(64, S.n_tri - first);
@@ -1563,7 +1711,8 @@ __device__ __forceinline__ const FrameParams &kernarg_params()
   return *(const FrameParams *)(const __attribute__((address_space(4))) FrameParams *)(p + kParamsOff);
 }
 
-template <bool STATS, bool CULL, bool MANYL, bool SMALL, bool PLANES, bool PARK, class PK, bool ONEL = false>
+template <bool STATS, bool CULL, bool MANYL, bool SMALL, bool PLANES, bool PARK, class PK, bool ONEL = false,
+          bool TBVH = false>
 __device__ __forceinline__ col trace_from(const DevScene &RFX_SCENE_PARAM, v3 origin, v3 ray, col mulc, col pix, int refl,
                                           int depth, v3 rd, const float *lut, Cnt &cnt, bool valid, const PK &park,
                                           bool &parked, const uint64_t *pm_tile = nullptr, bool pm_shadow = true)
@@ -1627,7 +1776,7 @@ __device__ __forceinline__ col trace_from(const DevScene &RFX_SCENE_PARAM, v3 or
       const uint64_t *pl = RFX_PRIM_LARGE && CULL && seg0 && pm_tile[0] != kPrimLargeNone ? pm_tile : nullptr;
       Bundle B;
       if constexpr (CULL) B = make_bundle(origin, ray, alive);
-      closest_hit<STATS, PLANES>(S, origin, ray, alive, CULL ? &B : nullptr, h, cnt, park.bvh(), pl);
+      closest_hit<STATS, PLANES, TBVH>(S, origin, ray, alive, CULL ? &B : nullptr, h, cnt, park.bvh(), pl);
     }
     const bool hit = alive && h.obj >= 0;
     // re-derive the winner's outputs with the reference's expressions
@@ -1707,7 +1856,7 @@ __device__ __forceinline__ col trace_from(const DevScene &RFX_SCENE_PARAM, v3 or
           {
             Bundle SB;
             if constexpr (CULL) SB = make_bundle(drop, sray, facing);
-            const bool occ = occluded<STATS, PLANES>(S, drop, sray, facing, skip_sph, skip_tri, skip_pln,
+            const bool occ = occluded<STATS, PLANES, TBVH>(S, drop, sray, facing, skip_sph, skip_tri, skip_pln,
                                                      CULL ? &SB : nullptr, cnt, park.bvh(), &occ_hint);
             if (facing && !occ) lit |= 1u << q;
           }
@@ -1858,12 +2007,12 @@ __device__ __forceinline__ col trace_from(const DevScene &RFX_SCENE_PARAM, v3 or
 #endif
 }
 
-template <bool STATS, bool CULL, bool MANYL, bool SMALL, bool PLANES, bool ONEL = false>
+template <bool STATS, bool CULL, bool MANYL, bool SMALL, bool PLANES, bool ONEL = false, bool TBVH = false>
 __device__ __forceinline__ col trace(const DevScene &S, v3 origin, v3 ray, int depth, v3 rd, const float *lut,
                                      Cnt &cnt, bool valid, const uint64_t *pm_tile = nullptr, bool pm_shadow = true)
 {
   bool parked;
-  return trace_from<STATS, CULL, MANYL, SMALL, PLANES, false, Park, ONEL>(S, origin, ray, mkc(1.0f, 1.0f, 1.0f), mkc(0.0f, 0.0f, 0.0f), 0,
+  return trace_from<STATS, CULL, MANYL, SMALL, PLANES, false, Park, ONEL, TBVH>(S, origin, ray, mkc(1.0f, 1.0f, 1.0f), mkc(0.0f, 0.0f, 0.0f), 0,
                                                        depth, rd, lut, cnt, valid, Park{0, nullptr, nullptr, 0, 0},
                                                        parked, pm_tile, pm_shadow);
 }
@@ -2018,6 +2167,9 @@ __host__ __device__ constexpr uint32_t ss_lane_block(int ss)
 // kCfgPlanes -- the scene holds planes (Scene::addPlane extension); kCfgPark -- plain pixels park their traces
 // for the bounce kernel (ray regrouping; rfx_trace_plain_park.hip)
 constexpr int kCfgCull = 1, kCfgManyLights = 2, kCfgSmall = 4, kCfgPlanes = 8, kCfgPark = 16, kCfgOneLight = 32;
+// kCfgTriBvh -- a non-small scene with a triangle BVH (rfx_types.h RFX_TRI_BVH): its culling configurations carry the
+// triangle walkers; every other scene runs kernels without them (with them C5 traced 3.0% slower)
+constexpr int kCfgTriBvh = 64;
 #ifndef RFX_ONE_LIGHT
 #define RFX_ONE_LIGHT 1
 #endif
@@ -2039,6 +2191,7 @@ __global__ __launch_bounds__(kWgThreads) __attribute__((amdgpu_waves_per_eu(
   constexpr bool CULL = (CFG & kCfgCull) != 0, MANYL = (CFG & kCfgManyLights) != 0, SMALL = (CFG & kCfgSmall) != 0;
   constexpr bool PLANES = (CFG & kCfgPlanes) != 0, PARK = MODE == kModePlain && !STATS && (CFG & kCfgPark) != 0;
   constexpr bool ONEL = (CFG & kCfgOneLight) != 0;  // exactly one light: the light loops unrolled
+  constexpr bool TBVH = (CFG & kCfgTriBvh) != 0;    // the scene has a triangle BVH
   RFX_WAVE_T0();
   __shared__ float lut[256];
   for (uint32_t i = threadIdx.x; i < 256; i += kWgThreads) lut[i] = (float)i / 255.0f;  // Color.cpp:11-13
@@ -2119,7 +2272,7 @@ __global__ __launch_bounds__(kWgThreads) __attribute__((amdgpu_waves_per_eu(
       // the tile's per-view masks (prim_cull_kernel<., true>; chunks: the pixel's closest-hit mask, every chunk)
       const uint64_t *pm = RFX_PRIM_LANES && SMALL && CULL && !STATS && P.prim_mask
                                ? P.prim_mask + (size_t)kPrimStride * t8 : nullptr;
-      const col c = trace<STATS, CULL, MANYL, SMALL, PLANES, ONEL>(S, eye, ray, P.depth, rd, lut, cnt, valid, pm,
+      const col c = trace<STATS, CULL, MANYL, SMALL, PLANES, ONEL, TBVH>(S, eye, ray, P.depth, rd, lut, cnt, valid, pm,
                                                                   P.prim_shadow != 0);
       {
 #ifdef RFX_LAUNDER_PARAMS
@@ -2220,7 +2373,7 @@ __global__ __launch_bounds__(kWgThreads) __attribute__((amdgpu_waves_per_eu(
     const v3 ray = mmul(view, mk((float)x - P.wh, (float)y - P.hh, P.rz));
     v3 rd = mk(0.0f, 0.0f, 0.0f);
     if (valid) rd = load_rd(P, (uint64_t)cy * bw + cx - P.trace_base);
-    const col c = trace<STATS, CULL, MANYL, SMALL, PLANES, ONEL>(S, eye, ray, P.depth, rd, lut, cnt, valid);
+    const col c = trace<STATS, CULL, MANYL, SMALL, PLANES, ONEL, TBVH>(S, eye, ray, P.depth, rd, lut, cnt, valid);
     if (valid)
     {
       const uint32_t ex = min(P.W, x + n), ey = min(P.H, y + n);
@@ -2253,7 +2406,7 @@ __global__ __launch_bounds__(kWgThreads) __attribute__((amdgpu_waves_per_eu(
       const ParkTile park{P.park_after, P.queue, P.queue_count, P, wv, w8};
       const uint64_t *pm_tile = (SMALL || RFX_PRIM_LARGE) && CULL && !STATS && P.prim_mask
                                     ? P.prim_mask + (size_t)(SMALL ? kPrimStride : kPrimLargeStride) * t8 : nullptr;
-      const col c = trace_from<STATS, CULL, MANYL, SMALL, PLANES, PARK, ParkTile, ONEL>(S, eye, ray, mkc(1.0f, 1.0f, 1.0f),
+      const col c = trace_from<STATS, CULL, MANYL, SMALL, PLANES, PARK, ParkTile, ONEL, TBVH>(S, eye, ray, mkc(1.0f, 1.0f, 1.0f),
                                                                   mkc(0.0f, 0.0f, 0.0f), 0, P.depth, rd, lut, cnt,
                                                                   valid, park, parked, pm_tile);
       out = cadd(mkc(0.0f, 0.0f, 0.0f), c);                                      // Render.cpp:185 (/ 1.0f exact)
@@ -2307,7 +2460,7 @@ __global__ __launch_bounds__(kWgThreads) __attribute__((amdgpu_waves_per_eu(
           // the tile's per-view masks cover every sample's primary rays (prim_cull_kernel)
           const uint64_t *pm = RFX_PRIM_SSAA && SMALL && CULL && !STATS && P.prim_mask
                                    ? P.prim_mask + (size_t)kPrimStride * t8s : nullptr;
-          const col c = trace<STATS, CULL, MANYL, SMALL, PLANES>(S, eye, ray, P.depth, rd, lut, cnt, svalid, pm,
+          const col c = trace<STATS, CULL, MANYL, SMALL, PLANES, false, TBVH>(S, eye, ray, P.depth, rd, lut, cnt, svalid, pm,
                                                                  P.prim_shadow != 0);
           float *f = reinterpret_cast<float *>(slot) + 3 * ls;
           f[0] = f[0] + c.r;
@@ -2344,7 +2497,7 @@ __global__ __launch_bounds__(kWgThreads) __attribute__((amdgpu_waves_per_eu(
           if (valid) rd = load_rd(P, pr * (uint64_t)(ss * ss) + (uint64_t)(sx * ss + sy));
           const uint64_t *pm = RFX_PRIM_SSAA && SMALL && CULL && !STATS && P.prim_mask
                                    ? P.prim_mask + (size_t)kPrimStride * t8 : nullptr;
-          fin = cadd(fin, trace<STATS, CULL, MANYL, SMALL, PLANES>(S, eye, ray, P.depth, rd, lut, cnt, valid, pm,
+          fin = cadd(fin, trace<STATS, CULL, MANYL, SMALL, PLANES, false, TBVH>(S, eye, ray, P.depth, rd, lut, cnt, valid, pm,
                                                                    P.prim_shadow != 0));
         }
       if (ss != 1)                                                                 // Render.cpp:189 (x / 1.0f == x)
@@ -2664,7 +2817,7 @@ __global__ RFX_TRACE_BOUNDS void bounce_kernel(DevScene S, FrameParams P)
   rf.refill(alive, origin, ray, mulc, pix, refl, rd);  // the wave's first 64 traces
   RFX_WAVE_T0();
   bool parked;
-  (void)trace_from<false, CULL, MANYL, SMALL, PLANES, false, decltype(rf), (CFG & kCfgOneLight) != 0>(
+  (void)trace_from<false, CULL, MANYL, SMALL, PLANES, false, decltype(rf), (CFG & kCfgOneLight) != 0, (CFG & kCfgTriBvh) != 0>(
       S, origin, ray, mulc, pix, refl, P.depth, rd, lut, cnt, alive, rf, parked);
   RFX_WAVE_T1(kBounceTimeBase + kWgWaves * blockIdx.x + wv);
 }
@@ -2710,7 +2863,7 @@ void bounce_kernel_lds(DevScene S, FrameParams P)
   int refl = 0;
   rf.refill(alive, origin, ray, mulc, pix, refl, rd);
   bool parked;
-  (void)trace_from<false, CULL, MANYL, SMALL, PLANES, false, decltype(rf), (CFG & kCfgOneLight) != 0>(
+  (void)trace_from<false, CULL, MANYL, SMALL, PLANES, false, decltype(rf), (CFG & kCfgOneLight) != 0, (CFG & kCfgTriBvh) != 0>(
       S, origin, ray, mulc, pix, refl, P.depth, rd, lut, cnt, alive, rf, parked);
 }
 
@@ -2725,6 +2878,22 @@ inline void launch_one(dim3 grid, const DevScene &S, const FrameParams &P, hipSt
 template <bool STATS, int MODE>
 inline void launch_cfg(int cfg, dim3 grid, const DevScene &S, const FrameParams &P, hipStream_t st)
 {
+#if RFX_TRI_BVH
+  if (cfg & kCfgTriBvh)  // the non-small culling configurations (rfx_kernels.hip launch_trace sets the bit for no other)
+  {
+    if constexpr (!STATS)
+      switch (cfg & ~kCfgTriBvh)
+      {
+        case 1: launch_one<STATS, MODE, 1 | kCfgTriBvh>(grid, S, P, st); return;
+        case 3: launch_one<STATS, MODE, 3 | kCfgTriBvh>(grid, S, P, st); return;
+        case 9: launch_one<STATS, MODE, 9 | kCfgTriBvh>(grid, S, P, st); return;
+        case 11: launch_one<STATS, MODE, 11 | kCfgTriBvh>(grid, S, P, st); return;
+        case 1 | kCfgOneLight: launch_one<STATS, MODE, 1 | kCfgOneLight | kCfgTriBvh>(grid, S, P, st); return;
+        case 9 | kCfgOneLight: launch_one<STATS, MODE, 9 | kCfgOneLight | kCfgTriBvh>(grid, S, P, st); return;
+      }
+    cfg &= ~kCfgTriBvh;
+  }
+#endif
   if (cfg & kCfgOneLight)  // scenes with exactly one light: the culling configurations have unrolled light loops
   {
     switch (cfg & ~kCfgOneLight)

@@ -19,6 +19,14 @@ void launch_trace_plain_park(int cfg, dim3 grid, const DevScene &S, const FrameP
 {
   switch (cfg & ~kCfgPark)
   {
+#if RFX_TRI_BVH
+    case 1 | kCfgTriBvh: launch_park_one<1 | kCfgTriBvh>(grid, S, P, st); break;
+    case 3 | kCfgTriBvh: launch_park_one<3 | kCfgTriBvh>(grid, S, P, st); break;
+    case 9 | kCfgTriBvh: launch_park_one<9 | kCfgTriBvh>(grid, S, P, st); break;
+    case 11 | kCfgTriBvh: launch_park_one<11 | kCfgTriBvh>(grid, S, P, st); break;
+    case 1 | kCfgOneLight | kCfgTriBvh: launch_park_one<1 | kCfgOneLight | kCfgTriBvh>(grid, S, P, st); break;
+    case 9 | kCfgOneLight | kCfgTriBvh: launch_park_one<9 | kCfgOneLight | kCfgTriBvh>(grid, S, P, st); break;
+#endif
     case 1 | kCfgOneLight: launch_park_one<1 | kCfgOneLight>(grid, S, P, st); break;
     case 5 | kCfgOneLight: launch_park_one<5 | kCfgOneLight>(grid, S, P, st); break;
     case 1: launch_park_one<1>(grid, S, P, st); break;
@@ -67,6 +75,14 @@ hipError_t launch_bounce_lds(int cfg, uint32_t groups, const DevScene &S, const 
 {
   switch (cfg)
   {
+#if RFX_TRI_BVH
+    case 1 | kCfgTriBvh: return launch_bounce_lds_one<1 | kCfgTriBvh>(groups, S, P, st);
+    case 3 | kCfgTriBvh: return launch_bounce_lds_one<3 | kCfgTriBvh>(groups, S, P, st);
+    case 9 | kCfgTriBvh: return launch_bounce_lds_one<9 | kCfgTriBvh>(groups, S, P, st);
+    case 11 | kCfgTriBvh: return launch_bounce_lds_one<11 | kCfgTriBvh>(groups, S, P, st);
+    case 1 | kCfgOneLight | kCfgTriBvh: return launch_bounce_lds_one<1 | kCfgOneLight | kCfgTriBvh>(groups, S, P, st);
+    case 9 | kCfgOneLight | kCfgTriBvh: return launch_bounce_lds_one<9 | kCfgOneLight | kCfgTriBvh>(groups, S, P, st);
+#endif
     case 1 | kCfgOneLight: return launch_bounce_lds_one<1 | kCfgOneLight>(groups, S, P, st);
     case 9 | kCfgOneLight: return launch_bounce_lds_one<9 | kCfgOneLight>(groups, S, P, st);
     case 1: return launch_bounce_lds_one<1>(groups, S, P, st);
@@ -82,6 +98,14 @@ void launch_bounce(int cfg, dim3 grid, const DevScene &S, const FrameParams &P, 
 {
   switch (cfg)
   {
+#if RFX_TRI_BVH
+    case 1 | kCfgTriBvh: launch_bounce_one<1 | kCfgTriBvh>(grid, S, P, st); break;
+    case 3 | kCfgTriBvh: launch_bounce_one<3 | kCfgTriBvh>(grid, S, P, st); break;
+    case 9 | kCfgTriBvh: launch_bounce_one<9 | kCfgTriBvh>(grid, S, P, st); break;
+    case 11 | kCfgTriBvh: launch_bounce_one<11 | kCfgTriBvh>(grid, S, P, st); break;
+    case 1 | kCfgOneLight | kCfgTriBvh: launch_bounce_one<1 | kCfgOneLight | kCfgTriBvh>(grid, S, P, st); break;
+    case 9 | kCfgOneLight | kCfgTriBvh: launch_bounce_one<9 | kCfgOneLight | kCfgTriBvh>(grid, S, P, st); break;
+#endif
     case 1 | kCfgOneLight: launch_bounce_one<1 | kCfgOneLight>(grid, S, P, st); break;
     case 5 | kCfgOneLight: launch_bounce_one<5 | kCfgOneLight>(grid, S, P, st); break;
     case 1: launch_bounce_one<1>(grid, S, P, st); break;

@@ -68,6 +68,19 @@ struct alignas(16) BvhNode { float lx[2], ly[2], lz[2], hx[2], hy[2], hz[2]; int
 #ifndef RFX_BVH_LEAF_PAIRS
 #define RFX_BVH_LEAF_PAIRS 4
 #endif
+// Triangle BVH of a non-small scene (rfx_host.cpp build_tri_tree, rfx_trace.h closest_tris_bvh / occluded_tris_bvh):
+// BvhNode nodes with the sphere tree's conventions (child >= 0 internal, ~g a leaf, boxes pre-widened, the same
+// margin reference point DevScene::bvh_ref), so ray_inv and bvh_box serve both trees.  Leaf ~g holds the records
+// [RFX_TRI_BVH_LEAF g, RFX_TRI_BVH_LEAF (g + 1)) of DevScene::tri_leaf: a spatially ordered copy of the triangles'
+// TriGeo whose padding carries the insertion index (pad[0]) and the object index (pad[1]) as int bits; a padding
+// record is all zero (a31 = a32 = a33 = 0: never hit).  tri_geo / tri_shade stay in insertion order.  RFX_TRI_BVH 0
+// removes the walkers from the kernels.
+#ifndef RFX_TRI_BVH
+#define RFX_TRI_BVH 1
+#endif
+#ifndef RFX_TRI_BVH_LEAF
+#define RFX_TRI_BVH_LEAF 4
+#endif
 // Plane(pos, norm, material) (Plane.h:6-14): the normal as given (the reference never normalises it)
 struct alignas(16) PlaneGeo { float px, py, pz, nx, ny, nz; int32_t obj, dielectric; };
 struct alignas(16) LightRec { float ox, oy, oz, radius, r, g, b, power; }; // OmniLight.h
@@ -106,6 +119,13 @@ struct DevScene {
   float amb_r, amb_g, amb_b;  // diffLightColor * diffLightPower (Scene.cpp:186, host-folded)
   float env_r, env_g, env_b;  // envColor (Scene.cpp:12,55)
   float half_tile_w, half_tile_h;  // Skybox.cpp:21-37
+  const BvhNode *tri_bvh;     // triangle BVH, root 0 (null: the 64-triangle chunk loops)
+  const TriGeo *tri_leaf;     // RFX_TRI_BVH_LEAF records per leaf (spatial order; pad[0] insertion index, pad[1] object)
+  const int32_t *tri_resid;   // n_tri_resid triangles outside the tree (cond >= 300 or singular), insertion indices:
+  int32_t n_tri_resid;        //   every ray tests them after the walk
+  int32_t n_tri_bvh;          // nodes of the triangle BVH
+  int32_t tri_bvh_depth;      // its internal levels (<= kBvhStack)
+  int32_t tri_bvh_narrow;     // narrow bundles (a tile's primary rays) walk the tree too (else: the bundle-culled chunks)
 };
 
 // The bounce kernel with the BVH staged in LDS (rfx_trace.h bounce_kernel_lds): one workgroup of kLdsBvhWaves waves

@@ -23,7 +23,7 @@ from __future__ import annotations
 
 import ctypes as C
 import os
-from typing import Optional, Sequence
+from typing import List, Optional, Sequence
 
 import numpy as np
 
@@ -158,6 +158,36 @@ class Scene:
                                                        material.transparency), "Scene.addTriangle")
         self._version += 1
         return Triangle(self, obj)
+
+    def addMesh(self, vertices, indices, material: Material) -> List[Triangle]:
+        """A triangle mesh in one call (rfx.h rfx_scene_add_mesh): vertices (n, 3) floats, indices (m, 3) vertex
+        numbers; the same as m addTriangle calls in index order.  Returns the m Triangle handles."""
+        v = np.ascontiguousarray(vertices, dtype=np.float32).reshape(-1, 3)
+        i = np.ascontiguousarray(indices, dtype=np.uint32).reshape(-1, 3)
+        first = check(_lib.load().rfx_scene_add_mesh(self._h, _lib.fptr(v), v.shape[0], _lib.u32ptr(i), i.shape[0],
+                                                     material.type, farr(material.color), material.reflectivity,
+                                                     material.transparency), "Scene.addMesh")
+        self._version += 1
+        return [Triangle(self, first + k) for k in range(i.shape[0])]
+
+    def tri_bvh_dump(self):
+        """The triangle BVH a renderer would build for this scene (rfx.h rfx_scene_tri_bvh_dump; host only), or None
+        without one: dict of nodes, leaves, leaf_size, depth, boxes (nodes, 2, 6), children (nodes, 2), leaf_ids
+        (leaves, leaf_size), residual."""
+        L = _lib.load()
+        cnt = (C.c_int32 * 5)()
+        if check(L.rfx_scene_tri_bvh_dump(self._h, cnt, None, None, None, None), "Scene.tri_bvh_dump") == 0:
+            return None
+        nodes, leaves, nres, leaf, depth = (int(x) for x in cnt)
+        boxes = np.zeros((nodes, 2, 6), np.float32)
+        children = np.zeros((nodes, 2), np.int32)
+        ids = np.zeros((leaves, leaf), np.int32)
+        res = np.zeros(nres, np.int32)
+        i32 = lambda a: a.ctypes.data_as(_lib._i32p)
+        check(L.rfx_scene_tri_bvh_dump(self._h, cnt, _lib.fptr(boxes), i32(children), i32(ids), i32(res)),
+              "Scene.tri_bvh_dump")
+        return {"nodes": nodes, "leaves": leaves, "leaf_size": leaf, "depth": depth, "boxes": boxes,
+                "children": children, "leaf_ids": ids, "residual": res}
 
     def addPlane(self, pos: Vector3, norm: Vector3, material: Material) -> Plane:
         """Plane(pos, norm, material) (Plane.cpp:9-14) as a scene object, traced by Plane::trace (Plane.cpp:36-73)."""
@@ -331,6 +361,18 @@ class Renderer:
         """The last trace launch's bounce kernel (rfx.h rfx_renderer_bounce_form): 0 none, 1 global-memory BVH, 2 the
         LDS-staged BVH."""
         return _lib.load().rfx_renderer_bounce_form(self._h)
+
+    def set_tri_accel(self, mode: int):
+        """Triangle BVH of non-small scenes (rfx.h rfx_renderer_set_tri_accel): -1 automatic (default), 0 off, 1 on,
+        2 on with narrow bundles walking the tree too (A/B).  Takes effect at the next set_scene (which then uploads again).  No pixel changes."""
+        check(_lib.load().rfx_renderer_set_tri_accel(self._h, int(mode)), "set_tri_accel")
+        self._scene_key = None
+
+    def accel_info(self) -> "_lib.AccelInfo":
+        """The uploaded scene's hierarchies (rfx.h rfx_renderer_accel_info)."""
+        a = _lib.AccelInfo()
+        check(_lib.load().rfx_renderer_accel_info(self._h, C.byref(a)), "accel_info")
+        return a
 
     def set_timing(self, enable):
         """HIP-event timing of the frames (rfx.h rfx_renderer_set_timing): True / 1 every frame, n > 1 every n-th

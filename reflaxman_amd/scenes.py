@@ -81,6 +81,14 @@ class SceneDesc:
                              (int(mat_type), tuple(map(f32, rgb)), f32(refl), f32(transp))))
         return len(self.objects) - 1
 
+    def add_mesh(self, vertices, indices, mat_type, rgb, refl, transp=0.0):
+        """An indexed mesh (rfx.h rfx_scene_add_mesh) as its add_triangle calls in index order -- the scene file
+        format knows triangles only.  Returns the first triangle's object index."""
+        first = len(self.objects)
+        for (a, b, c) in indices:
+            self.add_triangle(vertices[a], vertices[b], vertices[c], mat_type, rgb, refl, transp)
+        return first
+
     def add_plane(self, pos, norm, mat_type, rgb, refl, transp=0.0):
         self.objects.append(("plane", tuple(map(f32, pos)), tuple(map(f32, norm)),
                              (int(mat_type), tuple(map(f32, rgb)), f32(refl), f32(transp))))
@@ -364,6 +372,61 @@ def mesh_scene(nx: int = 10, nz: int = 5) -> SceneDesc:
     return s
 
 
+def soup_scene(n: int, seed: int = 4242, n_spheres: int = 0) -> SceneDesc:
+    """A triangle soup for the triangle BVH: n LCG triangles spread through the box [-12, 12] x [0.1, 6] x [-9, 9]
+    above the ground quad, edge lengths log-uniform from 1% to 50% of the box (8 units), so median splits are uneven
+    and the large triangles overlap many leaves; materials mixed, every 7th triangle textured (a seeded texture or
+    the checker); optionally n_spheres LCG spheres, added first."""
+    s = _base(f"soup{n}" + (f"_s{n_spheres}" if n_spheres else "") + (f"_{seed}" if seed != 4242 else ""))
+    _add_sun(s)
+    if n_spheres:
+        _lcg_spheres(s, n_spheres)
+    t0 = s.add_texture(synth_texture("soup", 64, 64, 3003))
+    t1 = s.add_texture(Texture("himiya", None))
+    _add_ground(s, t1)
+    g = Lcg(seed)
+    ext = 8.0
+    for i in range(n):
+        c = (g.uniform(-12.0, 12.0), g.uniform(0.1, 6.0), g.uniform(-9.0, 9.0))
+        size = ext * 0.01 * 50.0 ** g.uniform(0.0, 1.0)
+        e = [[g.uniform(-1.0, 1.0) * size for _ in range(3)] for _ in range(2)]
+        v0 = (c[0] - (e[0][0] + e[1][0]) / 3, c[1] - (e[0][1] + e[1][1]) / 3, c[2] - (e[0][2] + e[1][2]) / 3)
+        v1 = (v0[0] + e[0][0], v0[1] + e[0][1], v0[2] + e[0][2])
+        v2 = (v0[0] + e[1][0], v0[1] + e[1][1], v0[2] + e[1][2])
+        v0, v1, v2 = (tuple((p[0], max(p[1], 0.05), p[2])) for p in (v0, v1, v2))
+        mt = DIELECTRIC if (g.next_u32() >> 31) else METAL
+        rgb = (g.uniform(0.2, 1), g.uniform(0.2, 1), g.uniform(0.2, 1))
+        t = s.add_triangle(v0, v1, v2, mt, rgb, g.uniform(0, 1))
+        if i % 7 == 3:
+            s.set_texture(t, t0 if i % 2 else t1, (0.0, 0.0, 0.0, 1.0, 1.0, 0.0))
+    return s
+
+
+def degenerate_soup_scene() -> SceneDesc:
+    """soup_scene(300) plus the triangles a hierarchy can get wrong: 12 slivers of edge ratio 10^4 (an
+    ill-conditioned basis), 2 zero-area triangles (a singular basis: the reference falls back to the identity) and 4
+    exactly coincident pairs of different colours (the closest-hit tie goes to the first inserted)."""
+    s = soup_scene(300)
+    s.name = "soup300_degenerate"
+    g = Lcg(991)
+    for k in range(12):
+        c = (g.uniform(-8.0, 8.0), g.uniform(0.5, 4.0), g.uniform(-6.0, 6.0))
+        d = (g.uniform(-1, 1), g.uniform(-1, 1), g.uniform(-1, 1))
+        L = 4.0
+        a = (c[0] + L * d[0], c[1] + abs(L * d[1]), c[2] + L * d[2])
+        w = (d[1] * 4e-4, -d[0] * 4e-4, 0.0)  # L |d| / |w| >= 10^4
+        b = (c[0] + w[0], c[1] + w[1], c[2] + w[2])
+        s.add_triangle(c, a, b, METAL if k % 2 else DIELECTRIC, (g.uniform(0.3, 1), 0.4, 0.9), 0.5)
+    s.add_triangle((1.0, 1.0, 1.0), (1.0, 1.0, 1.0), (2.0, 2.0, 1.0), METAL, (1, 0, 0), 0.3)
+    s.add_triangle((0.0, 2.0, 0.0), (1.0, 3.0, 1.0), (2.0, 4.0, 2.0), METAL, (0, 1, 0), 0.3)
+    for k in range(4):
+        c = (g.uniform(0.0, 6.0), g.uniform(0.5, 3.0), g.uniform(-4.0, 2.0))
+        v = [(c[0], c[1], c[2]), (c[0] + 0.3, c[1] + 1.6, c[2] - 1.1), (c[0] - 1.2, c[1] + 0.4, c[2] - 1.7)]
+        s.add_triangle(*v, METAL, (1.0, 0.1, 0.1), 0.2)
+        s.add_triangle(*v, DIELECTRIC, (0.1, 0.2, 1.0), 0.7)
+    return s
+
+
 def planes_scene(n_spheres: int = 0) -> SceneDesc:
     """Planes in a scene (the addPlane extension of Plane.cpp:36-73): the 8 default spheres (or n LCG spheres,
     the general object loops), a textured ground triangle pair, then a dielectric floor plane just below the
@@ -399,6 +462,14 @@ SCENES = {
 def get_scene(name: str) -> SceneDesc:
     if name.startswith("stress") and name[6:].isdigit():
         return stress_scene(int(name[6:]))
+    if name.startswith("soup"):  # soup<n> or soup<n>_s<spheres>
+        n, _, sph = name[4:].partition("_s")
+        if n.isdigit() and (sph.isdigit() or not sph):
+            return soup_scene(int(n), n_spheres=int(sph or 0))
+    if name.startswith("mesh") and "x" in name:  # mesh<nx>x<nz>
+        nx, _, nz = name[4:].partition("x")
+        if nx.isdigit() and nz.isdigit():
+            return mesh_scene(int(nx), int(nz))
     return SCENES[name]()
 
 

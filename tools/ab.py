@@ -107,6 +107,12 @@ VARIANTS = {
     "sort32": ["RFX_TILE_SORT_EVERY=32"],
     "fmax1024": ["RFX_RNG_FUSED_MAX_BLOCKS=1024"],
     "fmax4096": ["RFX_RNG_FUSED_MAX_BLOCKS=4096"],
+    "base2": [],  # a second copy of base: the A/A spread of a session
+    "notribvh": ["RFX_TRI_BVH=0"],  # the kernels without the triangle walkers
+    "trileaf2": ["RFX_TRI_BVH_LEAF=2"],
+    "trileaf8": ["RFX_TRI_BVH_LEAF=8"],
+    "trinarrow": ["RFX_TRI_BVH_NARROW_MIN=0"],  # narrow bundles walk the triangle tree at any count
+    "trinonarrow": ["RFX_TRI_BVH_NARROW_MIN=(1<<30)"],  # narrow bundles always keep the bundle-culled chunk loop (base)
 }
 
 
@@ -145,13 +151,16 @@ def build_scene_with(L, desc):
 
 
 class Runner:
-    def __init__(self, name, path, desc, W, H, depth, seed, tile_order=None, regroup=None, prim=None, ss=1, additive=0):
+    def __init__(self, name, path, desc, W, H, depth, seed, tile_order=None, regroup=None, prim=None, ss=1, additive=0,
+                 tri_accel=None):
         self.name = name
         L = self.L = _lib.bind(path, partial=True)
         self.scene, eye, view, fov = build_scene_with(L, desc)
         self.r = C.c_void_p()
         rc = L.rfx_renderer_create(C.byref(self.r), 0)
         assert rc == 0, L.rfx_last_error()
+        if tri_accel is not None:  # before the upload: the tree is built by set_scene
+            assert L.rfx_renderer_set_tri_accel(self.r, tri_accel) == 0
         assert L.rfx_renderer_set_scene(self.r, self.scene) == 0, L.rfx_last_error()
         assert L.rfx_renderer_set_rng(self.r, seed, 0) == 0
         if tile_order is not None:
@@ -225,9 +234,12 @@ def cmd_run(args):
     # runtime variants: every build once per --regroup setting (rfx_renderer_set_regroup), named build@parkN
     regroups = [None] if not args.regroup else [int(v) for v in args.regroup.split(",")]
     prims = [None] if not args.prim else [int(v) for v in args.prim.split(",")]
-    runners = [Runner(n + ("" if g is None else f"@park{g}") + ("" if q is None else f"@prim{q}"), p, desc, args.width,
-                      args.height, args.depth, 1350490027, regroup=g, prim=q, ss=args.ss, additive=args.additive)
-               for n, p in zip(names, paths) for g in regroups for q in prims]
+    tris = [None] if not args.tri_accel else [int(v) for v in args.tri_accel.split(",")]
+    runners = [Runner(n + ("" if g is None else f"@park{g}") + ("" if q is None else f"@prim{q}") +
+                      ("" if t is None else f"@tri{t}"), p, desc, args.width,
+                      args.height, args.depth, 1350490027, regroup=g, prim=q, ss=args.ss, additive=args.additive,
+                      tri_accel=t)
+               for n, p in zip(names, paths) for g in regroups for q in prims for t in tris]
     # parity of every variant: frame 1 against the reference's full-frame hash (when the manifest has one), and
     # frame 1 + LATER frames (rendered in the learned longest-tile-first order, after the tile sorts) against
     # the product build rendering the same frames in raster order
@@ -287,6 +299,7 @@ def main():
     ap.add_argument("--later-frame", type=int, default=7, help="frame (1-based) also checked against raster order")
     ap.add_argument("--regroup", default="", help="comma list of park_after settings to run each build with (0 = off)")
     ap.add_argument("--prim", default="", help="comma list of rfx_renderer_set_prim_masks modes to run each build with")
+    ap.add_argument("--tri-accel", default="", help="comma list of rfx_renderer_set_tri_accel modes to run each build with")
     args = ap.parse_args()
     if args.cmd == "build":
         cmd_build(args.variants.split(","))
