@@ -226,6 +226,20 @@ int rfx_render_frame(rfx_renderer *r, const rfx_frame *frame, float *d_rgb, uint
 /* The most traces one rfx_render_frame launch takes (default 2^30: 4 GB of randDir state per buffer, two buffers);
  * 0 = the default.  Splitting changes no pixel (tests/test_gpu_parity.py forces small limits). */
 int rfx_renderer_set_launch_traces(rfx_renderer *r, uint64_t max_traces);
+/* The RNG pre-pass of one-device unsplit rfx_render_frame launches (no pixel changes): 1 (default) = the cycle table.
+ * Whether a triple of draws is accepted depends on the LCG state alone and a triple is an affine map of full period
+ * 2^32, so every frame's stream is a run of one cyclic sequence of 2^32 triples; the renderer counts the whole cycle's
+ * accepted triples once (on its first such frame: a few ms of GPU time, 8 MB), keeps the stream state's place in the
+ * cycle on the device, and every later pre-pass is one launch that looks its offsets up.  0 = the count and emit kernels
+ * of every frame, as the multi-GPU, band, strip and split-span paths always take. */
+int rfx_renderer_set_rng_prepass(rfx_renderer *r, int mode);
+/* Which pre-pass the last launch ran: 0 = the count / emit kernels, 1 = the cycle table, 2 = the one-pass kernel of
+ * small launches (taken only where the table is off). */
+int rfx_renderer_prepass_form(const rfx_renderer *r);
+/* The place of an LCG state in that cycle: the k with (three draws)^k applied to state 0 giving `state` (host only). */
+uint32_t rfx_rng_triple_index(uint32_t state);
+/* blocks of the cycle table (4096 triples each) */
+uint32_t rfx_rng_seq_blocks(void);
 
 /*
  * Multi-GPU form of the RNG pre-pass, around ONE exchange step.  The trace-ordered
@@ -358,6 +372,12 @@ int rfx_kat_div(rfx_renderer *r, uint64_t first, uint64_t n, uint64_t counts[3])
  * frame parameters (0 expected), out[2] = 1 if the build reads the scene record that way.  swapped = 1 runs the same
  * check in a kernel declared (FrameParams, DevScene): the check must report differences there. */
 int rfx_kat_kernarg(rfx_renderer *r, int swapped, uint32_t out[3]);
+/* The cycle table (rfx_renderer_set_rng_prepass), built if it is not yet: prefix[B] = accepted triples of the cycle's
+ * blocks [0, B), B <= rfx_rng_seq_blocks() (the last word: the cycle's total). */
+int rfx_kat_rng_seq_prefix(rfx_renderer *r, uint32_t *prefix);
+/* The same blocks' accept counts from the per-frame count kernel run on the cycle's origin state:
+ * counts[B], B < rfx_rng_seq_blocks(). */
+int rfx_kat_rng_seq_legacy(rfx_renderer *r, uint32_t *counts);
 
 #ifdef __cplusplus
 }

@@ -110,6 +110,10 @@ SIGNATURES = [
     ("rfx_renderer_set_regroup_sort", C.c_int, [C.c_void_p, C.c_int]),
     ("rfx_renderer_set_launch_traces", C.c_int, [C.c_void_p, C.c_uint64]),
     ("rfx_renderer_bounce_form", C.c_int, [C.c_void_p]),
+    ("rfx_renderer_set_rng_prepass", C.c_int, [C.c_void_p, C.c_int]),
+    ("rfx_renderer_prepass_form", C.c_int, [C.c_void_p]),
+    ("rfx_rng_triple_index", C.c_uint32, [C.c_uint32]),
+    ("rfx_rng_seq_blocks", C.c_uint32, []),
     ("rfx_renderer_set_tri_accel", C.c_int, [C.c_void_p, C.c_int]),
     ("rfx_renderer_accel_info", C.c_int, [C.c_void_p, C.POINTER(AccelInfo)]),
     ("rfx_renderer_get_timing", C.c_int, [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_double), _u64p]),
@@ -127,6 +131,8 @@ SIGNATURES = [
     ("rfx_kat_powf_cube", C.c_int, [C.c_void_p, C.POINTER(C.c_uint64)]),
     ("rfx_kat_div", C.c_int, [C.c_void_p, C.c_uint64, C.c_uint64, C.POINTER(C.c_uint64)]),
     ("rfx_kat_kernarg", C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_uint32)]),
+    ("rfx_kat_rng_seq_prefix", C.c_int, [C.c_void_p, _u32p]),
+    ("rfx_kat_rng_seq_legacy", C.c_int, [C.c_void_p, _u32p]),
 ]
 
 _lib = None

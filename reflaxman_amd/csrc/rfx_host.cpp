@@ -40,6 +40,17 @@ hipError_t launch_rng_finish_band(const uint32_t *d_seed, const uint32_t *d_jump
 hipError_t launch_rng_fused(const uint32_t *d_seed, const uint32_t *d_jump, uint32_t *d_next_seed, uint64_t nblk,
                             uint64_t traces, uint32_t *d_rd_state, int *d_err, unsigned long long *d_status,
                             unsigned long long *d_ticket, unsigned long long base, uint32_t epoch, hipStream_t st);
+uint32_t rng_seq_blocks();
+uint32_t rng_seq_header_words();
+void rng_seq_tables(uint32_t *hdr, uint32_t *state);
+uint32_t rng_seq_index_of(uint32_t s);
+hipError_t launch_rng_seq_build(const uint32_t *d_hdr, const uint32_t *d_state, uint32_t *d_p, uint32_t *d_tiles,
+                                hipStream_t st);
+hipError_t launch_rng_locate(const uint32_t *d_seed, const uint32_t *d_hdr, const uint32_t *d_state, const uint32_t *d_p,
+                             uint32_t *d_pos, hipStream_t st);
+hipError_t launch_rng_emit_seq(const uint32_t *d_pos, const uint32_t *d_hdr, const uint32_t *d_state, const uint32_t *d_p,
+                               uint64_t nblk, uint64_t traces, uint32_t *d_rd_state, uint32_t *d_next_seed,
+                               uint32_t *d_next_pos, int *d_err, hipStream_t st);
 hipError_t launch_trace(const DevScene &S, const FrameParams &P, bool stats, hipStream_t st);
 hipError_t launch_prim_cull(const DevScene &S, const FrameParams &P, uint64_t *masks, hipStream_t st);
 hipError_t launch_queue_sort(const uint32_t *count, const uint32_t *key, uint32_t *hist, uint32_t *order, hipStream_t st);
@@ -529,6 +540,15 @@ constexpr size_t kPrimLargeWords = 12;  // per wave tile, large scenes (rfx_trac
 #ifndef RFX_SPLIT_STREAMS
 #define RFX_SPLIT_STREAMS 2  // split frames: spans alternate between two streams (1: one stream, no overlap)
 #endif
+#ifndef RFX_RNG_SEQ
+#define RFX_RNG_SEQ 1  // one-device unsplit frames take their randDirs from the cycle table (0: the count / emit kernels)
+#endif
+#ifndef RFX_RNG_SEQ_SPLIT
+#define RFX_RNG_SEQ_SPLIT 1  // the spans of split frames take the table too (0: the count / scan / emit kernels)
+#endif
+#ifndef RFX_RNG_SEQ_MIN_BLOCKS
+#define RFX_RNG_SEQ_MIN_BLOCKS 0  // launches of fewer pre-pass blocks keep rng_fused
+#endif
 constexpr uint64_t kMaxLaunchTraces = 1ull << 31;  // the band scan's 32-bit offsets (rfx_kernels.hip rng_band_range)
 #ifndef RFX_SCAN_EMIT_BLOCKS
 // one-device emits of more RNG blocks than this scan the counts first (rng_band_range) instead of summing them per
@@ -584,6 +604,15 @@ struct rfx_renderer {
   uint32_t rng_epoch = 0;
   uint16_t *d_rng_masks = nullptr;  // one device's accept flags per pre-pass thread (rng_count -> rng_emit)
   uint32_t *d_jump = nullptr;  // LCG jump table for blk_cap blocks (rng_jump_table)
+  // the cycle table (rfx_kernels.hip "the cycle table"), built on the first frame that takes it: the jump header, each
+  // block's start state, the prefix of the accept counts (4 MB each) and build scratch.  d_seq_pos: the stream state's
+  // place in the cycle, (k, A) beside each of the two seed words; seq_valid: the pair beside the current word matches
+  // that word (a table emit wrote both) -- anything else that sets or moves the stream clears it, and the next table
+  // emit runs rng_locate first.
+  uint32_t *d_seq_hdr = nullptr, *d_seq_state = nullptr, *d_seq_p = nullptr, *d_seq_tiles = nullptr, *d_seq_pos = nullptr;
+  bool seq_valid = false;
+  int rng_prepass = RFX_RNG_SEQ;  // rfx_renderer_set_rng_prepass
+  int prepass_form = 0;           // rfx_renderer_prepass_form: the last pre-pass
   // host staging for rfx_render_frame_host
   float *d_img = nullptr; uint32_t *d_argb = nullptr; uint64_t *d_cnt = nullptr; size_t img_cap = 0;
   // tile schedule (rfx_renderer_set_tile_order): a recording trace launch writes per-tile clock costs; a counting
@@ -740,6 +769,8 @@ extern "C" void rfx_renderer_destroy(rfx_renderer *r)
   (void)hipFree(r->d_tile_sum);
   (void)hipFree(r->d_rng_range);
   (void)hipFree(r->d_rng_status); (void)hipFree(r->d_rng_ticket);
+  (void)hipFree(r->d_seq_hdr); (void)hipFree(r->d_seq_state); (void)hipFree(r->d_seq_p); (void)hipFree(r->d_seq_tiles);
+  (void)hipFree(r->d_seq_pos);
   (void)hipFree(r->d_img); (void)hipFree(r->d_argb); (void)hipFree(r->d_cnt);
   (void)hipFree(r->d_queue); (void)hipFree(r->d_qctr); (void)hipFree(r->d_prim_mask);
   (void)hipFree(r->d_split_mask[0]); (void)hipFree(r->d_split_mask[1]);
@@ -792,6 +823,21 @@ extern "C" int rfx_renderer_set_prim_masks(rfx_renderer *r, int mode)
   r->prim_seen.clear();
   return RFX_OK;
 }
+
+extern "C" int rfx_renderer_set_rng_prepass(rfx_renderer *r, int mode)
+{
+  if (!r || mode < 0 || mode > 1) return fail(RFX_ERR_ARG, "renderer_set_rng_prepass: mode 0 or 1");
+  r->rng_prepass = mode;
+  return RFX_OK;
+}
+
+extern "C" int rfx_renderer_prepass_form(const rfx_renderer *r)
+{
+  if (!r) return fail(RFX_ERR_ARG, "renderer_prepass_form: null renderer");
+  return r->prepass_form;
+}
+
+extern "C" uint32_t rfx_rng_triple_index(uint32_t state) { return rng_seq_index_of(state); }
 
 extern "C" int rfx_renderer_bounce_form(const rfx_renderer *r)
 {
@@ -1460,6 +1506,7 @@ extern "C" int rfx_renderer_set_rng(rfx_renderer *r, uint32_t sphere_seed, uint3
   HIP_CHECK(hipStreamSynchronize(r->stream));
   r->jitter_seed = jitter_seed;
   r->rewind_ok = false;
+  r->seq_valid = false;
   ++r->state_seq;
   return RFX_OK;
 }
@@ -1554,6 +1601,8 @@ static int enqueue_rng(rfx_renderer *r, uint64_t traces, hipStream_t st)
   HIP_CHECK(launch_rng_finish(seed_cur(r), r->d_jump, seed_next(r), r->d_blk_cnt, r->d_rng_masks, nblk, traces,
                               r->d_rd, r->d_err, 1, 1, 1, 0, 1, st));
   r->seed_idx ^= 1u;
+  r->seq_valid = false;
+  r->prepass_form = 0;
   ++r->state_seq;
   r->rewind_ok = false;
   return RFX_OK;
@@ -1664,6 +1713,8 @@ static int emit_frame(rfx_renderer *r, FramePlan &pl, const uint32_t *d_counts, 
     HIP_CHECK(launch_rng_finish(seed_cur(r), r->d_jump, seed_next(r), d_counts, d_masks, nblk, pl.traces, rd,
                                 r->d_err, ss2, P.W, P.row_block, P.rank, P.nranks, st));
   r->seed_idx ^= 1u;
+  r->seq_valid = false;  // the count / emit kernels write the next state alone
+  r->prepass_form = 0;
   ++r->state_seq;
   // the caller's event: the randDirs are written and the next frame's stream state is known (the next frame's
   // RNG count may start on another stream while this frame traces)
@@ -1672,7 +1723,8 @@ static int emit_frame(rfx_renderer *r, FramePlan &pl, const uint32_t *d_counts, 
 }
 
 // The whole pre-pass of a one-device launch in one kernel (rng_fused: count, look-back scan and scatter), with
-// emit_frame's bookkeeping.  RFX_RNG_FUSED=0 keeps the two-kernel form (rng_count, then emit_frame).
+// emit_frame's bookkeeping.  RFX_RNG_FUSED=0 keeps the two-kernel form (rng_count, then emit_frame).  Only where the
+// cycle table is off (prepass_seq below takes every such launch by default, and measured faster at C1's 166 blocks).
 // Launches of at most RFX_RNG_FUSED_MAX_BLOCKS pre-pass blocks take it.  Its block-order ticket (one atomic per
 // workgroup on one word) serialises the launch's start in proportion to the blocks, so it pays only on small launches
 // (interleaved A/B, frame ms, one-pass / two-kernel, profiles/r06/ab/prepass_limit_*_r6e.jsonl): 640x480 (166 blocks)
@@ -1702,6 +1754,61 @@ static int prepass_fused(rfx_renderer *r, FramePlan &pl, uint64_t nblk, uint32_t
                              r->d_rng_ticket, r->rng_tickets, r->rng_epoch, pl.st));
   r->rng_tickets += nblk;  // every block of the launch takes one ticket
   r->seed_idx ^= 1u;
+  r->seq_valid = false;
+  r->prepass_form = 2;
+  ++r->state_seq;
+  if (emitted) HIP_CHECK(hipEventRecord(emitted, pl.st));
+  return RFX_OK;
+}
+
+// The pre-pass from the cycle table (rfx_kernels.hip "the cycle table"): one emit launch, after the table's one-off
+// build on the first frame that takes it and, when the stream state was last set by anything but a table emit, the
+// one-workgroup rng_locate.  A launch takes it when its blocks and the one for the misaligned start stay well under one
+// cycle (15/16 of it: a 2^30-trace launch has half a cycle's blocks, the 2^31 limit a whole one and keeps the kernels).
+static bool seq_prepass(const rfx_renderer *r, const FramePlan &pl, uint64_t nblk)
+{
+  return RFX_RNG_SEQ && r->rng_prepass == 1 && !pl.band && (RFX_RNG_SEQ_SPLIT || !pl.split) && pl.P.nranks <= 1 &&
+         nblk >= (uint64_t)RFX_RNG_SEQ_MIN_BLOCKS && nblk + 1 <= (uint64_t)rng_seq_blocks() / 16 * 15;
+}
+
+static int ensure_seq_table(rfx_renderer *r, hipStream_t st)
+{
+  if (r->d_seq_p) return RFX_OK;
+  const uint32_t nb = rng_seq_blocks(), nh = rng_seq_header_words();
+  std::vector<uint32_t> hdr(nh), state(nb);
+  rng_seq_tables(hdr.data(), state.data());
+  uint32_t *d_p = nullptr;
+  if (!r->d_seq_hdr) HIP_CHECK(hipMalloc(&r->d_seq_hdr, nh * sizeof(uint32_t)));
+  if (!r->d_seq_state) HIP_CHECK(hipMalloc(&r->d_seq_state, (size_t)nb * sizeof(uint32_t)));
+  if (!r->d_seq_tiles) HIP_CHECK(hipMalloc(&r->d_seq_tiles, ((size_t)nb / 4096 + 4) * sizeof(uint32_t)));
+  if (!r->d_seq_pos) HIP_CHECK(hipMalloc(&r->d_seq_pos, 4 * sizeof(uint32_t)));
+  HIP_CHECK(hipMalloc(&d_p, ((size_t)nb + 4) * sizeof(uint32_t)));
+  hipError_t e = hipMemcpy(r->d_seq_hdr, hdr.data(), nh * sizeof(uint32_t), hipMemcpyHostToDevice);
+  if (e == hipSuccess) e = hipMemcpy(r->d_seq_state, state.data(), (size_t)nb * sizeof(uint32_t), hipMemcpyHostToDevice);
+  if (e == hipSuccess) e = launch_rng_seq_build(r->d_seq_hdr, r->d_seq_state, d_p, r->d_seq_tiles, st);
+  if (e == hipSuccess) e = hipStreamSynchronize(st);  // once per renderer: later frames may come on any stream
+  if (e != hipSuccess)
+  {
+    (void)hipFree(d_p);
+    return fail(RFX_ERR_HIP, "cycle table: %s", hipGetErrorString(e));
+  }
+  r->d_seq_p = d_p;
+  r->seq_valid = false;
+  return RFX_OK;
+}
+
+static int prepass_seq(rfx_renderer *r, FramePlan &pl, uint64_t nblk, uint32_t *rd, hipEvent_t emitted)
+{
+  int rc;
+  if ((rc = ensure_seq_table(r, pl.st)) != RFX_OK) return rc;
+  uint32_t *pos = r->d_seq_pos + 2 * r->seed_idx, *next_pos = r->d_seq_pos + 2 * (r->seed_idx ^ 1u);
+  if (!r->seq_valid)
+    HIP_CHECK(launch_rng_locate(seed_cur(r), r->d_seq_hdr, r->d_seq_state, r->d_seq_p, pos, pl.st));
+  HIP_CHECK(launch_rng_emit_seq(pos, r->d_seq_hdr, r->d_seq_state, r->d_seq_p, nblk + 1, pl.traces, rd, seed_next(r),
+                                next_pos, r->d_err, pl.st));
+  r->seed_idx ^= 1u;
+  r->seq_valid = true;
+  r->prepass_form = 1;
   ++r->state_seq;
   if (emitted) HIP_CHECK(hipEventRecord(emitted, pl.st));
   return RFX_OK;
@@ -1986,6 +2093,7 @@ extern "C" int rfx_frame_rng_discard(rfx_renderer *r)
 {
   if (!r) return fail(RFX_ERR_ARG, "frame_rng_discard: null renderer");
   r->rewind_ok = false;
+  r->seq_valid = false;
   if (r->emit_pending >= 0)
   {
     r->seed_idx ^= 1u;
@@ -2039,9 +2147,11 @@ extern "C" int rfx_render_frame(rfx_renderer *r, const rfx_frame *f, float *d_rg
   if ((rc = timing_start(r, pl.st)) != RFX_OK) return rc;
   if (r->emit_pending >= 0)
     return fail(RFX_ERR_STATE, "render_frame: an emitted frame awaits rfx_render_frame_emitted (or rfx_frame_rng_discard)");
-  if (fused_prepass(pl, nblk))
+  if (seq_prepass(r, pl, nblk) || fused_prepass(pl, nblk))
   {
-    if ((rc = prepass_fused(r, pl, nblk, r->d_rd, nullptr)) != RFX_OK) return rc;
+    if ((rc = seq_prepass(r, pl, nblk) ? prepass_seq(r, pl, nblk, r->d_rd, nullptr)
+                                       : prepass_fused(r, pl, nblk, r->d_rd, nullptr)) != RFX_OK)
+      return rc;
     r->trace_buf = 0;
     if ((rc = timing_event(r, pl.st)) != RFX_OK) return rc;
     if ((rc = trace_frame(r, pl, r->d_rd, d_rgb, d_argb, d_counters)) != RFX_OK) return rc;
@@ -2112,7 +2222,11 @@ static int render_split(rfx_renderer *r, const rfx_frame *f, uint64_t p0, uint64
     if (k > 0) HIP_CHECK(hipStreamWaitEvent(s2[side], r->split_ev[side ^ 1], 0));  // span k - 1's end state
     if ((rc = timing_start(r, pl.st)) != RFX_OK) return rc;
     uint32_t *rd = side ? r->d_rd_alt : r->d_rd;
-    if (fused_prepass(pl, nblk))
+    if (seq_prepass(r, pl, nblk))  // from the (seed, k, A) the last span's emit wrote
+    {
+      if ((rc = prepass_seq(r, pl, nblk, rd, r->split_ev[side])) != RFX_OK) return rc;
+    }
+    else if (fused_prepass(pl, nblk))
     {
       if ((rc = prepass_fused(r, pl, nblk, rd, r->split_ev[side])) != RFX_OK) return rc;
     }
@@ -2149,6 +2263,7 @@ extern "C" int rfx_frame_rng_rewind(rfx_renderer *r)
   if (!r) return fail(RFX_ERR_ARG, "frame_rng_rewind: null renderer");
   if (!r->rewind_ok) return fail(RFX_ERR_STATE, "frame_rng_rewind: the last call was not rfx_render_frame");
   if (r->rewind_flip) r->seed_idx ^= 1u;
+  r->seq_valid = false;
   ++r->state_seq;
   if (r->rewind_saved)
   {
@@ -2363,6 +2478,7 @@ extern "C" int rfx_rand_dirs(rfx_renderer *r, uint32_t seed, uint64_t n, float *
   uint32_t after = 0;
   HIP_CHECK(hipMemcpyAsync(&after, seed_cur(r), sizeof(uint32_t), hipMemcpyDeviceToHost, r->stream));  // flipped
   HIP_CHECK(hipMemcpyAsync(seed_cur(r), &saved, sizeof(uint32_t), hipMemcpyHostToDevice, r->stream));
+  r->seq_valid = false;
   if ((rc = rfx_synchronize(r)) != RFX_OK) return rc;
   for (uint64_t i = 0; i < n; ++i)  // Vector3.cpp:182-184 from each trace's state
   {
@@ -2469,6 +2585,41 @@ extern "C" int rfx_kat_div(rfx_renderer *r, uint64_t first, uint64_t n, uint64_t
   return RFX_OK;
 }
 
+extern "C" uint32_t rfx_rng_seq_blocks(void) { return rng_seq_blocks(); }
+
+extern "C" int rfx_kat_rng_seq_prefix(rfx_renderer *r, uint32_t *prefix)
+{
+  if (!r || !prefix) return fail(RFX_ERR_ARG, "kat_rng_seq_prefix: bad args");
+  int rc;
+  if ((rc = set_dev(r)) != RFX_OK) return rc;
+  if ((rc = ensure_seq_table(r, r->stream)) != RFX_OK) return rc;
+  HIP_CHECK(hipStreamSynchronize(r->stream));
+  HIP_CHECK(hipMemcpy(prefix, r->d_seq_p, ((size_t)rng_seq_blocks() + 1) * sizeof(uint32_t), hipMemcpyDeviceToHost));
+  return RFX_OK;
+}
+
+extern "C" int rfx_kat_rng_seq_legacy(rfx_renderer *r, uint32_t *counts)
+{
+  if (!r || !counts) return fail(RFX_ERR_ARG, "kat_rng_seq_legacy: bad args");
+  int rc;
+  if ((rc = set_dev(r)) != RFX_OK) return rc;
+  const uint64_t nb = rng_seq_blocks();
+  std::vector<uint32_t> jump(2 * (256 + nb));
+  rng_jump_table(nb, jump.data());
+  uint32_t *d_jump = nullptr, *d_cnt = nullptr, *d_origin = nullptr;
+  hipError_t e = hipMalloc(&d_jump, jump.size() * sizeof(uint32_t));
+  if (e == hipSuccess) e = hipMalloc(&d_cnt, nb * sizeof(uint32_t));
+  if (e == hipSuccess) e = hipMalloc(&d_origin, sizeof(uint32_t));
+  if (e == hipSuccess) e = hipMemcpy(d_jump, jump.data(), jump.size() * sizeof(uint32_t), hipMemcpyHostToDevice);
+  if (e == hipSuccess) e = hipMemset(d_origin, 0, sizeof(uint32_t));  // the cycle's origin state
+  if (e == hipSuccess) e = launch_rng_count(d_origin, d_jump, d_cnt, 0, nb, nullptr, r->stream);
+  if (e == hipSuccess) e = hipStreamSynchronize(r->stream);
+  if (e == hipSuccess) e = hipMemcpy(counts, d_cnt, nb * sizeof(uint32_t), hipMemcpyDeviceToHost);
+  (void)hipFree(d_jump); (void)hipFree(d_cnt); (void)hipFree(d_origin);
+  if (e != hipSuccess) return fail(RFX_ERR_HIP, "kat_rng_seq_legacy: %s", hipGetErrorString(e));
+  return RFX_OK;
+}
+
 extern "C" int rfx_kat_argb(rfx_renderer *r, const float *rgb, uint64_t n, uint32_t *out)
 {
   if (!r || (n && (!rgb || !out))) return fail(RFX_ERR_ARG, "kat_argb: bad args");
@@ -2497,7 +2648,11 @@ extern "C" int rfx_kat_kernarg(rfx_renderer *r, int swapped, uint32_t out[3])
 
 // ============================================================== internals shared with rfx_group.cpp (rfx_internal.h)
 int rfx_detail_fail(int code, const char *msg) { return fail(code, "%s", msg); }
-uint32_t *rfx_detail_seed_word(rfx_renderer *r) { return seed_cur(r); }
+uint32_t *rfx_detail_seed_word(rfx_renderer *r)
+{
+  r->seq_valid = false;  // the caller may write the word (a group hands member 0's state to the others)
+  return seed_cur(r);
+}
 uint32_t rfx_detail_jitter(const rfx_renderer *r) { return r->jitter_seed; }
 void rfx_detail_set_jitter(rfx_renderer *r, uint32_t jitter) { r->jitter_seed = jitter; }
 hipStream_t rfx_detail_stream(const rfx_renderer *r) { return r->stream; }

@@ -1,11 +1,14 @@
 // gfx950 kernels of librfx.so besides the trace kernel families (rfx_trace.h, rfx_trace_*.hip):
 //   rng_count / rng_emit : the reference's serial LCG stream (trace_math.h:34-39, Vector3.cpp:176-188) as a
 //       parallel pre-pass;
+//   rng_seq_* / rng_locate / rng_emit_seq : the same stream from the once-built table of the LCG's whole cycle;
 //   lpt_hist / lpt_scan / lpt_scatter : the longest-tile-first schedule of the trace launch;
 //   qs_hist / qs_scan / qs_scatter : the regroup queue's bucket order (ray regrouping of large scenes);
 //   kat_* : the trace kernel's primitive code on known-answer inputs (rfx.h rfx_kat_*);
 // and the library-internal launchers.
 #include "rfx_trace.h"
+
+#include <vector>
 
 #pragma clang fp contract(off)
 
@@ -341,12 +344,21 @@ __device__ __forceinline__ EmitIn emit_in(uint32_t b, const uint32_t *seed, cons
 // One block of the emit: block b's accepted triples are the traces [off, off + in.cnt).  Every thread of the workgroup
 // calls it with the same off and b's inputs (emit_in).  have_masks: in.mask holds the thread's accept flags (rng_count's), so only the LCG
 // states are regenerated.
+// skip: the block's first skip accepted triples belong to no trace of this launch (rng_emit_seq: the part of a cycle
+// block before the frame's start; off is then the trace of accepted triple skip).  seq (optional, with next_seed): the
+// block is cycle block seq->base / kTriplesPerBlock and seq->before accepted triples precede it in the cycle, and the
+// thread that writes the next frame's state also writes its place in the cycle (rng_emit_seq).
+struct EmitSeq {
+  uint32_t base, before;  // index of the block's first triple in the cycle; accepted triples of the cycle before it
+  uint32_t *next_pos;     // the next frame's (k, A)
+};
 __device__ __forceinline__ void emit_block(uint64_t off, const EmitIn &in, bool have_masks, uint64_t need,
                                            uint32_t *rd_state, uint32_t *next_seed, const EmitFilter &flt,
-                                           uint32_t *sst, uint32_t *wsum)
+                                           uint32_t *sst, uint32_t *wsum, uint32_t skip = 0u,
+                                           const EmitSeq *seq = nullptr)
 {
   if (off >= need) return;
-  const uint32_t cnt = (uint32_t)min((uint64_t)in.cnt, need - off);  // triples this block emits
+  const uint32_t cnt = (uint32_t)min((uint64_t)(in.cnt - skip), need - off);  // triples this block emits
   const uint64_t last = off + cnt - 1;
   // block-uniform skip: a block whose accepted indices all belong to other ranks' strips (and do not
   // include the frame's last trace, whose stream state every rank carries forward) writes nothing
@@ -390,8 +402,22 @@ __device__ __forceinline__ void emit_block(uint64_t off, const EmitIn &in, bool 
   for (int j = 0; j < kTriplesPerThread; ++j)
     if ((acc >> j) & 1u)
     {
-      if (li == fin) *next_seed = lcg_step(lcg_step(lcg_step(st[j])));
-      if (li < cnt) sst[li] = st[j];
+      const uint32_t ti = li - skip;  // the block's trace this triple is (wraps past cnt for a skipped one)
+      if (ti < cnt)
+      {
+        if (ti == fin)
+        {
+          *next_seed = lcg_step(lcg_step(lcg_step(st[j])));
+          if (seq)
+          {
+            // the triple after this one: its index in the cycle and the accepted triples before it (index 0: none)
+            const uint32_t k = seq->base + (uint32_t)kTriplesPerThread * threadIdx.x + (uint32_t)j + 1u;
+            seq->next_pos[0] = k;
+            seq->next_pos[1] = k ? seq->before + li + 1u : 0u;
+          }
+        }
+        sst[ti] = st[j];
+      }
       ++li;
     }
   __syncthreads();
@@ -768,8 +794,8 @@ __global__ __launch_bounds__(kRngBlock) void rng_fused(const uint32_t *seed, con
   {
     // The look-back outwaited its bound (only a broken invariant gets here): the offset is recomputed from the random
     // stream itself -- the accept counts of blocks 0 .. b - 1, regenerated by this workgroup -- so the frame's randDirs
-    // stay exact whatever the other blocks do.  Bit 4 of the error word records that it happened (not an error: the
-    // frame is exact; rfx_synchronize fails only on bits 1 and 2).
+    // stay exact whatever the other blocks do.  Value 4 in the error word records that it happened: the frame is exact,
+    // so it is not an error -- the host fails a call on bit 0 alone (a stream too short for the frame).
     uint32_t part = 0;
     for (uint32_t pb = 0; pb < b; ++pb)
     {
@@ -803,6 +829,157 @@ __global__ __launch_bounds__(kRngBlock) void rng_fused(const uint32_t *seed, con
     }
   __syncthreads();
   for (uint32_t i = threadIdx.x; i < cnt; i += kRngBlock) rd_state[off + i] = sst[i];
+}
+
+// ------------------------------------------------------------- the cycle table (RFX_RNG_SEQ)
+// Whether a triple is accepted depends on the LCG state before it alone, and one triple (three draws) is itself an affine
+// map mod 2^32 of full period: multiplier 214013^3 = 1 (mod 4), odd increment.  So from a fixed origin state (0) there
+// are exactly 2^32 triples, indexed k, and every frame's stream is a contiguous run of that one cyclic sequence.  The
+// accept counts of the whole cycle are therefore constants of the algorithm.  They are counted once per renderer, in
+// blocks of kTriplesPerBlock triples aligned to k (kSeqBlocks of them):
+//   state[B]: the LCG state before triple kTriplesPerBlock B (host: rng_seq_tables);
+//   P[B]: the accepted triples of blocks [0, B), P[kSeqBlocks] the cycle's total T (about 2.25e9: 32 bits hold it).
+// A frame that starts at triple k with A accepted triples before k in the cycle then needs one launch (rng_emit_seq):
+// block b takes cycle block B = (k / kTriplesPerBlock + b) mod kSeqBlocks and its first trace is P[B] - A (+ T past the
+// wrap) -- no count kernel, no per-block sum of the counts before it, no look-back.
+constexpr uint32_t kSeqBlocks = (uint32_t)((1ull << 32) / kTriplesPerBlock);
+static_assert((uint64_t)kSeqBlocks * kTriplesPerBlock == (1ull << 32), "the cycle is a whole number of blocks");
+static_assert(kSeqBlocks % kScanTileCounts == 0, "rng_seq_scan: whole tiles");
+
+// thread tid's first state in the block that starts at state s: tj = the thread jumps of rng_jump_table (its first
+// kRngBlock pairs)
+__device__ __forceinline__ uint32_t seq_thread_state(uint32_t s, const uint32_t *tj, uint32_t tid)
+{
+  return tj[2 * tid] * s + tj[2 * tid + 1];
+}
+
+// cnt[B]: the accepted triples of cycle block B (rng_count's count, from the block's tabulated state)
+__global__ __launch_bounds__(kRngBlock) void rng_seq_count(const uint32_t *state, const uint32_t *tj, uint32_t *cnt)
+{
+  const uint32_t B = blockIdx.x;
+  uint32_t c = (uint32_t)__popc(thread_flags<false>(seq_thread_state(state[B], tj, threadIdx.x), nullptr));
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) c += __shfl_xor(c, off, 64);
+  __shared__ uint32_t wsum[kRngBlock / 64];
+  if ((threadIdx.x & 63) == 0) wsum[threadIdx.x >> 6] = c;
+  __syncthreads();
+  if (threadIdx.x == 0)
+  {
+    uint32_t tot = 0;
+    for (int w = 0; w < kRngBlock / 64; ++w) tot += wsum[w];
+    cnt[B] = tot;
+  }
+}
+
+// p (the counts of kSeqBlocks blocks, then one more word) <- their exclusive prefix sums, in place, and the total in the
+// last word: one workgroup per tile of kScanTileCounts counts, as rng_tile_scan (tile_sum: rng_tile_sums' totals).  A tile
+// reads only its own counts and the tile totals, so scanning in place is safe.
+__global__ __launch_bounds__(kScanThreads) void rng_seq_scan(uint32_t *p, const uint32_t *tile_sum)
+{
+  static_assert(kScanTileCounts == 4 * kScanThreads, "rng_seq_scan: four counts per thread");
+  __shared__ uint32_t wsum[kScanThreads / 64];
+  __shared__ uint32_t s_pre;
+  const uint32_t tid = threadIdx.x, lane = tid & 63u, wv = tid >> 6;
+  uint32_t pre = 0;  // (the cycle's total fits 32 bits, so every prefix does)
+  for (uint32_t t = tid; t < blockIdx.x; t += kScanThreads) pre += tile_sum[t];
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) pre += __shfl_xor(pre, o, 64);
+  if (tid == 0) s_pre = 0;
+  __syncthreads();
+  if (lane == 0 && pre) atomicAdd(&s_pre, pre);
+  __syncthreads();
+  uint4 *v = reinterpret_cast<uint4 *>(p + (size_t)blockIdx.x * kScanTileCounts) + tid;
+  const uint4 a = *v;
+  const uint32_t sum = a.x + a.y + a.z + a.w;
+  uint32_t inc = sum;
+#pragma unroll
+  for (int o = 1; o < 64; o <<= 1)
+  {
+    const uint32_t t = __shfl_up(inc, o, 64);
+    if (lane >= (uint32_t)o) inc += t;
+  }
+  if (lane == 63) wsum[wv] = inc;
+  __syncthreads();
+  uint32_t wb = 0, tot = 0;
+  for (uint32_t w = 0; w < kScanThreads / 64; ++w)
+  {
+    wb += w < wv ? wsum[w] : 0u;
+    tot += wsum[w];
+  }
+  const uint32_t e = s_pre + wb + (inc - sum);
+  *v = make_uint4(e, e + a.x, e + a.x + a.y, e + a.x + a.y + a.z);
+  if (blockIdx.x == gridDim.x - 1 && tid == 0) p[kSeqBlocks] = s_pre + tot;
+}
+
+// The place of state s in the cycle: the k with (triple map)^k (origin) = s.  The low j bits of a full-period LCG's
+// state have period 2^j, so k mod 2^j is fixed by s mod 2^j: bit j of k is set exactly when the state reached so far
+// differs from s in bit j.  pow2: the (A, C) of 2^j triples, j < 32 (host: rng_seq_tables) -- 32 multiply-adds.
+__host__ __device__ inline uint32_t seq_index_of(uint32_t s, const uint32_t *pow2)
+{
+  uint32_t k = 0, x = 0;  // x: the origin jumped k triples
+  for (int j = 0; j < 32; ++j)
+    if ((x ^ s) >> j & 1u)
+    {
+      k |= 1u << j;
+      x = pow2[2 * j] * x + pow2[2 * j + 1];
+    }
+  return k;
+}
+
+// pos <- (k, A) of the stream state *seed: its triple index in the cycle and the accepted triples before it -- P of its
+// block plus the accepted triples of the block before k.  One workgroup; runs only when the stream state was set by
+// something other than a table emit (host: seq_valid).
+__global__ __launch_bounds__(kRngBlock) void rng_locate(const uint32_t *seed, const uint32_t *pow2, const uint32_t *state,
+                                                        const uint32_t *tj, const uint32_t *p, uint32_t *pos)
+{
+  __shared__ uint32_t wsum[kRngBlock / 64];
+  const uint32_t k = seq_index_of(*seed, pow2);  // (every thread: 32 dependent multiply-adds, no exchange)
+  const uint32_t B = k / (uint32_t)kTriplesPerBlock, r = k % (uint32_t)kTriplesPerBlock;
+  const uint32_t acc = thread_flags<false>(seq_thread_state(state[B], tj, threadIdx.x), nullptr);
+  // of this thread's triples [16 tid, 16 tid + 16) of the block, those before triple r
+  const uint32_t first = (uint32_t)kTriplesPerThread * threadIdx.x;
+  const uint32_t n = r > first ? min(r - first, (uint32_t)kTriplesPerThread) : 0u;
+  uint32_t c = (uint32_t)__popc(acc & ((1u << n) - 1u));
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) c += __shfl_xor(c, off, 64);
+  if ((threadIdx.x & 63) == 0) wsum[threadIdx.x >> 6] = c;
+  __syncthreads();
+  if (threadIdx.x == 0)
+  {
+    uint32_t tot = 0;
+    for (int w = 0; w < kRngBlock / 64; ++w) tot += wsum[w];
+    pos[0] = k;
+    pos[1] = p[B] + tot;
+  }
+}
+
+// The frame's randDirs in one launch: pos = (k, A) of the frame's start state.  Block b emits cycle block
+// B = (k / kTriplesPerBlock + b) mod kSeqBlocks; block 0 drops the accepted triples before k.  The grid covers the
+// frame's blocks and the misaligned start (host: rng_blocks_for + 1, well under one cycle), so no cycle block is taken
+// twice and the offsets wrap at most once.
+__global__ __launch_bounds__(kRngBlock) void rng_emit_seq(const uint32_t *pos, const uint32_t *state, const uint32_t *tj,
+                                                          const uint32_t *p, uint64_t need, uint32_t *rd_state,
+                                                          uint32_t *next_seed, uint32_t *next_pos, int *err)
+{
+  __shared__ uint32_t sst[kTriplesPerBlock];
+  __shared__ uint32_t wsum[kRngBlock / 64];
+  const uint32_t k = pos[0], A = pos[1];
+  const uint32_t T = p[kSeqBlocks];
+  const uint32_t Bu = k / (uint32_t)kTriplesPerBlock + blockIdx.x, B = Bu % kSeqBlocks;
+  const uint32_t before = p[B];
+  EmitIn in;
+  in.cnt = p[B + 1] - before;
+  in.s0 = seq_thread_state(state[B], tj, threadIdx.x);
+  in.mask = 0u;
+  uint64_t off = 0;
+  uint32_t skip = 0;
+  if (blockIdx.x == 0) skip = min(A - before, in.cnt);  // the accepted triples of the block before k
+  else off = (uint64_t)before + (Bu >= kSeqBlocks ? (uint64_t)T : 0ull) - (uint64_t)A;
+  // the last block flags a stream too short for the frame (host: RFX_ERR_RNG)
+  if (blockIdx.x == gridDim.x - 1 && threadIdx.x == 0 && off + (in.cnt - skip) < need) *err = 1;
+  const EmitFilter flt{1, 1, 1, 0, 1, 0, UINT64_MAX};
+  const EmitSeq seq{B * (uint32_t)kTriplesPerBlock, before, next_pos};
+  emit_block(off, in, false, need, rd_state, next_seed, flt, sst, wsum, skip, &seq);
 }
 
 // ------------------------------------------------------------- device known-answer kernels
@@ -1176,6 +1353,76 @@ hipError_t launch_rng_fused(const uint32_t *d_seed, const uint32_t *d_jump, uint
 {
   hipLaunchKernelGGL(rng_fused, dim3((uint32_t)nblk), dim3(kRngBlock), 0, st, d_seed, d_jump, (uint32_t)nblk, traces,
                      d_rd_state, d_next_seed, d_err, d_status, d_ticket, base, epoch);
+  return hipGetLastError();
+}
+
+// ---- the cycle table (rng_seq_count ... rng_emit_seq)
+uint32_t rng_seq_blocks() { return kSeqBlocks; }
+// words of rng_seq_tables' header: the thread jumps (rng_jump_table's first kRngBlock pairs), then the (A, C) of 2^j
+// triples, j < 32
+constexpr uint32_t kSeqPow2 = 2 * kRngBlock, kSeqHeader = kSeqPow2 + 64;
+uint32_t rng_seq_header_words() { return kSeqHeader; }
+
+// hdr (rng_seq_header_words words): the thread jumps and the power-of-two triple jumps; state (kSeqBlocks words, or
+// null): the LCG state before each block's first triple, the origin (state 0) jumped block by block
+void rng_seq_tables(uint32_t *hdr, uint32_t *state)
+{
+  std::vector<uint32_t> jump(2 * (kRngBlock + 2));
+  rng_jump_table(2, jump.data());
+  for (uint32_t i = 0; i < kSeqPow2; ++i) hdr[i] = jump[i];
+  const uint32_t ab = jump[2 * (kRngBlock + 1)], cb = jump[2 * (kRngBlock + 1) + 1];  // one block's draws
+  uint32_t a = kTripleJump.m[1].a, c = kTripleJump.m[1].c;  // one triple
+  for (int j = 0; j < 32; ++j)
+  {
+    hdr[kSeqPow2 + 2 * j] = a;
+    hdr[kSeqPow2 + 2 * j + 1] = c;
+    c = a * c + c;  // the map applied twice
+    a = a * a;
+  }
+  if (!state) return;
+  uint32_t s = 0;
+  for (uint32_t b = 0; b < kSeqBlocks; ++b)
+  {
+    state[b] = s;
+    s = ab * s + cb;
+  }
+}
+
+// the triple index of LCG state s in the cycle that starts at state 0 (rfx.h rfx_rng_triple_index)
+uint32_t rng_seq_index_of(uint32_t s)
+{
+  uint32_t hdr[kSeqHeader];
+  rng_seq_tables(hdr, nullptr);
+  return seq_index_of(s, hdr + kSeqPow2);
+}
+
+// Builds the table: d_p (kSeqBlocks + 4 words, 16-byte aligned) <- the exclusive prefix of the blocks' accept counts and
+// the cycle's total; d_tiles: kSeqBlocks / kScanTileCounts + 4 words of scratch.
+hipError_t launch_rng_seq_build(const uint32_t *d_hdr, const uint32_t *d_state, uint32_t *d_p, uint32_t *d_tiles,
+                                hipStream_t st)
+{
+  const uint32_t ntiles = kSeqBlocks / kScanTileCounts;
+  hipLaunchKernelGGL(rng_seq_count, dim3(kSeqBlocks), dim3(kRngBlock), 0, st, d_state, d_hdr, d_p);
+  hipLaunchKernelGGL(rng_tile_sums, dim3(ntiles), dim3(kTileSumThreads), 0, st, (const uint32_t *)d_p,
+                     (uint64_t)kSeqBlocks, d_tiles, d_tiles + ntiles);  // (its three range words: unused here)
+  hipLaunchKernelGGL(rng_seq_scan, dim3(ntiles), dim3(kScanThreads), 0, st, d_p, (const uint32_t *)d_tiles);
+  return hipGetLastError();
+}
+
+hipError_t launch_rng_locate(const uint32_t *d_seed, const uint32_t *d_hdr, const uint32_t *d_state, const uint32_t *d_p,
+                             uint32_t *d_pos, hipStream_t st)
+{
+  hipLaunchKernelGGL(rng_locate, dim3(1), dim3(kRngBlock), 0, st, d_seed, d_hdr + kSeqPow2, d_state, d_hdr, d_p, d_pos);
+  return hipGetLastError();
+}
+
+// nblk: the launch's blocks, the one for the misaligned start included (fewer than kSeqBlocks)
+hipError_t launch_rng_emit_seq(const uint32_t *d_pos, const uint32_t *d_hdr, const uint32_t *d_state, const uint32_t *d_p,
+                               uint64_t nblk, uint64_t traces, uint32_t *d_rd_state, uint32_t *d_next_seed,
+                               uint32_t *d_next_pos, int *d_err, hipStream_t st)
+{
+  hipLaunchKernelGGL(rng_emit_seq, dim3((uint32_t)nblk), dim3(kRngBlock), 0, st, d_pos, d_state, d_hdr, d_p, traces,
+                     d_rd_state, d_next_seed, d_next_pos, d_err);
   return hipGetLastError();
 }
 

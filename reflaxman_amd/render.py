@@ -362,6 +362,28 @@ class Renderer:
         LDS-staged BVH."""
         return _lib.load().rfx_renderer_bounce_form(self._h)
 
+    def set_rng_prepass(self, mode: int):
+        """The RNG pre-pass of one-device unsplit frames (rfx.h rfx_renderer_set_rng_prepass): 1 the cycle table
+        (default), 0 the count and emit kernels of every frame.  No pixel changes."""
+        check(_lib.load().rfx_renderer_set_rng_prepass(self._h, int(mode)), "set_rng_prepass")
+
+    def prepass_form(self) -> int:
+        """The last launch's pre-pass (rfx.h rfx_renderer_prepass_form): 0 count / emit kernels, 1 the cycle table, 2 the
+        one-pass kernel."""
+        return _lib.load().rfx_renderer_prepass_form(self._h)
+
+    def kat_rng_seq_prefix(self) -> np.ndarray:
+        """The cycle table's prefix of accept counts, rfx_rng_seq_blocks() + 1 words (rfx.h rfx_kat_rng_seq_prefix)."""
+        out = np.zeros(_lib.load().rfx_rng_seq_blocks() + 1, np.uint32)
+        check(_lib.load().rfx_kat_rng_seq_prefix(self._h, _lib.u32ptr(out)), "rfx_kat_rng_seq_prefix")
+        return out
+
+    def kat_rng_seq_legacy(self) -> np.ndarray:
+        """The same blocks' accept counts from the per-frame count kernel (rfx.h rfx_kat_rng_seq_legacy)."""
+        out = np.zeros(_lib.load().rfx_rng_seq_blocks(), np.uint32)
+        check(_lib.load().rfx_kat_rng_seq_legacy(self._h, _lib.u32ptr(out)), "rfx_kat_rng_seq_legacy")
+        return out
+
     def set_tri_accel(self, mode: int):
         """Triangle BVH of non-small scenes (rfx.h rfx_renderer_set_tri_accel): -1 automatic (default), 0 off, 1 on,
         2 on with narrow bundles walking the tree too (A/B).  Takes effect at the next set_scene (which then uploads again).  No pixel changes."""

@@ -112,6 +112,9 @@ VARIANTS = {
     "trileaf2": ["RFX_TRI_BVH_LEAF=2"],
     "trileaf8": ["RFX_TRI_BVH_LEAF=8"],
     "trinarrow": ["RFX_TRI_BVH_NARROW_MIN=0"],  # narrow bundles walk the triangle tree at any count
+    "seq0": ["RFX_RNG_SEQ=0"],  # every frame's pre-pass by the count / emit kernels (no cycle table)
+    "seqsplit0": ["RFX_RNG_SEQ_SPLIT=0"],  # the spans of split frames keep the count / scan / emit kernels
+    "seqbig": ["RFX_RNG_SEQ_MIN_BLOCKS=257"],  # the table only where rng_fused does not apply
     "trinonarrow": ["RFX_TRI_BVH_NARROW_MIN=(1<<30)"],  # narrow bundles always keep the bundle-culled chunk loop (base)
 }
 
