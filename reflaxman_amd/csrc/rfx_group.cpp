@@ -21,29 +21,15 @@
 #include <string.h>
 
 #include <algorithm>
-#include <string>
 #include <vector>
 
 #include "rfx_internal.h"
 
+using rfx::fail;
+
 namespace {
 constexpr int kBalanceEvery = 8;
 constexpr uint32_t kGrain = 8;
-
-int hip_fail(hipError_t e, const char *what)
-{
-  return rfx_detail_fail(RFX_ERR_HIP, (std::string(what) + ": " + hipGetErrorString(e)).c_str());
-}
-#define GCHECK(expr)                                  \
-  do {                                                \
-    hipError_t e_ = (expr);                           \
-    if (e_ != hipSuccess) return hip_fail(e_, #expr); \
-  } while (0)
-#define RCHECK(expr)             \
-  do {                           \
-    int rc_ = (expr);            \
-    if (rc_ != RFX_OK) return rc_; \
-  } while (0)
 
 // strictly increasing bounds, each band at least `grain` rows where the frame allows it (dist.py _fix_bounds)
 std::vector<uint32_t> fix_bounds(std::vector<double> b, uint32_t H, uint32_t grain)
@@ -181,23 +167,24 @@ static int create(rfx_group *g, const int *devices, int n)
     {
       if (g->dev[i] == g->dev[j]) continue;
       int can = 0;
-      GCHECK(hipDeviceCanAccessPeer(&can, g->dev[i], g->dev[j]));
+      HIP_CHECK(hipDeviceCanAccessPeer(&can, g->dev[i], g->dev[j]));
       if (!can) continue;  // hipMemcpyPeerAsync still works, staged by the runtime
-      GCHECK(hipSetDevice(g->dev[i]));
+      HIP_CHECK(hipSetDevice(g->dev[i]));
       const hipError_t e = hipDeviceEnablePeerAccess(g->dev[j], 0);
-      if (e != hipSuccess && e != hipErrorPeerAccessAlreadyEnabled) return hip_fail(e, "hipDeviceEnablePeerAccess");
+      if (e != hipSuccess && e != hipErrorPeerAccessAlreadyEnabled)
+        return fail(RFX_ERR_HIP, "hipDeviceEnablePeerAccess: %s", hipGetErrorString(e));
       (void)hipGetLastError();
     }
   for (int i = 0; i < n; ++i)
   {
-    GCHECK(hipSetDevice(g->dev[i]));
+    HIP_CHECK(hipSetDevice(g->dev[i]));
     hipStream_t s = nullptr, c = nullptr;
-    GCHECK(hipStreamCreateWithFlags(&s, hipStreamNonBlocking));
+    HIP_CHECK(hipStreamCreateWithFlags(&s, hipStreamNonBlocking));
     g->own.push_back(s);
-    GCHECK(hipStreamCreateWithFlags(&c, hipStreamNonBlocking));
+    HIP_CHECK(hipStreamCreateWithFlags(&c, hipStreamNonBlocking));
     g->cp.push_back(c);
     hipEvent_t e[7];
-    for (hipEvent_t &x : e) GCHECK(hipEventCreate(&x));
+    for (hipEvent_t &x : e) HIP_CHECK(hipEventCreate(&x));
     g->ev_start.push_back(e[0]);
     g->ev_cnt.push_back(e[1]);
     g->ev_emit[0].push_back(e[2]);
@@ -207,7 +194,7 @@ static int create(rfx_group *g, const int *devices, int n)
     g->ev_copied[1].push_back(e[6]);
     // the double-buffer waits of the first two passes find recorded events
     for (int k = 2; k < 7; ++k)
-      if (k != 4) GCHECK(hipEventRecord(e[k], s));
+      if (k != 4) HIP_CHECK(hipEventRecord(e[k], s));
     for (int b = 0; b < 2; ++b)
     {
       g->cnt[b].push_back(nullptr);
@@ -222,7 +209,7 @@ static int create(rfx_group *g, const int *devices, int n)
 
 extern "C" int rfx_group_create(rfx_group **out, const int *devices, int n)
 {
-  if (!out || !devices || n <= 0 || n > 64) return rfx_detail_fail(RFX_ERR_ARG, "group_create: 1..64 devices");
+  if (!out || !devices || n <= 0 || n > 64) return fail(RFX_ERR_ARG, "group_create: 1..64 devices");
   *out = nullptr;
   rfx_group *g = new rfx_group();
   const int rc = create(g, devices, n);
@@ -244,14 +231,14 @@ extern "C" rfx_renderer *rfx_group_renderer(rfx_group *g, int i)
 
 extern "C" int rfx_group_set_scene(rfx_group *g, const rfx_scene *s)
 {
-  if (!g || !s) return rfx_detail_fail(RFX_ERR_ARG, "group_set_scene: bad args");
+  if (!g || !s) return fail(RFX_ERR_ARG, "group_set_scene: bad args");
   for (rfx_renderer *r : g->r) RCHECK(rfx_renderer_set_scene(r, s));
   return RFX_OK;
 }
 
 extern "C" int rfx_group_set_bands(rfx_group *g, uint32_t height, const uint32_t *bounds)
 {
-  if (!g) return rfx_detail_fail(RFX_ERR_ARG, "group_set_bands: null group");
+  if (!g) return fail(RFX_ERR_ARG, "group_set_bands: null group");
   if (!bounds)
   {
     g->fixed = false;
@@ -259,9 +246,9 @@ extern "C" int rfx_group_set_bands(rfx_group *g, uint32_t height, const uint32_t
     return RFX_OK;
   }
   const size_t n = g->n();
-  if (bounds[0] != 0 || bounds[n] != height) return rfx_detail_fail(RFX_ERR_ARG, "group_set_bands: 0 .. height");
+  if (bounds[0] != 0 || bounds[n] != height) return fail(RFX_ERR_ARG, "group_set_bands: 0 .. height");
   for (size_t i = 0; i < n; ++i)
-    if (bounds[i] >= bounds[i + 1]) return rfx_detail_fail(RFX_ERR_ARG, "group_set_bands: bands must be non-empty");
+    if (bounds[i] >= bounds[i + 1]) return fail(RFX_ERR_ARG, "group_set_bands: bands must be non-empty");
   g->bounds.assign(bounds, bounds + n + 1);
   g->fixed = true;
   g->H = height;
@@ -270,8 +257,8 @@ extern "C" int rfx_group_set_bands(rfx_group *g, uint32_t height, const uint32_t
 
 extern "C" int rfx_group_get_bands(const rfx_group *g, uint32_t *bounds)
 {
-  if (!g || !bounds) return rfx_detail_fail(RFX_ERR_ARG, "group_get_bands: bad args");
-  if (g->bounds.empty()) return rfx_detail_fail(RFX_ERR_STATE, "group_get_bands: no frame rendered yet");
+  if (!g || !bounds) return fail(RFX_ERR_ARG, "group_get_bands: bad args");
+  if (g->bounds.empty()) return fail(RFX_ERR_STATE, "group_get_bands: no frame rendered yet");
   std::copy(g->bounds.begin(), g->bounds.end(), bounds);
   return RFX_OK;
 }
@@ -283,15 +270,15 @@ static int collect_times(rfx_group *g)
   const size_t n = g->n();
   for (size_t i = 0; i < n; ++i)
   {
-    GCHECK(hipSetDevice(g->dev[i]));
+    HIP_CHECK(hipSetDevice(g->dev[i]));
     if (hipEventQuery(g->ev_t1[i]) != hipSuccess) return RFX_OK;  // not yet: try after the next frame
   }
   g->timing_pending = false;
   for (size_t i = 0; i < n; ++i)
   {
     float ms = 0.0f;
-    GCHECK(hipSetDevice(g->dev[i]));
-    GCHECK(hipEventElapsedTime(&ms, g->ev_emit[g->timing_parity][i], g->ev_t1[i]));
+    HIP_CHECK(hipSetDevice(g->dev[i]));
+    HIP_CHECK(hipEventElapsedTime(&ms, g->ev_emit[g->timing_parity][i], g->ev_t1[i]));
     g->acc[i] += ms;
   }
   if (++g->acc_frames >= kBalanceEvery)
@@ -313,13 +300,13 @@ static int ensure_buffers(rfx_group *g, const rfx_frame &f0, size_t m)
   {
     for (size_t i = 0; i < n; ++i)
     {
-      GCHECK(hipSetDevice(g->dev[i]));
-      GCHECK(hipDeviceSynchronize());  // frames still in flight read the old arrays
+      HIP_CHECK(hipSetDevice(g->dev[i]));
+      HIP_CHECK(hipDeviceSynchronize());  // frames still in flight read the old arrays
       for (int b = 0; b < 2; ++b)
       {
         (void)hipFree(g->cnt[b][i]);
         g->cnt[b][i] = nullptr;
-        GCHECK(hipMalloc(&g->cnt[b][i], bps * m * sizeof(uint32_t)));
+        HIP_CHECK(hipMalloc(&g->cnt[b][i], bps * m * sizeof(uint32_t)));
       }
     }
     g->cnt_words = bps * m;
@@ -329,14 +316,14 @@ static int ensure_buffers(rfx_group *g, const rfx_frame &f0, size_t m)
   {
     for (size_t i = 0; i < n; ++i)
     {
-      GCHECK(hipSetDevice(g->dev[i]));
-      GCHECK(hipDeviceSynchronize());  // traces and copies still in flight use the old scratch
+      HIP_CHECK(hipSetDevice(g->dev[i]));
+      HIP_CHECK(hipDeviceSynchronize());  // traces and copies still in flight use the old scratch
       for (int b = 0; b < 2; ++b)
       {
         (void)hipFree(g->rgb[b][i]); (void)hipFree(g->argb[b][i]);
         g->rgb[b][i] = nullptr; g->argb[b][i] = nullptr;
-        GCHECK(hipMalloc(&g->rgb[b][i], px * 3 * sizeof(float)));
-        GCHECK(hipMalloc(&g->argb[b][i], px * sizeof(uint32_t)));
+        HIP_CHECK(hipMalloc(&g->rgb[b][i], px * 3 * sizeof(float)));
+        HIP_CHECK(hipMalloc(&g->argb[b][i], px * sizeof(uint32_t)));
       }
     }
     g->px_cap = px;
@@ -375,66 +362,67 @@ static int group_pass(rfx_group *g, const rfx_frame *f, uint32_t y0, uint32_t y1
   const bool accumulate = f->additive_counter > 1;
   const std::vector<hipStream_t> &st = g->own;
   // 0. the caller's work on its stream before this pass
-  GCHECK(hipSetDevice(g->dev[0]));
-  GCHECK(hipEventRecord(g->ev_start[0], s0));
+  HIP_CHECK(hipSetDevice(g->dev[0]));
+  HIP_CHECK(hipEventRecord(g->ev_start[0], s0));
   bool handoff = !g->seq_ok;
-  for (size_t i = 0; i < g->n(); ++i) handoff = handoff || rfx_detail_state_seq(g->r[i]) != g->seq[i];
-  const uint32_t jitter = rfx_detail_jitter(g->r[0]);
+  for (size_t i = 0; i < g->n(); ++i) handoff = handoff || g->r[i]->rng.state_seq != g->seq[i];
+  const uint32_t jitter = g->r[0]->jitter_seed;
   for (size_t i = 0; i < m; ++i)
   {
-    GCHECK(hipSetDevice(g->dev[i]));
-    if (handoff || accumulate) GCHECK(hipStreamWaitEvent(st[i], g->ev_start[0], 0));
+    HIP_CHECK(hipSetDevice(g->dev[i]));
+    if (handoff || accumulate) HIP_CHECK(hipStreamWaitEvent(st[i], g->ev_start[0], 0));
     // member 0's stream state is the group's: handed to the others when theirs may differ
     if (handoff && i)
-      GCHECK(hipMemcpyPeerAsync(rfx_detail_seed_word(g->r[i]), g->dev[i], rfx_detail_seed_word(g->r[0]), g->dev[0],
+      HIP_CHECK(hipMemcpyPeerAsync(g->r[i]->rng.cur_for_write(), g->dev[i], g->r[0]->rng.cur_for_write(), g->dev[0],
                                 sizeof(uint32_t), st[i]));
-    rfx_detail_set_jitter(g->r[i], jitter);
-    GCHECK(hipStreamWaitEvent(st[i], g->ev_copied[b][i], 0));  // the copy of two passes ago has read scratch b
+    g->r[i]->jitter_seed = jitter;
+    HIP_CHECK(hipStreamWaitEvent(st[i], g->ev_copied[b][i], 0));  // the copy of two passes ago has read scratch b
   }
   // 1. each member counts its slice of the pass's random stream and pushes it to every other member
   const size_t sl = g->bps * sizeof(uint32_t);
   for (size_t i = 0; i < m; ++i)
   {
     RCHECK(rfx_frame_rng_count(g->r[i], &fr[i], (uint32_t)i, (uint32_t)m, g->cnt[b][i], st[i]));
-    GCHECK(hipSetDevice(g->dev[i]));
+    HIP_CHECK(hipSetDevice(g->dev[i]));
     for (size_t j = 0; j < m; ++j)
     {
       if (j == i) continue;
-      GCHECK(hipStreamWaitEvent(st[i], g->ev_emit[b][j], 0));  // j's emit of two passes ago read this array
-      GCHECK(hipMemcpyPeerAsync(g->cnt[b][j] + i * g->bps, g->dev[j], g->cnt[b][i] + i * g->bps, g->dev[i], sl, st[i]));
+      HIP_CHECK(hipStreamWaitEvent(st[i], g->ev_emit[b][j], 0));  // j's emit of two passes ago read this array
+      HIP_CHECK(hipMemcpyPeerAsync(g->cnt[b][j] + i * g->bps, g->dev[j], g->cnt[b][i] + i * g->bps, g->dev[i], sl, st[i]));
     }
-    GCHECK(hipEventRecord(g->ev_cnt[i], st[i]));
+    HIP_CHECK(hipEventRecord(g->ev_cnt[i], st[i]));
   }
   // 2. every slice arrived: emit the band's randDirs and trace the band into scratch; 3. the band rows to the caller's
   // frame on the member's copy stream
   for (size_t i = 0; i < m; ++i)
   {
-    GCHECK(hipSetDevice(g->dev[i]));
+    HIP_CHECK(hipSetDevice(g->dev[i]));
     for (size_t j = 0; j < m; ++j)
-      if (j != i) GCHECK(hipStreamWaitEvent(st[i], g->ev_cnt[j], 0));
+      if (j != i) HIP_CHECK(hipStreamWaitEvent(st[i], g->ev_cnt[j], 0));
     const uint64_t r0 = bd[i], rows = bd[i + 1] - r0;
     float *img = g->rgb[b][i];
     uint32_t *a = g->argb[b][i];
     if (accumulate)  // the accumulated rows this member adds to (Render.cpp:191-194)
-      GCHECK(hipMemcpyPeerAsync(img + r0 * W * 3, g->dev[i], d_rgb + r0 * W * 3, g->dev[0], rows * W * 12, st[i]));
-    const uint32_t j0 = rfx_detail_jitter(g->r[i]);
+      HIP_CHECK(hipMemcpyPeerAsync(img + r0 * W * 3, g->dev[i], d_rgb + r0 * W * 3, g->dev[0], rows * W * 12, st[i]));
+    const uint32_t j0 = g->r[i]->jitter_seed;
     RCHECK(rfx_render_frame_counted_ev(g->r[i], &fr[i], (uint32_t)m, g->cnt[b][i], img, d_argb ? a : nullptr, nullptr,
                                        st[i], g->ev_emit[b][i]));
-    rfx_detail_set_rewindable(g->r[i], j0);
-    GCHECK(hipSetDevice(g->dev[i]));
-    GCHECK(hipEventRecord(g->ev_t1[i], st[i]));
-    GCHECK(hipStreamWaitEvent(g->cp[i], g->ev_t1[i], 0));
-    GCHECK(hipStreamWaitEvent(g->cp[i], g->ev_start[0], 0));  // the caller's frame is free to be written
+    // (one pre-pass flip, jitter advanced from j0: rfx_frame_rng_rewind may undo it, as after rfx_render_frame)
+    g->r[i]->rng.rewindable(j0, true);
+    HIP_CHECK(hipSetDevice(g->dev[i]));
+    HIP_CHECK(hipEventRecord(g->ev_t1[i], st[i]));
+    HIP_CHECK(hipStreamWaitEvent(g->cp[i], g->ev_t1[i], 0));
+    HIP_CHECK(hipStreamWaitEvent(g->cp[i], g->ev_start[0], 0));  // the caller's frame is free to be written
     if (d_rgb)
-      GCHECK(hipMemcpyPeerAsync(d_rgb + r0 * W * 3, g->dev[0], img + r0 * W * 3, g->dev[i], rows * W * 12, g->cp[i]));
+      HIP_CHECK(hipMemcpyPeerAsync(d_rgb + r0 * W * 3, g->dev[0], img + r0 * W * 3, g->dev[i], rows * W * 12, g->cp[i]));
     if (d_argb)
-      GCHECK(hipMemcpyPeerAsync(d_argb + r0 * W, g->dev[0], a + r0 * W, g->dev[i], rows * W * 4, g->cp[i]));
-    GCHECK(hipEventRecord(g->ev_copied[b][i], g->cp[i]));
+      HIP_CHECK(hipMemcpyPeerAsync(d_argb + r0 * W, g->dev[0], a + r0 * W, g->dev[i], rows * W * 4, g->cp[i]));
+    HIP_CHECK(hipEventRecord(g->ev_copied[b][i], g->cp[i]));
   }
-  GCHECK(hipSetDevice(g->dev[0]));
-  for (size_t i = 0; i < m; ++i) GCHECK(hipStreamWaitEvent(s0, g->ev_copied[b][i], 0));
+  HIP_CHECK(hipSetDevice(g->dev[0]));
+  for (size_t i = 0; i < m; ++i) HIP_CHECK(hipStreamWaitEvent(s0, g->ev_copied[b][i], 0));
   ++g->frames;
-  for (size_t i = 0; i < g->n(); ++i) g->seq[i] = rfx_detail_state_seq(g->r[i]);
+  for (size_t i = 0; i < g->n(); ++i) g->seq[i] = g->r[i]->rng.state_seq;
   // members m..n-1 sat this pass out (a span of fewer rows than members): their streams stayed behind member 0's, so
   // the next pass hands member 0's state over again
   g->seq_ok = m == g->n();
@@ -443,28 +431,28 @@ static int group_pass(rfx_group *g, const rfx_frame *f, uint32_t y0, uint32_t y1
 
 extern "C" int rfx_group_render_frame(rfx_group *g, const rfx_frame *f, float *d_rgb, uint32_t *d_argb, void *stream)
 {
-  if (!g || !f || (!d_rgb && !d_argb)) return rfx_detail_fail(RFX_ERR_ARG, "group_render_frame: bad args");
+  if (!g || !f || (!d_rgb && !d_argb)) return fail(RFX_ERR_ARG, "group_render_frame: bad args");
   const size_t n = g->n();
   const uint32_t W = f->width, H = f->height;
   const uint64_t npx = (uint64_t)W * H;
   // ARGB8-only frames (a display that never reads the float image): only the 4-B/px plane crosses to member 0
   const bool argb_only = d_rgb == nullptr;
   if (argb_only && f->additive_counter > 1)
-    return rfx_detail_fail(RFX_ERR_ARG, "group_render_frame: an accumulating frame needs the float frame (d_rgb)");
+    return fail(RFX_ERR_ARG, "group_render_frame: an accumulating frame needs the float frame (d_rgb)");
   if (f->sample_num <= 0 || f->sample_num > 256 || (f->nranks > 1) ||
       !((f->pixel_begin == 0 && f->pixel_end == 0) || (f->pixel_begin == 0 && f->pixel_end == npx)))
-    return rfx_detail_fail(RFX_ERR_ARG, "group_render_frame: a whole frame with sample_num > 0 (no partition fields)");
-  hipStream_t s0 = stream ? (hipStream_t)stream : rfx_detail_stream(g->r[0]);
+    return fail(RFX_ERR_ARG, "group_render_frame: a whole frame with sample_num > 0 (no partition fields)");
+  hipStream_t s0 = stream ? (hipStream_t)stream : g->r[0]->stream;
   if (n == 1 || H < n)  // one member renders the frame (and splits a large one itself)
   {
     if (argb_only && npx > g->rgb0_cap)
     {
-      GCHECK(hipSetDevice(g->dev[0]));
-      GCHECK(hipDeviceSynchronize());  // any earlier frame on any stream may still write the old buffer
+      HIP_CHECK(hipSetDevice(g->dev[0]));
+      HIP_CHECK(hipDeviceSynchronize());  // any earlier frame on any stream may still write the old buffer
       (void)hipFree(g->rgb0);
       g->rgb0 = nullptr;
       g->rgb0_cap = 0;
-      GCHECK(hipMalloc(&g->rgb0, npx * 3 * sizeof(float)));
+      HIP_CHECK(hipMalloc(&g->rgb0, npx * 3 * sizeof(float)));
       g->rgb0_cap = npx;
     }
     g->seq_ok = false;
@@ -473,18 +461,19 @@ extern "C" int rfx_group_render_frame(rfx_group *g, const rfx_frame *f, float *d
   // a frame of more traces than one pass takes -- every member's band at most its launch limit, the pass under the band
   // scan's 2^31 -- runs as passes over consecutive row spans, each cut into equal bands (no balancing)
   const uint64_t spp = (uint64_t)f->sample_num * (uint64_t)f->sample_num;
-  const uint64_t cap = std::min<uint64_t>((uint64_t)n * rfx_detail_launch_traces(g->r[0]), 1ull << 31);
+  const uint64_t cap = std::min<uint64_t>((uint64_t)n * g->r[0]->launch_traces, 1ull << 31);
   if (npx * spp > cap)
   {
     const uint64_t per = cap / ((uint64_t)W * spp);  // rows per pass
-    if (!per) return rfx_detail_fail(RFX_ERR_ARG, "group_render_frame: one row exceeds 2^31 traces");
-    GCHECK(hipSetDevice(g->dev[0]));
-    const uint32_t jitter0 = rfx_detail_jitter(g->r[0]);
+    if (!per) return fail(RFX_ERR_ARG, "group_render_frame: one row exceeds 2^31 traces");
+    HIP_CHECK(hipSetDevice(g->dev[0]));
+    const uint32_t jitter0 = g->r[0]->jitter_seed;
     // the frame's start state for a rewind, saved on member 0's stream after the caller's work (the first pass hands
     // member 0's state over when it differs)
-    GCHECK(hipEventRecord(g->ev_start[0], s0));
-    GCHECK(hipStreamWaitEvent(g->own[0], g->ev_start[0], 0));
-    RCHECK(rfx_detail_save_start(g->r[0], g->own[0]));
+    HIP_CHECK(hipEventRecord(g->ev_start[0], s0));
+    HIP_CHECK(hipStreamWaitEvent(g->own[0], g->ev_start[0], 0));
+    RCHECK(rfx::set_dev(g->r[0]));
+    RCHECK(rfx::save_rewind_state(g->r[0], g->own[0]));
     for (uint64_t y = 0; y < H; y += per)
     {
       const uint32_t y0 = (uint32_t)y, y1 = (uint32_t)std::min<uint64_t>(H, y + per);
@@ -494,12 +483,12 @@ extern "C" int rfx_group_render_frame(rfx_group *g, const rfx_frame *f, float *d
       RCHECK(group_pass(g, f, y0, y1, bd, d_rgb, d_argb, s0));
     }
     g->timing_pending = false;  // the bands of a split frame are not the frame's bands
-    rfx_detail_set_rewindable_saved(g->r[0], jitter0, s0);
+    g->r[0]->rng.rewindable_saved(jitter0, s0);
     return RFX_OK;
   }
   if (W != g->W || H != g->H || g->bounds.size() != n + 1)
   {
-    if (g->fixed && H != g->H) return rfx_detail_fail(RFX_ERR_ARG, "group_render_frame: fixed bands of another height");
+    if (g->fixed && H != g->H) return fail(RFX_ERR_ARG, "group_render_frame: fixed bands of another height");
     if (!g->fixed) g->bounds = equal_bounds(H, n);
     g->W = W;
     g->H = H;

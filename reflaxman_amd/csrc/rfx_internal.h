@@ -1,18 +1,212 @@
-// Internals of librfx shared between its translation units (not part of the C-ABI).
+// Internals of librfx shared between its HIP-side translation units (rfx_host.cpp, rfx_group.cpp, rfx_kat.cpp); not
+// part of the C-ABI.  The host-only part (rfx::fail, SceneBuild) is rfx_scene.h.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include "../../include/rfx.h"
+#include <vector>
 
-int rfx_detail_fail(int code, const char *msg);
-uint32_t *rfx_detail_seed_word(rfx_renderer *r);  // device word holding the sphere stream's current state
-uint32_t rfx_detail_jitter(const rfx_renderer *r);
-void rfx_detail_set_jitter(rfx_renderer *r, uint32_t jitter);
-hipStream_t rfx_detail_stream(const rfx_renderer *r);
-void rfx_detail_set_rewindable(rfx_renderer *r, uint32_t jitter0);
-// a frame of several passes: its start state saved on `st` before the first, then rewindable to it (rfx_frame_rng_rewind)
-int rfx_detail_save_start(rfx_renderer *r, hipStream_t st);
-void rfx_detail_set_rewindable_saved(rfx_renderer *r, uint32_t jitter0, hipStream_t st);
-uint64_t rfx_detail_launch_traces(const rfx_renderer *r);
-uint64_t rfx_detail_state_seq(const rfx_renderer *r);  // moves whenever the random streams move or are set
+#include "rfx_launch.h"
+#include "rfx_scene.h"
+
+#define HIP_CHECK(expr)                                                                          \
+  do {                                                                                           \
+    hipError_t e_ = (expr);                                                                      \
+    if (e_ != hipSuccess) return rfx::fail(RFX_ERR_HIP, "%s: %s", #expr, hipGetErrorString(e_)); \
+  } while (0)
+#define RCHECK(expr)               \
+  do {                             \
+    int rc_ = (expr);              \
+    if (rc_ != RFX_OK) return rc_; \
+  } while (0)
+
+namespace rfx {
+
+// A device array the renderer owns, freed with it (on the device current at destruction: rfx_renderer_destroy sets
+// it).  Grow-only: reserve(n) keeps an array of at least n elements, else frees it and allocates n -- the contents are
+// not carried over.  Returns 1 when it allocated (the caller re-initialises what the array held), 0 when the array
+// stays, an RFX_ERR_* (< 0) when the allocation failed (the array is then empty: capacity 0).  Where several arrays grow
+// as a set behind one array's capacity, release() that array before the first of the others is touched and reserve it
+// last: its capacity is then non-zero only while the whole set is allocated and initialised.
+template <class T>
+struct DevBuf {
+  T *p = nullptr;
+  size_t cap = 0;
+  DevBuf() = default;
+  DevBuf(const DevBuf &) = delete;
+  DevBuf &operator=(const DevBuf &) = delete;
+  ~DevBuf() { release(); }
+  void release()
+  {
+    (void)hipFree(p);
+    p = nullptr;
+    cap = 0;
+  }
+  int reserve(size_t n)
+  {
+    if (n <= cap) return 0;
+    release();
+    HIP_CHECK(hipMalloc(&p, n * sizeof(T)));
+    cap = n;
+    return 1;
+  }
+  operator T *() const { return p; }
+};
+
+// The sphere stream's state (the reference's serial LCG, trace_math.h:34-39) and what follows it around.  seed[idx] is
+// the current state; a pre-pass reads it and writes the state after its frame to the other word, and moved() makes
+// that one current (no device copy between frames).  seed[2]: the start state of a frame of several launches.  pos:
+// the state's place in the LCG's cycle, (k, A) beside each of the two seed words (rfx_kernels.hip "the cycle table");
+// seq_valid: the pair beside the current word matches that word (a table emit wrote both) -- anything else that sets
+// or moves the stream clears it, and the next table emit runs rng_locate first.
+struct RngState {
+  DevBuf<uint32_t> seed, pos;
+  uint32_t idx = 0;
+  bool seq_valid = false;
+  int prepass_form = 0;  // rfx_renderer_prepass_form: the last pre-pass (0 count + emit, 1 cycle table, 2 one pass)
+  // bumped whenever the random streams move or are set (emits, set_rng, rewinds): a device group compares it with the
+  // value after its own last frame to know whether the members' streams still equal member 0's
+  uint64_t state_seq = 0;
+  // rfx_frame_rng_rewind: the last call was an rfx_render_frame; its start states (the sphere stream's is the other
+  // seed word while rewind_flip, or seed[2] on rewind_stream while rewind_saved) can be restored
+  bool rewind_ok = false, rewind_flip = false, rewind_saved = false;
+  uint32_t rewind_jitter = 0;
+  hipStream_t rewind_stream = nullptr;
+
+  uint32_t *cur() const { return seed.p + idx; }
+  uint32_t *next() const { return seed.p + (idx ^ 1u); }
+  uint32_t *cur_pos() const { return pos.p + 2 * idx; }
+  uint32_t *next_pos() const { return pos.p + 2 * (idx ^ 1u); }
+  // a pre-pass of `form` wrote next() (form 1: next_pos() too)
+  void moved(int form)
+  {
+    idx ^= 1u;
+    seq_valid = form == 1;
+    prepass_form = form;
+    ++state_seq;
+  }
+  // cur() is about to be written from outside (no pre-pass): its cycle position is unknown
+  uint32_t *cur_for_write()
+  {
+    seq_valid = false;
+    return cur();
+  }
+  // the stream was set from outside, or stepped back one pre-pass (flip: the other word becomes current again)
+  void reset(bool flip)
+  {
+    if (flip) idx ^= 1u;
+    seq_valid = false;
+    ++state_seq;
+  }
+  // the call that ends here can be undone by rfx_frame_rng_rewind: by flipping back (flip), or not at all moved
+  void rewindable(uint32_t jitter0, bool flip)
+  {
+    rewind_ok = true;
+    rewind_flip = flip;
+    rewind_saved = false;
+    rewind_jitter = jitter0;
+  }
+  // ... a frame of several launches: from seed[2] (save_rewind_state before the first), copied back on st
+  void rewindable_saved(uint32_t jitter0, hipStream_t st)
+  {
+    rewindable(jitter0, false);
+    rewind_saved = true;
+    rewind_stream = st;
+  }
+};
+
+}  // namespace rfx
+
+struct rfx_renderer {
+  rfx_renderer();  // rfx_host.cpp: the defaults its compile-time knobs set
+  int device = 0;
+  int cus = 256;  // compute units of the device (the bounce kernel's grid: one resident wave per slot)
+  hipStream_t own_stream = nullptr;
+  hipStream_t stream = nullptr;
+  // scene on device
+  rfx::DevScene dev{};
+  std::vector<void *> scene_allocs;
+  bool has_scene = false;
+  rfx::RngState rng;
+  rfx::DevBuf<int> err;  // the pre-pass kernels' error word (rfx_synchronize)
+  uint32_t jitter_seed = 0;
+  // workspaces
+  rfx::DevBuf<uint32_t> rd;      // per-trace LCG states (rng_emit)
+  rfx::DevBuf<uint32_t> rd_alt;  // emit-ahead, the odd spans of a split frame: the second randDir buffer
+  int emit_pending = -1;  // emit-ahead: buffer (0 rd, 1 rd_alt) of an emitted, untraced frame, or -1
+  int trace_buf = 0;      // buffer the last enqueued trace read
+  bool split_alt_busy = false;  // a split frame's odd spans traced from rd_alt on split_stream (done at split_ev[2])
+  uint64_t emit_key[10] = {};  // the emitted frame's plan (traces, band, geometry): rfx_render_frame_emitted must match it
+  // frames of more traces than launch_traces: consecutive spans alternate between the caller's stream and split_stream
+  // (randDirs in rd / rd_alt); split_ev[k] marks span k's emit (the next span's pre-pass starts from its state)
+  uint64_t launch_traces;
+  hipStream_t split_stream = nullptr;
+  hipEvent_t split_ev[3] = {nullptr, nullptr, nullptr};
+  // the pre-pass's per-block arrays, sized together for blk_cnt.cap blocks (rfx_host.cpp ensure_rng_workspace): the
+  // accept counts; band emits' scanned block offsets, the band's first / last / final block and the multi-workgroup
+  // scan's tile totals (one per 4096 blocks); one device's accept flags per pre-pass thread (rng_count -> rng_emit);
+  // the LCG jump table (rng_jump_table)
+  rfx::DevBuf<uint32_t> blk_cnt, rng_range, tile_sum, jump;
+  rfx::DevBuf<uint64_t> blk_off;
+  rfx::DevBuf<uint16_t> rng_masks;
+  // the one-pass pre-pass (rng_fused): per-block status words, the block ticket word (counts up across launches, never
+  // reset), the tickets taken so far, the launch's epoch tag
+  rfx::DevBuf<unsigned long long> rng_status, rng_ticket;
+  unsigned long long rng_tickets = 0;
+  uint32_t rng_epoch = 0;
+  // the cycle table, built on the first frame that takes it (seq_built): the jump header, each block's start state,
+  // the prefix of the accept counts (4 MB each) and build scratch
+  rfx::DevBuf<uint32_t> seq_hdr, seq_state, seq_p, seq_tiles;
+  bool seq_built = false;
+  int rng_prepass;  // rfx_renderer_set_rng_prepass
+  // host staging for rfx_render_frame_host
+  rfx::DevBuf<float> img;
+  rfx::DevBuf<uint32_t> argb;
+  rfx::DevBuf<uint64_t> cnt;
+  // tile schedule (rfx_renderer_set_tile_order): a recording trace launch writes per-tile clock costs; a counting
+  // sort (lpt_*) turns them into the next launch's order (longest first), on the launch's stream (or, RFX_TILE_SORT_MAIN
+  // = 0, on tile_stream while the next frame's RNG pre-pass runs); a launch on another stream waits on tile_join.
+  // tile_n: tiles of the launch the order is for.
+  int tile_mode;
+  rfx::DevBuf<uint32_t> tile_cost, tile_order, tile_scratch;
+  uint32_t tile_n = 0;
+  uint64_t tile_key = 0;
+  hipStream_t tile_stream = nullptr;
+  hipEvent_t tile_fork = nullptr, tile_join = nullptr;
+  bool tile_pending = false;         // a sort has been launched: its order is valid for (tile_n, tile_key)
+  hipStream_t tile_waited = nullptr; // the stream that already waits on the last sort (tile_join)
+  uint64_t tile_count = 0;           // scheduled launches (costs are recorded every RFX_TILE_SORT_EVERY-th)
+  int park_after = -1;  // rfx_renderer_set_regroup: -1 = default (RFX_PARK_AFTER on large scenes), 0 = off
+  // primary-bundle cull masks (small scenes, plain frames): kPrimStride u64 per wave tile, valid for prim_key
+  rfx::DevBuf<uint64_t> prim_mask;
+  // split frames in the chunk mode: each span's pixel masks, in the buffer of its stream side (render_split)
+  rfx::DevBuf<uint64_t> split_mask[2];
+  std::vector<uint8_t> prim_key;   // the view the masks hold (empty: none)
+  std::vector<uint8_t> prim_seen;  // the view of the last plain small-scene launch
+  uint64_t scene_gen = 0;  // bumped by every set_scene
+  int prim_mode = 1;       // rfx_renderer_set_prim_masks
+  int tri_accel = -1;      // rfx_renderer_set_tri_accel: -1 automatic (RFX_TRI_BVH_AUTO_MIN triangles), 0 off, 1 on,
+                           // 2 on with the narrow bundles walking the tree too
+  rfx_accel_info accel{};  // the uploaded scene's hierarchies (rfx_renderer_accel_info)
+  int bounce_form = 0;     // the last trace launch's bounce kernel: 0 none, 1 global-memory BVH, 2 LDS-staged BVH
+  // ray regrouping of large-scene plain frames (RFX_PARK_AFTER): parked traces; qctr: their count, the bounce kernel's
+  // claim counter, then the sort's kQueueBuckets histogram words; the regroup sort's per-entry bucket and bucket order
+  rfx::DevBuf<rfx::QRay> queue;
+  rfx::DevBuf<uint32_t> qctr, qkey, qorder;
+  int queue_sort;  // rfx_renderer_set_regroup_sort
+  // per-phase event timing: triples {start, after pre-pass, after trace} on every timing_every-th frame (the events'
+  // own cost stays off the other frames: ~10 us per frame for three records at C1's 640x480)
+  bool timing = false, timing_this = false;
+  uint32_t timing_every = 1;
+  uint64_t timing_seq = 0;
+  std::vector<hipEvent_t> events;
+  size_t events_used = 0;
+};
+
+namespace rfx {
+// rfx_host.cpp, for the other units
+int set_dev(rfx_renderer *r);  // hipSetDevice(r->device)
+int ensure_seq_table(rfx_renderer *r, hipStream_t st);  // the cycle table, built on first use
+// the stream state a frame of several passes starts from, saved on `st` (r's device current) before the first
+int save_rewind_state(rfx_renderer *r, hipStream_t st);
+}  // namespace rfx

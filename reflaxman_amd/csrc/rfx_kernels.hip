@@ -80,8 +80,6 @@ __global__ __launch_bounds__(kLptThreads) void lpt_scatter(const uint32_t *cost,
   for (uint32_t i = i0 + threadIdx.x; i < i1; i += kLptThreads) order[atomicAdd(&off[lpt_key(cost, i)], 1u)] = i;
 }
 
-uint32_t trace_tiles(const FrameParams &P);
-
 // bytes of scratch launch_tile_order needs
 size_t tile_order_scratch() { return (size_t)kLptGroups * kLptBuckets * sizeof(uint32_t); }
 
@@ -795,7 +793,7 @@ __global__ __launch_bounds__(kRngBlock) void rng_fused(const uint32_t *seed, con
     // The look-back outwaited its bound (only a broken invariant gets here): the offset is recomputed from the random
     // stream itself -- the accept counts of blocks 0 .. b - 1, regenerated by this workgroup -- so the frame's randDirs
     // stay exact whatever the other blocks do.  Value 4 in the error word records that it happened: the frame is exact,
-    // so it is not an error -- the host fails a call on bit 0 alone (a stream too short for the frame).
+    // so it is not an error -- rfx_renderer_get_rng and rfx_synchronize fail on bit 0 alone (a stream too short).
     uint32_t part = 0;
     for (uint32_t pb = 0; pb < b; ++pb)
     {

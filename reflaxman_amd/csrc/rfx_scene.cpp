@@ -1,0 +1,979 @@
+// The host-only part of librfx.so: the scene builder C-ABI of include/rfx.h (scene objects, textures and their TGA / BMP
+// files, camera helpers, strip arithmetic), the two hierarchy builders, and SceneBuild -- the host half of
+// rfx_renderer_set_scene.  Scene builder calls restate the reference's constructors (host precompute in strict IEEE,
+// shared rfx_math.h).  Nothing here touches HIP: the file also compiles with a plain C++ compiler (-ffp-contract=off),
+// which is how tests/native/scene_host_check.cpp runs it under the host sanitizers.
+#include <math.h>
+#include <stdarg.h>
+#include <stdio.h>
+#include <stdlib.h>
+#include <string.h>
+
+#include <algorithm>
+#include <cmath>
+#include <string>
+#include <vector>
+
+#include "rfx_math.h"
+#include "rfx_scene.h"
+
+#pragma clang fp contract(off)
+
+using namespace rfx;
+
+static thread_local std::string g_last_error;
+
+int rfx::fail(int code, const char *fmt, ...)
+{
+  char buf[512];
+  va_list ap;
+  va_start(ap, fmt);
+  vsnprintf(buf, sizeof(buf), fmt, ap);
+  va_end(ap);
+  g_last_error = buf;
+  return code;
+}
+
+extern "C" const char *rfx_last_error(void) { return g_last_error.c_str(); }
+
+// ============================================================== scene (host)
+// w x h as loaded; no texels = the reference's empty colorBuf (procedural checker).  loaded: the file was read
+// (Skybox::loadTexture then derives its half tiles from w and h, Skybox.cpp:21-37).
+struct HostTexture { uint32_t w = 0, h = 0; bool loaded = false; std::vector<uint32_t> texels; };
+struct HostMat { int dielectric; float r, g, b, refl, transp; };
+struct HostSphere { v3 center; float radius, sq_radius; HostMat mat; int obj; };
+struct HostTri {
+  v3 v0, v1, v2, norm;
+  double cond = INFINITY;  // ||M||_F ||M^-1||_F of the basis M = [v2-v0 | v1-v0 | -norm] (cull bound)
+  m33 ax, tuv;
+  float tu0 = 0, tv0 = 0;
+  int tex = -1;
+  HostMat mat;
+  int obj;
+};
+struct HostLight { v3 origin; float radius; float r, g, b, power; };
+struct HostPlane { v3 pos, norm; HostMat mat; int obj; };
+
+struct rfx_scene {
+  col diff, env;
+  float diff_power;
+  float half_tile_w, half_tile_h;
+  int skybox = -1;
+  std::vector<HostSphere> spheres;
+  std::vector<HostTri> tris;
+  std::vector<HostPlane> planes;
+  std::vector<int> obj_kind, obj_idx;  // insertion order: kind 0 sphere, 1 triangle, 2 plane
+  std::vector<HostLight> lights;
+  std::vector<HostTexture> textures;
+};
+
+static void default_half_tiles(rfx_scene *s)  // Skybox.cpp:5-9 / failed load :32-33
+{
+  s->half_tile_w = 1.0f / 8.0f - kFltEpsilon;
+  s->half_tile_h = 1.0f / 6.0f - kFltEpsilon;
+}
+
+extern "C" rfx_scene *rfx_scene_create(float dr, float dg, float db, float dp)   // Scene.cpp:10-15
+{
+  rfx_scene *s = new rfx_scene();
+  s->diff = mkc(dr, dg, db);
+  s->diff_power = dp;
+  s->env = cscale(s->diff, dp);
+  default_half_tiles(s);
+  return s;
+}
+
+extern "C" void rfx_scene_destroy(rfx_scene *s) { delete s; }
+
+static HostMat make_mat(int type, const float rgb[3], float refl, float transp)      // Material.cpp:8-14
+{
+  HostMat m;
+  m.dielectric = type == RFX_DIELECTRIC;
+  m.r = rgb[0]; m.g = rgb[1]; m.b = rgb[2];
+  m.refl = clampf(refl, 0.0f, 1.0f);
+  m.transp = clampf(transp, 0.0f, 1.0f);
+  return m;
+}
+
+extern "C" int rfx_scene_add_sphere(rfx_scene *s, const float c[3], float radius, int type, const float rgb[3],
+                                    float refl, float transp)                          // Scene.cpp:29-39
+{
+  if (!s || !c || !rgb || (type != RFX_METAL && type != RFX_DIELECTRIC)) return fail(RFX_ERR_ARG, "add_sphere: bad args");
+  if (radius <= kVerySmall) radius = kVerySmall;
+  HostSphere sp;
+  sp.center = mk(c[0], c[1], c[2]);
+  sp.radius = radius;
+  sp.sq_radius = radius * radius;                                                    // Sphere.cpp:19
+  sp.mat = make_mat(type, rgb, refl, transp);
+  sp.obj = (int)s->obj_kind.size();
+  s->obj_kind.push_back(0);
+  s->obj_idx.push_back((int)s->spheres.size());
+  s->spheres.push_back(sp);
+  return sp.obj;
+}
+
+extern "C" int rfx_scene_add_triangle(rfx_scene *s, const float a[3], const float b[3], const float c[3], int type,
+                                      const float rgb[3], float refl, float transp)    // Triangle.cpp:11-21
+{
+  if (!s || !a || !b || !c || !rgb || (type != RFX_METAL && type != RFX_DIELECTRIC))
+    return fail(RFX_ERR_ARG, "add_triangle: bad args");
+  HostTri t;
+  const v3 v0 = mk(a[0], a[1], a[2]), v1 = mk(b[0], b[1], b[2]), v2 = mk(c[0], c[1], c[2]);
+  t.v0 = v0;
+  t.mat = make_mat(type, rgb, refl, transp);
+  t.norm = normalized(cross(sub(v1, v0), sub(v2, v0)));
+  const m33 basis = from_cols(sub(v2, v0), sub(v1, v0), neg(t.norm));
+  t.ax = inverted(basis);
+  t.v1 = v1;
+  t.v2 = v2;
+  {
+    const float *a = &basis.m11, *b = &t.ax.m11;
+    double na = 0.0, nb = 0.0;
+    for (int k = 0; k < 9; ++k) { na += (double)a[k] * a[k]; nb += (double)b[k] * b[k]; }
+    const float det = basis.m11 * (basis.m22 * basis.m33 - basis.m32 * basis.m23) +
+                      basis.m21 * (basis.m32 * basis.m13 - basis.m12 * basis.m33) +
+                      basis.m31 * (basis.m12 * basis.m23 - basis.m13 * basis.m22);
+    t.cond = fabsf(det) > kVerySmall ? sqrt(na * nb) : INFINITY;
+  }
+  memset(&t.tuv, 0, sizeof(t.tuv));
+  t.obj = (int)s->obj_kind.size();
+  s->obj_kind.push_back(1);
+  s->obj_idx.push_back((int)s->tris.size());
+  s->tris.push_back(t);
+  return t.obj;
+}
+
+extern "C" int rfx_scene_add_mesh(rfx_scene *s, const float *vertices, uint32_t n_vertices, const uint32_t *indices,
+                                  uint32_t n_triangles, int type, const float rgb[3], float refl, float transp)
+{
+  if (!s || !rgb || (type != RFX_METAL && type != RFX_DIELECTRIC) || (n_triangles && (!vertices || !indices)))
+    return fail(RFX_ERR_ARG, "add_mesh: bad args");
+  for (size_t i = 0; i < 3 * (size_t)n_triangles; ++i)
+    if (indices[i] >= n_vertices)
+      return fail(RFX_ERR_ARG, "add_mesh: index %u of triangle %zu is not below %u vertices", indices[i], i / 3, n_vertices);
+  const int first = (int)s->obj_kind.size();
+  s->tris.reserve(s->tris.size() + n_triangles);
+  for (size_t i = 0; i < n_triangles; ++i)
+  {
+    const int rc = rfx_scene_add_triangle(s, vertices + 3 * (size_t)indices[3 * i], vertices + 3 * (size_t)indices[3 * i + 1],
+                                          vertices + 3 * (size_t)indices[3 * i + 2], type, rgb, refl, transp);
+    if (rc < 0) return rc;
+  }
+  return first;
+}
+
+extern "C" int rfx_scene_add_plane(rfx_scene *s, const float pos[3], const float norm[3], int type, const float rgb[3],
+                                   float refl, float transp)                         // Plane.cpp:9-14
+{
+  if (!s || !pos || !norm || !rgb || (type != RFX_METAL && type != RFX_DIELECTRIC))
+    return fail(RFX_ERR_ARG, "add_plane: bad args");
+  HostPlane p;
+  p.pos = mk(pos[0], pos[1], pos[2]);
+  p.norm = mk(norm[0], norm[1], norm[2]);
+  p.mat = make_mat(type, rgb, refl, transp);
+  p.obj = (int)s->obj_kind.size();
+  s->obj_kind.push_back(2);
+  s->obj_idx.push_back((int)s->planes.size());
+  s->planes.push_back(p);
+  return p.obj;
+}
+
+extern "C" int rfx_triangle_set_texture(rfx_scene *s, int obj, int tex, const float uv[6])  // Triangle.cpp:110-120
+{
+  if (!s || !uv || obj < 0 || obj >= (int)s->obj_kind.size() || s->obj_kind[obj] != 1)
+    return fail(RFX_ERR_ARG, "set_texture: object %d is not a triangle", obj);
+  if (tex < 0 || tex >= (int)s->textures.size()) return fail(RFX_ERR_ARG, "set_texture: bad texture %d", tex);
+  HostTri &t = s->tris[s->obj_idx[obj]];
+  t.tex = tex;
+  t.tu0 = uv[0];
+  t.tv0 = uv[1];
+  const v3 p1 = mk(uv[0], uv[1], 0), p2 = mk(uv[2], uv[3], 0), p3 = mk(uv[4], uv[5], 0);
+  t.tuv = from_cols(sub(p3, p1), sub(p2, p1), mk(0, 0, -1));
+  return RFX_OK;
+}
+
+extern "C" int rfx_scene_add_light(rfx_scene *s, const float o[3], float radius, const float rgb[3], float power)
+{                                                                                     // Scene.cpp:48-59
+  if (!s || !o || !rgb) return fail(RFX_ERR_ARG, "add_light: bad args");
+  if (radius <= kVerySmall) radius = kVerySmall;
+  const col c = mkc(rgb[0], rgb[1], rgb[2]);
+  s->env = cadd(s->env, cscale(c, power));
+  HostLight l;
+  l.origin = mk(o[0], o[1], o[2]);
+  l.radius = radius;
+  l.r = c.r; l.g = c.g; l.b = c.b;
+  l.power = clampf(power, 0.0f, 1.0f);                                                // OmniLight.cpp:13
+  s->lights.push_back(l);
+  return (int)s->lights.size() - 1;
+}
+
+extern "C" int rfx_scene_add_texture_argb(rfx_scene *s, uint32_t w, uint32_t h, const uint32_t *argb)
+{
+  if (!s) return fail(RFX_ERR_ARG, "add_texture: null scene");
+  HostTexture t;
+  if (argb && w && h)
+  {
+    t.w = w; t.h = h;
+    t.loaded = true;
+    t.texels.assign(argb, argb + (size_t)w * h);
+  }
+  s->textures.push_back(std::move(t));
+  return (int)s->textures.size() - 1;
+}
+
+// ---- TGA / BMP (Texture.cpp:34-173, image_headers.h) ----
+#pragma pack(push, 1)
+struct TgaHeader { int8_t idlen, colmptype, imagetype; int16_t cmorg, cmlen; int8_t cmbits; int16_t xoff, yoff, xsize, ysize; int8_t bpix, imagedesc; };
+struct BmpFileHeader { uint16_t bfType; uint32_t bfSize; uint16_t r1, r2; uint32_t bfOffBits; };
+struct BmpInfoHeader { uint32_t biSize; int32_t biWidth, biHeight; uint16_t biPlanes, biBitCount; uint32_t biCompression, biSizeImage; int32_t xppm, yppm; uint32_t clrUsed, clrImportant; };
+#pragma pack(pop)
+
+// Texture::loadFromTGAFile (Texture.cpp:34-108): type 2, 24/32 bpp, rows in file order (origin bit ignored).
+// As in the reference a header with a zero width or height loads successfully as an empty texture (w x h kept,
+// no texels).  Negative (int16) sizes, which the reference cannot allocate, fail.
+static bool tga_read(const char *path, uint32_t &w, uint32_t &h, std::vector<uint32_t> &out)
+{
+  w = h = 0;
+  out.clear();
+  FILE *f = fopen(path, "rb");
+  if (!f) return false;
+  TgaHeader hd;
+  bool ok = false;
+  if (fread(&hd, sizeof(hd), 1, f) == 1 && hd.imagetype == 2 && hd.xsize >= 0 && hd.ysize >= 0)
+  {
+    const uint32_t W = (uint32_t)hd.xsize, H = (uint32_t)hd.ysize;
+    const int bpp = hd.bpix;
+    const long off = (long)sizeof(hd) + hd.idlen + hd.cmlen * hd.cmbits / 8;
+    if (!fseek(f, off, SEEK_SET) && (bpp == 24 || bpp == 32))
+    {
+      const size_t n = (size_t)W * H, ps = (size_t)bpp / 8;
+      std::vector<uint8_t> raw(n * ps);
+      if (!n || fread(raw.data(), 1, raw.size(), f) == raw.size())
+      {
+        out.resize(n);
+        for (size_t i = 0; i < n; ++i)
+        {
+          const uint8_t *p = &raw[i * ps];
+          const uint32_t a = bpp == 32 ? p[3] : 0xFFu;
+          out[i] = a << 24 | (uint32_t)p[2] << 16 | (uint32_t)p[1] << 8 | p[0];
+        }
+        w = W; h = H;
+        ok = true;
+      }
+    }
+  }
+  fclose(f);
+  if (!ok) out.clear();
+  return ok;
+}
+
+static bool has_ext(const char *path, const char *ext)
+{
+  const char *dot = strrchr(path, '.');
+  return dot && !strcmp(dot, ext);
+}
+
+extern "C" int rfx_tga_load(const char *path, uint32_t *w, uint32_t *h, uint32_t *argb, size_t capacity)
+{
+  if (!path || !w || !h) return fail(RFX_ERR_ARG, "tga_load: bad args");
+  std::vector<uint32_t> px;
+  if (!tga_read(path, *w, *h, px)) return fail(RFX_ERR_IO, "tga_load: cannot read %s", path);
+  if (argb)
+  {
+    if (capacity < px.size()) return fail(RFX_ERR_ARG, "tga_load: capacity %zu < %zu", capacity, px.size());
+    memcpy(argb, px.data(), px.size() * 4);
+  }
+  return RFX_OK;
+}
+
+extern "C" int rfx_tga_save(const char *path, uint32_t w, uint32_t h, const uint32_t *argb)  // Texture.cpp:110-137
+{
+  if (!path || !argb || !w || !h) return fail(RFX_ERR_ARG, "tga_save: bad args");
+  FILE *f = fopen(path, "wb");
+  if (!f) return fail(RFX_ERR_IO, "tga_save: cannot open %s", path);
+  TgaHeader hd;
+  memset(&hd, 0, sizeof(hd));
+  hd.imagetype = 2; hd.xsize = (int16_t)w; hd.ysize = (int16_t)h; hd.bpix = 32;
+  bool ok = fwrite(&hd, sizeof(hd), 1, f) == 1 && fwrite(argb, (size_t)w * h * 4, 1, f) == 1;
+  fclose(f);
+  return ok ? RFX_OK : fail(RFX_ERR_IO, "tga_save: short write");
+}
+
+extern "C" int rfx_bmp_save(const char *path, uint32_t w, uint32_t h, const uint32_t *argb)  // Texture.cpp:139-173
+{
+  if (!path || !argb || !w || !h) return fail(RFX_ERR_ARG, "bmp_save: bad args");
+  FILE *f = fopen(path, "wb");
+  if (!f) return fail(RFX_ERR_IO, "bmp_save: cannot open %s", path);
+  BmpFileHeader fh;
+  BmpInfoHeader ih;
+  memset(&fh, 0, sizeof(fh));
+  memset(&ih, 0, sizeof(ih));
+  fh.bfType = ((uint16_t)'M' << 8) | (uint16_t)'B';
+  fh.bfSize = (uint32_t)(sizeof(fh) + sizeof(ih) + (size_t)w * h * 4);
+  fh.bfOffBits = sizeof(fh) + sizeof(ih);
+  ih.biSize = sizeof(ih); ih.biWidth = (int32_t)w; ih.biHeight = (int32_t)h; ih.biPlanes = 1; ih.biBitCount = 32;
+  bool ok = fwrite(&fh, sizeof(fh), 1, f) == 1 && fwrite(&ih, sizeof(ih), 1, f) == 1 &&
+            fwrite(argb, (size_t)w * h * 4, 1, f) == 1;
+  fclose(f);
+  return ok ? RFX_OK : fail(RFX_ERR_IO, "bmp_save: short write");
+}
+
+extern "C" int rfx_scene_add_texture_file(rfx_scene *s, const char *path, int *loaded)  // Scene.cpp:61-66
+{
+  if (!s || !path) return fail(RFX_ERR_ARG, "add_texture_file: bad args");
+  HostTexture t;
+  const bool ok = has_ext(path, ".tga") && tga_read(path, t.w, t.h, t.texels);     // Texture.cpp:175-189
+  t.loaded = ok;
+  if (loaded) *loaded = ok ? 1 : 0;
+  s->textures.push_back(std::move(t));
+  return (int)s->textures.size() - 1;
+}
+
+static void set_skybox_index(rfx_scene *s, int idx)                                   // Skybox.cpp:21-37
+{
+  s->skybox = idx;
+  const HostTexture &t = s->textures[idx];
+  if (t.loaded)
+  {
+    s->half_tile_w = 1.0f / 8.0f - 1.0f / (float)t.w - kFltEpsilon;
+    s->half_tile_h = 1.0f / 6.0f - 1.0f / (float)t.h - kFltEpsilon;
+  }
+  else
+    default_half_tiles(s);
+}
+
+extern "C" int rfx_scene_set_skybox_file(rfx_scene *s, const char *path)
+{
+  if (!s || !path) return fail(RFX_ERR_ARG, "set_skybox_file: bad args");
+  int loaded = 0;
+  const int idx = rfx_scene_add_texture_file(s, path, &loaded);
+  set_skybox_index(s, idx);
+  return loaded;
+}
+
+extern "C" int rfx_scene_set_skybox_argb(rfx_scene *s, uint32_t w, uint32_t h, const uint32_t *argb)
+{
+  if (!s) return fail(RFX_ERR_ARG, "set_skybox_argb: null scene");
+  const int idx = rfx_scene_add_texture_argb(s, w, h, argb);
+  set_skybox_index(s, idx);
+  return s->textures[idx].loaded ? 1 : 0;
+}
+
+extern "C" int rfx_scene_plane_count(const rfx_scene *s)
+{
+  if (!s) return fail(RFX_ERR_ARG, "plane_count: null scene");
+  return (int)s->planes.size();
+}
+
+extern "C" int rfx_scene_counts(const rfx_scene *s, int *ns, int *nt, int *nl, int *nx)
+{
+  if (!s) return fail(RFX_ERR_ARG, "counts: null scene");
+  if (ns) *ns = (int)s->spheres.size();
+  if (nt) *nt = (int)s->tris.size();
+  if (nl) *nl = (int)s->lights.size();
+  if (nx) *nx = (int)s->textures.size();
+  return RFX_OK;
+}
+
+// ============================================================== camera / images
+extern "C" void rfx_camera_view(const float e[3], const float a[3], float view[9])    // Camera.cpp:24-38
+{
+  const v3 eye = mk(e[0], e[1], e[2]), at = mk(a[0], a[1], a[2]);
+  const v3 up = mk(0.0f, 1.0f, 0.0f);
+  const v3 oz = normalized(sub(at, eye));
+  const v3 ox = normalized(cross(up, oz));
+  const v3 oy = normalized(cross(oz, ox));
+  const m33 m = from_cols(ox, oy, oz);
+  memcpy(view, &m, sizeof(m));
+}
+
+extern "C" float rfx_camera_rz(uint32_t width, float fov)                             // Render.cpp:148
+{
+  return (float)width / 2.0f / tanf(fov / 2.0f);
+}
+
+extern "C" void rfx_argb_from_rgb(const float *rgb, size_t n, uint32_t *out)
+{
+  for (size_t i = 0; i < n; ++i) out[i] = argb(mkc(rgb[i * 3], rgb[i * 3 + 1], rgb[i * 3 + 2]));
+}
+
+extern "C" uint32_t rfx_strip_rows(uint32_t H, uint32_t rb, uint32_t rank, uint32_t nranks)
+{
+  if (nranks <= 1) return H;
+  if (!rb || rank >= nranks) return 0;
+  const uint32_t full = H / rb, rem = H % rb;
+  uint32_t rows = (full / nranks) * rb;
+  const uint32_t extra = full % nranks;
+  if (rank < extra) rows += rb;
+  if (rem && full % nranks == rank) rows += rem;
+  return rows;
+}
+
+extern "C" uint32_t rfx_strip_row_to_y(uint32_t r, uint32_t rb, uint32_t rank, uint32_t nranks)
+{
+  if (nranks <= 1) return r;
+  return (r / rb * nranks + rank) * rb + r % rb;
+}
+
+// ============================================================== hierarchies
+#ifndef RFX_TRI_BVH_AUTO_MIN
+// rfx_renderer_set_tri_accel(-1): the triangle count from which a non-small scene gets the triangle BVH (DESIGN.md
+// "Triangle BVH": the smallest measured soup size at which the tree wins)
+#define RFX_TRI_BVH_AUTO_MIN 128
+#endif
+#ifndef RFX_TRI_BVH_NARROW_MIN
+// the triangle count from which narrow bundles (a tile's primary rays) walk the triangle BVH too instead of culling
+// every triangle's bound for the wave: never by default -- the bundle cull won on every soup from 64 to 100,000
+// triangles (0.8% to 15% less trace time) and lost 1% on a 2,560-triangle height field (DESIGN.md "Triangle BVH")
+#define RFX_TRI_BVH_NARROW_MIN (1 << 30)
+#endif
+// Device order of a large scene's spheres: recursive median splits of the centres along their longest axis,
+// left parts of even size, so pairs (2j, 2j + 1) are neighbours and every aligned run of 2^k spheres is a
+// compact cluster (the 64-sphere chunks of the bundle cull, the leaves of the pair BVH).
+static void spatial_order(std::vector<uint32_t> &idx, size_t a, size_t b, const std::vector<HostSphere> &sp)
+{
+  if (b - a <= 2) return;
+  double lo[3] = {INFINITY, INFINITY, INFINITY}, hi[3] = {-INFINITY, -INFINITY, -INFINITY};
+  for (size_t i = a; i < b; ++i)
+  {
+    const double c[3] = {sp[idx[i]].center.x, sp[idx[i]].center.y, sp[idx[i]].center.z};
+    for (int k = 0; k < 3; ++k) { lo[k] = fmin(lo[k], c[k]); hi[k] = fmax(hi[k], c[k]); }
+  }
+  int axis = 0;
+  for (int k = 1; k < 3; ++k)
+    if (hi[k] - lo[k] > hi[axis] - lo[axis]) axis = k;
+  const size_t mid = a + 2 * ((b - a + 2) / 4);
+  auto key = [&](uint32_t i) { return axis == 0 ? sp[i].center.x : axis == 1 ? sp[i].center.y : sp[i].center.z; };
+  std::nth_element(idx.begin() + a, idx.begin() + mid, idx.begin() + b,
+                   [&](uint32_t x, uint32_t y) { return key(x) < key(y) || (key(x) == key(y) && x < y); });
+  spatial_order(idx, a, mid, sp);
+  spatial_order(idx, mid, b, sp);
+}
+
+// Pair BVH of a large scene: leaves are the device sphere pairs (2j, 2j + 1, neighbours); internal nodes
+// split their pairs where the surface-area heuristic is lowest (every position of the pair centres sorted
+// along each axis), as long as the split keeps the tree within the kernel's stack depth, else at the
+// median of the pair centres along the longest axis (SAH against median splits alone: C5 -0.8%, round 2).  Each
+// node stores its two
+// children's boxes (spheres grown by their radii); the kernel widens them by its exact-cull margin per ray.
+// Returns the node index (or ~pair for a leaf) of range [a, b) of `pairs`; depth: internal levels below.
+namespace {
+struct PairBox { double lo[3], hi[3], c[3]; };
+
+int build_pair_bvh(std::vector<BvhNode> &nodes, std::vector<uint32_t> &pairs, size_t a, size_t b,
+                   const std::vector<PairBox> &box, const double *ref, int level, int &depth, bool widen = true)
+{
+  if (b - a == 1) return ~(int)pairs[a];
+  depth = std::max(depth, level + 1);
+  const int id = (int)nodes.size();
+  nodes.push_back(BvhNode{});
+  double lo[3] = {INFINITY, INFINITY, INFINITY}, hi[3] = {-INFINITY, -INFINITY, -INFINITY};
+  for (size_t i = a; i < b; ++i)
+    for (int k = 0; k < 3; ++k) { lo[k] = fmin(lo[k], box[pairs[i]].c[k]); hi[k] = fmax(hi[k], box[pairs[i]].c[k]); }
+  int axis = 0;
+  for (int k = 1; k < 3; ++k)
+    if (hi[k] - lo[k] > hi[axis] - lo[axis]) axis = k;
+  size_t mid = a + (b - a) / 2;
+  // surface-area heuristic over sorted pair centres (all three axes, every split position), while the depth
+  // budget allows an unbalanced split: the subtree of n leaves must still fit kBvhStack levels
+  const size_t cnt = b - a;
+  int need = 0;
+  while (((size_t)1 << need) < cnt) ++need;
+  if (level + need + 2 <= kBvhStack && cnt > 2)
+  {
+    double best = INFINITY;
+    int best_axis = axis;
+    size_t best_mid = mid;
+    std::vector<uint32_t> tmp(pairs.begin() + a, pairs.begin() + b);
+    std::vector<double> right(cnt + 1);
+    auto area = [](const double *l, const double *h) {
+      const double dx = h[0] - l[0], dy = h[1] - l[1], dz = h[2] - l[2];
+      return dx * dy + dy * dz + dz * dx;
+    };
+    for (int ax = 0; ax < 3; ++ax)
+    {
+      std::sort(tmp.begin(), tmp.end(), [&](uint32_t x, uint32_t y) {
+        return box[x].c[ax] < box[y].c[ax] || (box[x].c[ax] == box[y].c[ax] && x < y);
+      });
+      double l[3] = {INFINITY, INFINITY, INFINITY}, h[3] = {-INFINITY, -INFINITY, -INFINITY};
+      for (size_t i = cnt; i-- > 0;)
+      {
+        for (int k = 0; k < 3; ++k) { l[k] = fmin(l[k], box[tmp[i]].lo[k]); h[k] = fmax(h[k], box[tmp[i]].hi[k]); }
+        right[i] = area(l, h) * (double)(cnt - i);
+      }
+      for (int k = 0; k < 3; ++k) { l[k] = INFINITY; h[k] = -INFINITY; }
+      // a split leaving at most 2^(budget - 1) leaves on each side keeps the depth bound
+      const size_t cap = (size_t)1 << std::min(30, kBvhStack - level - 2);
+      for (size_t i = 1; i < cnt; ++i)
+      {
+        for (int k = 0; k < 3; ++k) { l[k] = fmin(l[k], box[tmp[i - 1]].lo[k]); h[k] = fmax(h[k], box[tmp[i - 1]].hi[k]); }
+        if (i > cap || cnt - i > cap) continue;
+        const double cost = area(l, h) * (double)i + right[i];
+        if (cost < best) { best = cost; best_axis = ax; best_mid = a + i; }
+      }
+    }
+    axis = best_axis;
+    mid = best_mid;
+  }
+  std::nth_element(pairs.begin() + a, pairs.begin() + mid, pairs.begin() + b, [&](uint32_t x, uint32_t y) {
+    return box[x].c[axis] < box[y].c[axis] || (box[x].c[axis] == box[y].c[axis] && x < y);
+  });
+  const int kids[2] = {build_pair_bvh(nodes, pairs, a, mid, box, ref, level + 1, depth, widen),
+                       build_pair_bvh(nodes, pairs, mid, b, box, ref, level + 1, depth, widen)};
+  const size_t range[2][2] = {{a, mid}, {mid, b}};
+  BvhNode &n = nodes[id];
+  for (int c = 0; c < 2; ++c)
+  {
+    double l[3] = {INFINITY, INFINITY, INFINITY}, h[3] = {-INFINITY, -INFINITY, -INFINITY};
+    for (size_t i = range[c][0]; i < range[c][1]; ++i)
+      for (int k = 0; k < 3; ++k) { l[k] = fmin(l[k], box[pairs[i]].lo[k]); h[k] = fmax(h[k], box[pairs[i]].hi[k]); }
+#if RFX_BVH_PREWIDE
+    if (widen)  // (false: rfx_scene_tri_bvh_dump, the boxes as built)
+    {
+      // the box grown by the node part of the kernel's margin, kCullRel mt[c] (rfx_trace.h kCullRel = 2e-3), from the
+      // float mt the kernel would have used, with a relative 1e-6 on top
+      double cd = 0.0, hd = 0.0;
+      for (int k = 0; k < 3; ++k)
+      {
+        const double dc = ref[k] - 0.5 * (l[k] + h[k]), dh = 0.5 * (h[k] - l[k]);
+        cd += dc * dc;
+        hd += dh * dh;
+      }
+      const double w = 2e-3 * (double)nextafterf((float)((sqrt(cd) + sqrt(hd)) * 1.0001), INFINITY) * (1.0 + 1e-6);
+      for (int k = 0; k < 3; ++k) { l[k] -= w; h[k] += w; }
+    }
+#endif
+    // round outwards to float
+    n.lx[c] = nextafterf((float)l[0], -INFINITY); n.ly[c] = nextafterf((float)l[1], -INFINITY);
+    n.lz[c] = nextafterf((float)l[2], -INFINITY);
+    n.hx[c] = nextafterf((float)h[0], INFINITY); n.hy[c] = nextafterf((float)h[1], INFINITY);
+    n.hz[c] = nextafterf((float)h[2], INFINITY);
+    n.child[c] = kids[c];
+    // margin term of the child against the reference point ref (the root box centre), rounded up
+    double mt = 0.0;
+    {
+      // Euclidean: |ref - centre|_2 + the half-diagonal (round 3; the L1 form made C5 2.2% slower)
+      double cd = 0.0, hd = 0.0;
+      for (int k = 0; k < 3; ++k)
+      {
+        const double dc = ref[k] - 0.5 * (l[k] + h[k]), dh = 0.5 * (h[k] - l[k]);
+        cd += dc * dc;
+        hd += dh * dh;
+      }
+      mt = sqrt(cd) + sqrt(hd);
+    }
+    n.mt[c] = nextafterf((float)(mt * 1.0001), INFINITY);
+  }
+  return id;
+}
+
+// the spatial order of build_tri_tree (below)
+void tri_spatial_order(std::vector<int32_t> &idx, size_t a, size_t b, const std::vector<double> &cen)
+{
+  if (b - a <= RFX_TRI_BVH_LEAF) return;
+  double lo[3] = {INFINITY, INFINITY, INFINITY}, hi[3] = {-INFINITY, -INFINITY, -INFINITY};
+  for (size_t i = a; i < b; ++i)
+    for (int k = 0; k < 3; ++k) { lo[k] = fmin(lo[k], cen[3 * idx[i] + k]); hi[k] = fmax(hi[k], cen[3 * idx[i] + k]); }
+  int axis = 0;
+  for (int k = 1; k < 3; ++k)
+    if (hi[k] - lo[k] > hi[axis] - lo[axis]) axis = k;
+  const size_t groups = (b - a + RFX_TRI_BVH_LEAF - 1) / RFX_TRI_BVH_LEAF;
+  const size_t mid = a + RFX_TRI_BVH_LEAF * (groups / 2);
+  std::nth_element(idx.begin() + a, idx.begin() + mid, idx.begin() + b, [&](int32_t x, int32_t y) {
+    return cen[3 * x + axis] < cen[3 * y + axis] || (cen[3 * x + axis] == cen[3 * y + axis] && x < y);
+  });
+  tri_spatial_order(idx, a, mid, cen);
+  tri_spatial_order(idx, mid, b, cen);
+}
+
+// Triangle BVH of a non-small scene (rfx_types.h RFX_TRI_BVH).  The triangles with a well-conditioned basis
+// (cond < 300: their reported hits lie within the cull margin of their vertices, see the bounds in
+// SceneBuild below) are put in spatial order -- recursive median splits of the centroids along their longest
+// axis, left parts a multiple of the leaf size -- so every aligned run of RFX_TRI_BVH_LEAF is a compact leaf; the
+// leaves' vertex boxes then take the pair builder above (SAH within its depth budget).  Every other triangle
+// (cond >= 300, a singular basis) goes to the residual list.  The scene's arrays are not reordered: order[] lists
+// insertion indices, leaf g = order[RFX_TRI_BVH_LEAF g ..], -1 padding the last leaf (TriTree, rfx_scene.h).
+// false: no tree (fewer than two leaves, deeper than the kernel's stack, or more nodes / leaves than an int16 stack
+// slot holds) -- the kernels keep their 64-triangle chunk loops
+bool build_tri_tree(const std::vector<HostTri> &tris, const double *ref, bool widen, TriTree &T)
+{
+  T = TriTree{};
+  std::vector<int32_t> idx;
+  for (size_t i = 0; i < tris.size(); ++i)
+    (tris[i].cond < 300.0 ? idx : T.resid).push_back((int32_t)i);
+  const size_t nleaf = (idx.size() + RFX_TRI_BVH_LEAF - 1) / RFX_TRI_BVH_LEAF;
+  if (nleaf < 2 || nleaf > 32768) { T.resid.clear(); return false; }
+  std::vector<double> cen(3 * tris.size(), 0.0);
+  for (int32_t i : idx)
+  {
+    const HostTri &t = tris[i];
+    cen[3 * i] = ((double)t.v0.x + t.v1.x + t.v2.x) / 3.0;
+    cen[3 * i + 1] = ((double)t.v0.y + t.v1.y + t.v2.y) / 3.0;
+    cen[3 * i + 2] = ((double)t.v0.z + t.v1.z + t.v2.z) / 3.0;
+  }
+  tri_spatial_order(idx, 0, idx.size(), cen);
+  T.order.assign(nleaf * RFX_TRI_BVH_LEAF, -1);
+  std::copy(idx.begin(), idx.end(), T.order.begin());
+  std::vector<PairBox> box(nleaf);
+  for (size_t g = 0; g < nleaf; ++g)
+  {
+    PairBox &b = box[g];
+    for (int k = 0; k < 3; ++k) { b.lo[k] = INFINITY; b.hi[k] = -INFINITY; }
+    for (int e = 0; e < RFX_TRI_BVH_LEAF; ++e)
+    {
+      const int32_t i = T.order[RFX_TRI_BVH_LEAF * g + e];
+      if (i < 0) continue;
+      for (const v3 &q : {tris[i].v0, tris[i].v1, tris[i].v2})
+      {
+        const double c[3] = {q.x, q.y, q.z};
+        for (int k = 0; k < 3; ++k) { b.lo[k] = fmin(b.lo[k], c[k]); b.hi[k] = fmax(b.hi[k], c[k]); }
+      }
+    }
+    for (int k = 0; k < 3; ++k) b.c[k] = 0.5 * (b.lo[k] + b.hi[k]);
+  }
+  std::vector<uint32_t> leaves(nleaf);
+  for (size_t g = 0; g < nleaf; ++g) leaves[g] = (uint32_t)g;
+  build_pair_bvh(T.nodes, leaves, 0, nleaf, box, ref, 0, T.depth, widen);
+  if (T.depth > kBvhStack || T.nodes.size() > 32767) { T = TriTree{}; return false; }
+  return true;
+}
+}  // namespace
+
+// the margin reference point both trees measure from: the sphere BVH's root box centre, or -- no sphere BVH (at most
+// 32 spheres) -- the centre of the triangles' vertex box
+static void tri_ref_point(const std::vector<HostTri> &tris, double *ref)
+{
+  double lo[3] = {INFINITY, INFINITY, INFINITY}, hi[3] = {-INFINITY, -INFINITY, -INFINITY};
+  for (const HostTri &t : tris)
+  {
+    if (!(t.cond < 300.0)) continue;
+    for (const v3 &q : {t.v0, t.v1, t.v2})
+    {
+      const double c[3] = {q.x, q.y, q.z};
+      for (int k = 0; k < 3; ++k) { lo[k] = fmin(lo[k], c[k]); hi[k] = fmax(hi[k], c[k]); }
+    }
+  }
+  for (int k = 0; k < 3; ++k) ref[k] = lo[k] <= hi[k] ? (double)(float)(0.5 * (lo[k] + hi[k])) : 0.0;
+}
+
+extern "C" int rfx_scene_tri_bvh_dump(const rfx_scene *s, int32_t counts[5], float *boxes, int32_t *children,
+                                      int32_t *leaf_ids, int32_t *residual)
+{
+  if (!s || !counts) return fail(RFX_ERR_ARG, "tri_bvh_dump: bad args");
+  for (int k = 0; k < 5; ++k) counts[k] = 0;
+  counts[3] = RFX_TRI_BVH_LEAF;
+  if (s->spheres.size() <= 32 && s->tris.size() <= 32) return 0;  // a small scene: no tree
+  TriTree T;
+  double ref[3];
+  tri_ref_point(s->tris, ref);
+  if (!build_tri_tree(s->tris, ref, false, T)) return 0;
+  counts[0] = (int32_t)T.nodes.size();
+  counts[1] = (int32_t)T.leaves();
+  counts[2] = (int32_t)T.resid.size();
+  counts[4] = T.depth;
+  for (size_t i = 0; i < T.nodes.size(); ++i)
+  {
+    const BvhNode &n = T.nodes[i];
+    if (boxes)
+      for (int c = 0; c < 2; ++c)
+      {
+        float *b = boxes + 12 * i + 6 * c;
+        b[0] = n.lx[c]; b[1] = n.ly[c]; b[2] = n.lz[c]; b[3] = n.hx[c]; b[4] = n.hy[c]; b[5] = n.hz[c];
+      }
+    if (children) { children[2 * i] = n.child[0]; children[2 * i + 1] = n.child[1]; }
+  }
+  if (leaf_ids) std::copy(T.order.begin(), T.order.end(), leaf_ids);
+  if (residual) std::copy(T.resid.begin(), T.resid.end(), residual);
+  return 1;
+}
+
+// ============================================================== the device form of a scene
+SceneBuild::SceneBuild(const rfx_scene &scene, int tri_accel)
+{
+  const rfx_scene *s = &scene;
+  // Large scenes (more than 32 spheres): spheres in spatial order (spatial_order: recursive median splits),
+  // so each 64-sphere chunk of the device arrays is compact and its bounding sphere can cull it as a whole,
+  // and each pair is a BVH leaf.  Every record keeps its object index (sph_info),
+  // and the large-scene kernel path compares (distance, object index), so the order changes no result.
+  const size_t nsph = s->spheres.size();
+  std::vector<uint32_t> order(nsph);
+  for (size_t i = 0; i < nsph; ++i) order[i] = (uint32_t)i;
+  if (nsph > 32) spatial_order(order, 0, nsph, s->spheres);
+
+  for (uint32_t oi : order)
+  {
+    const HostSphere &hs = s->spheres[oi];
+    sg.push_back({hs.center.x, hs.center.y, hs.center.z, hs.sq_radius});
+    sm.push_back({hs.mat.r, hs.mat.g, hs.mat.b, hs.mat.refl});
+    si.push_back(hs.obj);
+    si.push_back(hs.mat.dielectric);
+  }
+  // (large scenes: a whole number of BVH leaves of RFX_BVH_LEAF_PAIRS pairs; the padding pairs never hit)
+  const size_t npair_dev = sg.size() > 32 ? ((sg.size() + 1) / 2 + RFX_BVH_LEAF_PAIRS - 1) / RFX_BVH_LEAF_PAIRS *
+                                                RFX_BVH_LEAF_PAIRS
+                                          : (sg.size() + 1) / 2;
+  sp.assign(npair_dev, SpherePair{});
+  for (size_t i = 0; i < 2 * sp.size(); ++i)
+  {
+    SpherePair &p = sp[i / 2];
+    const int l = (int)(i & 1);
+    const bool real = i < sg.size();
+    p.cx[l] = real ? sg[i].cx : 0.0f;
+    p.cy[l] = real ? sg[i].cy : 0.0f;
+    p.cz[l] = real ? sg[i].cz : 0.0f;
+    p.r2[l] = real ? sg[i].sq_radius : -INFINITY;
+  }
+  for (const HostTri &t : s->tris)
+  {
+    TriGeo g{};
+    g.v0x = t.v0.x; g.v0y = t.v0.y; g.v0z = t.v0.z;
+    g.a11 = t.ax.m11; g.a12 = t.ax.m12; g.a13 = t.ax.m13;
+    g.a21 = t.ax.m21; g.a22 = t.ax.m22; g.a23 = t.ax.m23;
+    g.a31 = t.ax.m31; g.a32 = t.ax.m32; g.a33 = t.ax.m33;
+    tg.push_back(g);
+    TriShade h{};
+    h.nx = t.norm.x; h.ny = t.norm.y; h.nz = t.norm.z;
+    h.tu0 = t.tu0; h.tv0 = t.tv0;
+    h.t11 = t.tuv.m11; h.t12 = t.tuv.m12; h.t21 = t.tuv.m21; h.t22 = t.tuv.m22;
+    h.tex = t.tex; h.dielectric = t.mat.dielectric; h.obj = t.obj;
+    ts.push_back(h);
+    tm.push_back({t.mat.r, t.mat.g, t.mat.b, t.mat.refl});
+  }
+  // bounding spheres for the wave-bundle cull: a sphere's own (radius grown by a relative 1e-5), a
+  // triangle's centroid and farthest vertex; a triangle whose axTrans is ill-conditioned (the reference
+  // falls back to the identity for a singular basis, Matrix33.cpp:58-79) may report hits far from its
+  // vertices, so it gets r = +inf and is never culled
+  for (uint32_t oi : order)
+  {
+    const HostSphere &hs = s->spheres[oi];
+    bd.push_back({hs.center.x, hs.center.y, hs.center.z, hs.radius * 1.00001f});
+  }
+  // chunk bounds: 64 consecutive spheres of the device order, centred on their mean centre
+  for (size_t first = 0; first < nsph; first += 64)
+  {
+    const size_t last = std::min(nsph, first + 64);
+    double m[3] = {0.0, 0.0, 0.0};
+    for (size_t i = first; i < last; ++i) { m[0] += bd[i].x; m[1] += bd[i].y; m[2] += bd[i].z; }
+    for (double &v : m) v /= (double)(last - first);
+    double r = 0.0;
+    for (size_t i = first; i < last; ++i)
+    {
+      const double dx = bd[i].x - m[0], dy = bd[i].y - m[1], dz = bd[i].z - m[2];
+      r = fmax(r, sqrt(dx * dx + dy * dy + dz * dz) + (double)bd[i].r);
+    }
+    cb.push_back({(float)m[0], (float)m[1], (float)m[2], (float)(r * 1.0001 + 1e-6)});
+  }
+  for (const HostTri &t : s->tris)
+  {
+    const double cx = ((double)t.v0.x + t.v1.x + t.v2.x) / 3.0, cy = ((double)t.v0.y + t.v1.y + t.v2.y) / 3.0,
+                 cz = ((double)t.v0.z + t.v1.z + t.v2.z) / 3.0;
+    double r2 = 0.0;
+    for (const v3 &q : {t.v0, t.v1, t.v2})
+      r2 = fmax(r2, (q.x - cx) * (q.x - cx) + (q.y - cy) * (q.y - cy) + (q.z - cz) * (q.z - cz));
+    float r = (float)(sqrt(r2) * 1.0001 + 1e-6);
+    if (!(t.cond < 300.0)) r = INFINITY;
+    bd.push_back({(float)cx, (float)cy, (float)cz, r});
+  }
+  // small-scene lane table (rfx_types.h CullRec)
+  uint64_t cull_valid = 0;
+  const bool small = s->spheres.size() <= 32 && s->tris.size() <= 32;
+  if (small)
+  {
+    cs.assign(64, CullRec{});
+    ct.assign(32, CullTri{});
+    for (size_t i = 0; i < s->spheres.size(); ++i)
+    {
+      const int lane = (int)(i & 1u) * 16 + (int)(i >> 1);
+      const Bound &b = bd[i];
+      CullRec c{};
+      c.x = b.x; c.y = b.y; c.z = b.z; c.r = b.r;
+      cs[lane] = c;
+      cull_valid |= 1ull << lane;
+    }
+    for (size_t i = 0; i < s->tris.size(); ++i)
+    {
+      const HostTri &t = s->tris[i];
+      const Bound &b = bd[s->spheres.size() + i];
+      CullRec c{};
+      c.x = b.x; c.y = b.y; c.z = b.z; c.r = b.r;
+      if (t.cond < 300.0)
+      {
+        // plane of the triangle in double: unit normal of (v1 - v0) x (v2 - v0), offset n . v0
+        const double ax = (double)t.v1.x - t.v0.x, ay = (double)t.v1.y - t.v0.y, az = (double)t.v1.z - t.v0.z;
+        const double bx = (double)t.v2.x - t.v0.x, by = (double)t.v2.y - t.v0.y, bz = (double)t.v2.z - t.v0.z;
+        double nx = ay * bz - az * by, ny = az * bx - ax * bz, nz = ax * by - ay * bx;
+        const double nl = sqrt(nx * nx + ny * ny + nz * nz);
+        if (nl > 0.0)
+        {
+          nx /= nl; ny /= nl; nz /= nl;
+          c.nx = (float)nx; c.ny = (float)ny; c.nz = (float)nz;
+          c.d = (float)(nx * t.v0.x + ny * t.v0.y + nz * t.v0.z);
+        }
+      }
+      cs[32 + i] = c;
+      cull_valid |= 1ull << (32 + i);
+      // footprint record (primary-bundle masks): the dual rows of the basis (A, B, C) = (v2 - v0, v1 - v0, n) in
+      // double (the float inverse the reference computes differs by a relative ~cond eps, inside the test's
+      // margins); only for well-conditioned triangles (cond < 100)
+      CullTri q{};
+      q.v0x = t.v0.x; q.v0y = t.v0.y; q.v0z = t.v0.z;
+      q.nu = q.nv = q.nuv = INFINITY;
+      if (t.cond < 100.0 && c.nx * c.nx + c.ny * c.ny + c.nz * c.nz > 0.5f)
+      {
+        const double A[3] = {(double)t.v2.x - t.v0.x, (double)t.v2.y - t.v0.y, (double)t.v2.z - t.v0.z};
+        const double Bv[3] = {(double)t.v1.x - t.v0.x, (double)t.v1.y - t.v0.y, (double)t.v1.z - t.v0.z};
+        const double Cv[3] = {c.nx, c.ny, c.nz};
+        auto cross = [](const double *a, const double *b, double *o) {
+          o[0] = a[1] * b[2] - a[2] * b[1]; o[1] = a[2] * b[0] - a[0] * b[2]; o[2] = a[0] * b[1] - a[1] * b[0];
+        };
+        double bc[3], ca[3];
+        cross(Bv, Cv, bc);
+        cross(Cv, A, ca);
+        const double det = A[0] * bc[0] + A[1] * bc[1] + A[2] * bc[2];
+        if (fabs(det) > 0.0)
+        {
+          const double gu[3] = {bc[0] / det, bc[1] / det, bc[2] / det}, gv[3] = {ca[0] / det, ca[1] / det, ca[2] / det};
+          q.gux = (float)gu[0]; q.guy = (float)gu[1]; q.guz = (float)gu[2];
+          q.gvx = (float)gv[0]; q.gvy = (float)gv[1]; q.gvz = (float)gv[2];
+          q.nu = (float)(sqrt(gu[0] * gu[0] + gu[1] * gu[1] + gu[2] * gu[2]) * 1.001);
+          q.nv = (float)(sqrt(gv[0] * gv[0] + gv[1] * gv[1] + gv[2] * gv[2]) * 1.001);
+          const double s0 = gu[0] + gv[0], s1 = gu[1] + gv[1], s2 = gu[2] + gv[2];
+          q.nuv = (float)(sqrt(s0 * s0 + s1 * s1 + s2 * s2) * 1.001);
+        }
+      }
+      ct[i] = q;
+    }
+  }
+  // pair BVH (large scenes; spheres of a pair whose second slot is padding: r2 = -inf, never hit)
+  int bvh_depth = 0;
+  double bvh_ref[3] = {0.0, 0.0, 0.0};
+  if (nsph > 32)
+  {
+    // leaves: groups of RFX_BVH_LEAF_PAIRS consecutive pairs (compact clusters of the median-split order)
+    const size_t npairs = ((nsph + 1) / 2 + RFX_BVH_LEAF_PAIRS - 1) / RFX_BVH_LEAF_PAIRS;
+    constexpr size_t kLeafSph = 2 * RFX_BVH_LEAF_PAIRS;
+    std::vector<PairBox> box(npairs);
+    for (size_t j = 0; j < npairs; ++j)
+    {
+      PairBox &b = box[j];
+      for (int k = 0; k < 3; ++k) { b.lo[k] = INFINITY; b.hi[k] = -INFINITY; }
+      for (size_t q = kLeafSph * j; q < std::min(nsph, kLeafSph * j + kLeafSph); ++q)
+      {
+        const double c[3] = {bd[q].x, bd[q].y, bd[q].z}, rr = bd[q].r;
+        for (int k = 0; k < 3; ++k) { b.lo[k] = fmin(b.lo[k], c[k] - rr); b.hi[k] = fmax(b.hi[k], c[k] + rr); }
+      }
+      for (int k = 0; k < 3; ++k) b.c[k] = 0.5 * (b.lo[k] + b.hi[k]);
+    }
+    std::vector<uint32_t> pairs(npairs);
+    for (size_t j = 0; j < npairs; ++j) pairs[j] = (uint32_t)j;
+    for (int k = 0; k < 3; ++k)
+    {
+      double lo = INFINITY, hi = -INFINITY;
+      for (const PairBox &pb : box) { lo = fmin(lo, pb.lo[k]); hi = fmax(hi, pb.hi[k]); }
+      bvh_ref[k] = (double)(float)(0.5 * (lo + hi));  // the float the kernel measures from
+    }
+    build_pair_bvh(bvh, pairs, 0, npairs, box, bvh_ref, 0, bvh_depth);
+    if (bvh_depth > kBvhStack) { bvh.clear(); bvh_depth = 0; }  // deeper than the kernel's stack: chunk loops
+    if (bvh.size() > 32767 || npairs > 32768) { bvh.clear(); bvh_depth = 0; }  // int16 stack slots (rfx_trace.h)
+  }
+  // triangle BVH (rfx_types.h RFX_TRI_BVH), when rfx_renderer_set_tri_accel asks for it: the nodes, the leaves' copy
+  // of the triangle records and the residual list
+  const bool want_tri = RFX_TRI_BVH && !small &&
+                        (tri_accel >= 1 || (tri_accel < 0 && s->tris.size() >= (size_t)RFX_TRI_BVH_AUTO_MIN));
+  if (want_tri)
+  {
+    if (nsph <= 32) tri_ref_point(s->tris, bvh_ref);
+    if (build_tri_tree(s->tris, bvh_ref, true, tt))
+    {
+      tleaf.assign(tt.order.size(), TriGeo{});
+      for (size_t q = 0; q < tt.order.size(); ++q)
+      {
+        const int32_t i = tt.order[q];
+        if (i < 0) continue;  // padding: all zero, never hit
+        tleaf[q] = tg[i];
+        const int32_t obj = s->tris[i].obj;
+        memcpy(&tleaf[q].pad[0], &i, 4);
+        memcpy(&tleaf[q].pad[1], &obj, 4);
+      }
+    }
+  }
+  for (const HostPlane &p : s->planes)
+  {
+    pg.push_back({p.pos.x, p.pos.y, p.pos.z, p.norm.x, p.norm.y, p.norm.z, p.obj, p.mat.dielectric});
+    pm.push_back({p.mat.r, p.mat.g, p.mat.b, p.mat.refl});
+  }
+  // object index -> (kind, index in the device arrays): spheres through their spatial order
+  loc.assign(s->obj_kind.size(), 0);
+  {
+    std::vector<int32_t> sph_dev(nsph);
+    for (size_t di = 0; di < nsph; ++di) sph_dev[order[di]] = (int32_t)di;
+    for (size_t o = 0; o < loc.size(); ++o)
+    {
+      const int kind = s->obj_kind[o], idx = s->obj_idx[o];
+      loc[o] = kind << 28 | (kind == 0 ? sph_dev[idx] : idx);
+    }
+  }
+  for (const HostLight &l : s->lights) lr.push_back({l.origin.x, l.origin.y, l.origin.z, l.radius, l.r, l.g, l.b, l.power});
+  for (const HostTexture &t : s->textures)
+  {
+    const bool empty = t.texels.empty();  // the reference's empty colorBuf: checker (Texture.cpp:242-243)
+    tr.push_back({(uint32_t)pool.size(), empty ? 0u : t.w, empty ? 0u : t.h, 0});
+    pool.insert(pool.end(), t.texels.begin(), t.texels.end());
+  }
+  d.n_tri_resid = (int32_t)tt.resid.size();
+  d.n_tri_bvh = (int32_t)tt.nodes.size();
+  d.tri_bvh_depth = tt.depth;
+  accel.tri_nodes = d.n_tri_bvh;
+  accel.tri_depth = tt.depth;
+  accel.tri_leaf_size = RFX_TRI_BVH_LEAF;
+  accel.tri_in_leaves = tt.nodes.empty() ? 0 : (int32_t)(s->tris.size() - tt.resid.size());
+  accel.tri_residual = d.n_tri_resid;
+  accel.sph_nodes = (int32_t)bvh.size();
+  accel.sph_depth = bvh_depth;
+  d.tri_bvh_narrow = !tt.nodes.empty() && (tri_accel == 2 || s->tris.size() >= (size_t)RFX_TRI_BVH_NARROW_MIN);
+  accel.narrow_tri_bvh = d.tri_bvh_narrow;
+  {
+    // the bounce kernel's LDS copy of the node links and margin terms (rfx_types.h DevScene::bvh_aux): mt rounded up
+    // to a multiple of mstep (one step more than the ceiling, so the float decode stays above)
+    float mt_max = 0.0f;
+    for (const BvhNode &n : bvh) mt_max = fmaxf(mt_max, fmaxf(n.mt[0], n.mt[1]));
+    const float mstep = mt_max > 0.0f ? mt_max / 65000.0f : 1.0f;
+    aux.assign(2 * bvh.size(), 0u);
+    for (size_t i = 0; i < bvh.size(); ++i)
+    {
+      const BvhNode &n = bvh[i];
+      uint32_t q[2];
+      for (int c = 0; c < 2; ++c) q[c] = (uint32_t)std::min(65535.0, ceil((double)n.mt[c] / mstep) + 1.0);
+      aux[2 * i] = ((uint32_t)(uint16_t)(int16_t)n.child[0]) | ((uint32_t)(uint16_t)(int16_t)n.child[1] << 16);
+      aux[2 * i + 1] = q[0] | q[1] << 16;
+    }
+    d.bvh_mstep = mstep;
+    d.n_bvh = (int32_t)bvh.size();
+  }
+  d.n_sph = (int32_t)sg.size();
+  d.n_tri = (int32_t)tg.size();
+  d.n_light = (int32_t)lr.size();
+  d.n_chunk = (int32_t)cb.size();
+  d.n_pln = (int32_t)pg.size();
+  d.n_tex = (int32_t)tr.size();
+  d.bvh_depth = bvh_depth;
+  d.bvh_rx = (float)bvh_ref[0]; d.bvh_ry = (float)bvh_ref[1]; d.bvh_rz = (float)bvh_ref[2];
+  if (!bvh.empty())  // regroup sort keys: 8 origin cells per axis over the root box
+  {
+    const BvhNode &root = bvh[0];
+    const float lo[3] = {fminf(root.lx[0], root.lx[1]), fminf(root.ly[0], root.ly[1]), fminf(root.lz[0], root.lz[1])};
+    const float hi[3] = {fmaxf(root.hx[0], root.hx[1]), fmaxf(root.hy[0], root.hy[1]), fmaxf(root.hz[0], root.hz[1])};
+    float s[3];
+    for (int k = 0; k < 3; ++k) s[k] = hi[k] > lo[k] ? 8.0f / (hi[k] - lo[k]) : 0.0f;
+    d.key_lx = lo[0]; d.key_ly = lo[1]; d.key_lz = lo[2];
+    d.key_sx = s[0]; d.key_sy = s[1]; d.key_sz = s[2];
+  }
+  d.n_obj = (int32_t)loc.size();
+  d.cull_valid = cull_valid;
+  d.skybox_tex = s->skybox;
+  const col amb = cscale(s->diff, s->diff_power);                                    // Scene.cpp:186 (first factor)
+  d.amb_r = amb.r; d.amb_g = amb.g; d.amb_b = amb.b;
+  d.env_r = s->env.r; d.env_g = s->env.g; d.env_b = s->env.b;
+  d.half_tile_w = s->half_tile_w;
+  d.half_tile_h = s->half_tile_h;
+}

@@ -1,0 +1,50 @@
+// The host-only part of librfx.so (rfx_scene.cpp: the scene builder, image files, camera helpers and the hierarchy
+// builders) as the rest of the library sees it.  No HIP here: a plain C++ compiler builds rfx_scene.cpp with this.
+#pragma once
+#include <stdint.h>
+
+#include <vector>
+
+#include "../../include/rfx.h"
+#include "rfx_types.h"
+
+namespace rfx {
+
+// records the calling thread's rfx_last_error text, returns code
+int fail(int code, const char *fmt, ...) __attribute__((format(printf, 2, 3)));
+
+// The triangle BVH of a non-small scene (rfx_scene.cpp build_tri_tree): order[] lists insertion indices, leaf g =
+// order[RFX_TRI_BVH_LEAF g ..], -1 padding the last leaf; resid: the triangles outside the tree.
+struct TriTree {
+  std::vector<BvhNode> nodes;
+  std::vector<int32_t> order;  // leaves x RFX_TRI_BVH_LEAF insertion indices (-1: padding)
+  std::vector<int32_t> resid;
+  int depth = 0;
+  size_t leaves() const { return order.size() / RFX_TRI_BVH_LEAF; }
+};
+
+// Everything rfx_renderer_set_scene puts on the device, built on the host from a scene and the renderer's
+// rfx_renderer_set_tri_accel mode: one vector per DevScene array (named as there in the comments), the scalar fields
+// of `d` (its pointers stay null: the upload sets them) and the hierarchies' summary.
+struct SceneBuild {
+  SceneBuild(const rfx_scene &scene, int tri_accel);
+  std::vector<SphereGeo> sg;                 // sph_geo
+  std::vector<SpherePair> sp;                // sph_pair
+  std::vector<MatRec> sm, tm, pm;            // sph_mat, tri_mat, pln_mat
+  std::vector<int32_t> si, loc;              // sph_info, obj_loc
+  std::vector<TriGeo> tg, tleaf;             // tri_geo, tri_leaf
+  std::vector<TriShade> ts;                  // tri_shade
+  std::vector<Bound> bd, cb;                 // bound, chunk_bound
+  std::vector<CullRec> cs;                   // cull_small
+  std::vector<CullTri> ct;                   // cull_tri
+  std::vector<BvhNode> bvh;                  // bvh
+  std::vector<uint32_t> aux, pool;           // bvh_aux, texels
+  TriTree tt;                                // tri_bvh (nodes), tri_resid (resid)
+  std::vector<PlaneGeo> pg;                  // pln_geo
+  std::vector<LightRec> lr;                  // lights
+  std::vector<TexRec> tr;                    // texs
+  DevScene d{};
+  rfx_accel_info accel{};
+};
+
+}  // namespace rfx

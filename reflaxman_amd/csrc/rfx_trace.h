@@ -27,6 +27,7 @@
 
 #include "rfx_math.h"
 #include "rfx_powf.h"
+#include "rfx_launch.h"
 #include "rfx_types.h"
 
 #pragma clang fp contract(off)
@@ -500,8 +501,7 @@ __device__ __forceinline__ bool plane_hit(const PlaneGeo &g, v3 o, v3 ray, float
 constexpr float kCullRel = 2e-3f;
 
 // per-view primary masks (prim_cull_kernel): per wave tile, the closest hit's mask and the shadow masks of the
-// first kPrimLights lights
-constexpr int kPrimLights = 4, kPrimStride = 1 + kPrimLights;
+// first kPrimLights lights (kPrimStride words, rfx_types.h)
 // Per-view masks of SSAA / additive frames (RFX_PRIM_SSAA) and per-view chunk lists of large scenes (RFX_PRIM_LARGE):
 // built, parity-tested and measured slower in round 4 (the screenshot frame +4.3%, C5 +3.3%; interleaved A/B,
 // profiles/r04/ab/), so compiled out by default
@@ -517,8 +517,8 @@ constexpr int kPrimLights = 4, kPrimStride = 1 + kPrimLights;
 #endif
 // Large scenes (prim_cull_large_kernel): per wave tile, the chunk cull of its primary bundle -- [0] the number of kept
 // 64-sphere chunks (at most kPrimLargeChunks; kPrimLargeNone: no list, the tile culls per launch), [1] the triangle mask,
-// [2] the chunk mask (scenes of at most 64 chunks), [4..] the kept chunks' sphere masks in chunk order
-constexpr int kPrimLargeChunks = 8, kPrimLargeStride = 4 + kPrimLargeChunks;
+// [2] the chunk mask (scenes of at most 64 chunks), [4..] the kept chunks' sphere masks in chunk order (kPrimLargeStride
+// words, rfx_types.h)
 constexpr uint64_t kPrimLargeNone = ~0ull;
 
 struct Bundle {
@@ -861,12 +861,12 @@ __device__ __forceinline__ bool tri_takes(float sq, float best_sq, int obj, int 
 // reference could report: skipping it changes no result.  Closest hit: a child whose entry distance exceeds
 // the best hit so far (with 0.1% slack over rounding; sphere distances computed by the reference are at least
 // the entry distance into their widened box) cannot win or tie and is skipped too.  Leaves run the exact
-// pair test with the (distance, object index) rule, so the visiting order changes no result.
-constexpr int kBvhStack = 16;
+// pair test with the (distance, object index) rule, so the visiting order changes no result.  The stack holds kBvhStack
+// (rfx_types.h) levels: the host builds no deeper hierarchy (rfx_scene.cpp: such a scene falls back to the chunk loops).
 #ifndef RFX_NARROW_BUNDLE_COS
 #define RFX_NARROW_BUNDLE_COS 0.9995f
 #endif
-constexpr float kNarrowBundleCos = RFX_NARROW_BUNDLE_COS;  // rfx_host.cpp RFX_BVH_STACK: deeper hierarchies fall back to the chunk loops
+constexpr float kNarrowBundleCos = RFX_NARROW_BUNDLE_COS;
 // Stack slots: int16 node / ~pair indices (the host builds no BVH for 32768 or more nodes or pairs).  Halving the
 // stack's LDS against int32 slots (8 -> 4 KB per workgroup) made C5 6.3% faster (tools/ab.py, round 2): workgroups
 // holding less LDS fit the CU's LDS with more slack as they finish out of order.
@@ -1137,7 +1137,7 @@ __device__ __forceinline__ int occluded_spheres_bvh(const DevScene &S, v3 o, v3 
 
 #if RFX_TRI_BVH
 // ------------------------------------------------------------- non-small scenes: per-ray triangle BVH
-// The same walk over the triangle tree (rfx_types.h RFX_TRI_BVH, rfx_host.cpp build_tri_tree).  A child box is the
+// The same walk over the triangle tree (rfx_types.h RFX_TRI_BVH, rfx_scene.cpp build_tri_tree).  A child box is the
 // AABB of its triangles' vertices under the margin of the sphere boxes: a triangle in the tree (cond < 300) reports a
 // hit only where the ray passes within kCullRel |o - p| of a point p of the triangle (DESIGN.md "Triangle BVH"), and
 // the box grown by kCullRel (|o - centre| + half-diagonal) + 1e-6 per axis holds that neighbourhood of every p
@@ -2165,11 +2165,9 @@ __host__ __device__ constexpr uint32_t ss_lane_block(int ss)
 // CFG bits: kCfgCull -- wave-bundle culling (every non-stats launch); kCfgManyLights -- more than 32 lights;
 // kCfgSmall -- at most 32 spheres and 32 triangles (one lane-layout cull mask for the whole scene)
 // kCfgPlanes -- the scene holds planes (Scene::addPlane extension); kCfgPark -- plain pixels park their traces
-// for the bounce kernel (ray regrouping; rfx_trace_plain_park.hip)
-constexpr int kCfgCull = 1, kCfgManyLights = 2, kCfgSmall = 4, kCfgPlanes = 8, kCfgPark = 16, kCfgOneLight = 32;
+// for the bounce kernel (ray regrouping; rfx_trace_plain_park.hip).  The values: rfx_types.h.
 // kCfgTriBvh -- a non-small scene with a triangle BVH (rfx_types.h RFX_TRI_BVH): its culling configurations carry the
 // triangle walkers; every other scene runs kernels without them (with them C5 traced 3.0% slower)
-constexpr int kCfgTriBvh = 64;
 #ifndef RFX_ONE_LIGHT
 #define RFX_ONE_LIGHT 1
 #endif
@@ -2925,21 +2923,5 @@ inline void launch_cfg(int cfg, dim3 grid, const DevScene &S, const FrameParams 
     case 15: launch_one<STATS, MODE, 15>(grid, S, P, st); break;
   }
 }
-
-// one trace_kernel family (rfx_trace_<mode>_<stats>.hip)
-#define RFX_DECLARE_TRACE_FAMILY(name) \
-  void name(int cfg, dim3 grid, const DevScene &S, const FrameParams &P, hipStream_t st)
-RFX_DECLARE_TRACE_FAMILY(launch_trace_plain_fast);
-RFX_DECLARE_TRACE_FAMILY(launch_trace_plain_stats);
-RFX_DECLARE_TRACE_FAMILY(launch_trace_ssaa_fast);
-RFX_DECLARE_TRACE_FAMILY(launch_trace_ssaa_stats);
-RFX_DECLARE_TRACE_FAMILY(launch_trace_lanes_fast);
-RFX_DECLARE_TRACE_FAMILY(launch_trace_lanes_stats);
-RFX_DECLARE_TRACE_FAMILY(launch_trace_chunks_fast);
-RFX_DECLARE_TRACE_FAMILY(launch_trace_chunks_stats);
-RFX_DECLARE_TRACE_FAMILY(launch_trace_block_fast);
-RFX_DECLARE_TRACE_FAMILY(launch_trace_block_stats);
-RFX_DECLARE_TRACE_FAMILY(launch_trace_plain_park);
-RFX_DECLARE_TRACE_FAMILY(launch_bounce);
 
 }  // namespace rfx

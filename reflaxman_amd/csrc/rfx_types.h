@@ -1,8 +1,9 @@
-// POD layouts shared by the host C-ABI (rfx_host.cpp) and the gfx950 kernels
+// POD layouts and constants shared by the host C-ABI (rfx_host.cpp, rfx_scene.cpp) and the gfx950 kernels
 // (rfx_trace.h, rfx_kernels.hip).  All device arrays are structure-of-arrays, 16-B aligned,
 // and walked in wave-uniform order by the trace kernel, so the compiler serves
 // them through the scalar cache (s_load_dwordx4) rather than per-lane loads.
 #pragma once
+#include <stddef.h>
 #include <stdint.h>
 
 namespace rfx {
@@ -40,7 +41,7 @@ struct alignas(16) TriShade {                                        // Triangle
   float tv0; int32_t tex; int32_t dielectric; int32_t obj;
 };
 // Bounding sphere of an object for the wave-bundle cull (rfx_trace.h): spheres first, then triangles.
-// r = +inf marks an object that is never culled (an ill-conditioned triangle, see rfx_host.cpp).
+// r = +inf marks an object that is never culled (an ill-conditioned triangle, see rfx_scene.cpp).
 struct alignas(16) Bound { float x, y, z, r; };
 // Small scenes (<= 32 spheres, <= 32 triangles): one cull record per lane of a wave.  Lanes 0-15 hold
 // spheres 0, 2, .., 30, lanes 16-31 spheres 1, 3, .., 31 (so a ballot folds into the pair mask with one
@@ -52,7 +53,7 @@ struct alignas(16) CullRec { float x, y, z, r, nx, ny, nz, d; };
 // u = gu . (P - v0) and v = gv . (P - v0) for P in the plane; nu = |gu|, nv = |gv|, nuv = |gu + gv| (+inf: the
 // footprint test must not touch the triangle -- ill-conditioned or degenerate).
 struct alignas(16) CullTri { float v0x, v0y, v0z, nu, gux, guy, guz, nv, gvx, gvy, gvz, nuv; };
-// Bounding-volume hierarchy over the sphere pairs of a large scene (rfx_host.cpp build_pair_bvh): an internal
+// Bounding-volume hierarchy over the sphere pairs of a large scene (rfx_scene.cpp build_pair_bvh): an internal
 // node holds its two children's boxes (the spheres grown by their radii) and their indices: c >= 0 an internal
 // node, c < 0 the leaf pair ~c (spheres 2(~c), 2(~c) + 1 of the device arrays, which are in spatial order).
 // mt[c]: |ref - centre of child c|_2 + its half-diagonal (ref: DevScene::bvh_ref), so that kCullRel (|o - ref|_2 + mt[c])
@@ -62,13 +63,15 @@ struct alignas(16) CullTri { float v0x, v0y, v0z, nu, gux, guy, guz, nv, gvx, gv
 #ifndef RFX_BVH_PREWIDE
 #define RFX_BVH_PREWIDE 1
 #endif
+// the kernels' per-lane traversal stack: the host builders keep both trees within it (a deeper one: the chunk loops)
+constexpr int kBvhStack = 16;
 struct alignas(16) BvhNode { float lx[2], ly[2], lz[2], hx[2], hy[2], hz[2]; int32_t child[2]; float mt[2]; };
-// Sphere pairs per BVH leaf (rfx_host.cpp build_pair_bvh, rfx_trace.h leaf tests): leaf ~g holds the pairs
+// Sphere pairs per BVH leaf (rfx_scene.cpp build_pair_bvh, rfx_trace.h leaf tests): leaf ~g holds the pairs
 // [RFX_BVH_LEAF_PAIRS g, RFX_BVH_LEAF_PAIRS (g + 1)) of the device order (sph_pair padded with never-hit pairs)
 #ifndef RFX_BVH_LEAF_PAIRS
 #define RFX_BVH_LEAF_PAIRS 4
 #endif
-// Triangle BVH of a non-small scene (rfx_host.cpp build_tri_tree, rfx_trace.h closest_tris_bvh / occluded_tris_bvh):
+// Triangle BVH of a non-small scene (rfx_scene.cpp build_tri_tree, rfx_trace.h closest_tris_bvh / occluded_tris_bvh):
 // BvhNode nodes with the sphere tree's conventions (child >= 0 internal, ~g a leaf, boxes pre-widened, the same
 // margin reference point DevScene::bvh_ref), so ray_inv and bvh_box serve both trees.  Leaf ~g holds the records
 // [RFX_TRI_BVH_LEAF g, RFX_TRI_BVH_LEAF (g + 1)) of DevScene::tri_leaf: a spatially ordered copy of the triangles'
@@ -187,5 +190,13 @@ struct FrameParams {
   const uint64_t *prim_mask;
   int32_t prim_shadow;
 };
+
+// words per wave tile of the per-view primary masks (rfx_trace.h prim_cull_kernel / prim_cull_large_kernel; the host
+// sizes FrameParams::prim_mask by them)
+constexpr int kPrimLights = 4, kPrimStride = 1 + kPrimLights;
+constexpr int kPrimLargeChunks = 8, kPrimLargeStride = 4 + kPrimLargeChunks;
+// the trace and bounce kernels' CFG template bits (rfx_trace.h trace_kernel), chosen per launch by the host
+constexpr int kCfgCull = 1, kCfgManyLights = 2, kCfgSmall = 4, kCfgPlanes = 8, kCfgPark = 16, kCfgOneLight = 32;
+constexpr int kCfgTriBvh = 64;
 
 }  // namespace rfx

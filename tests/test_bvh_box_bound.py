@@ -36,7 +36,7 @@ def kept(lo, hi, o, d, ref, mt, rng, fused):
         if fused:  # ray_inv clamps the reciprocals to +-1e30 for the fused forms
             inv = np.clip(inv, F(-1e30), F(1e30))
         if fused == "prewide":
-            # rfx_host.cpp: the box grown by kCullRel mt (x (1 + 1e-6)) and rounded outward; the kernel's slab
+            # rfx_scene.cpp: the box grown by kCullRel mt (x (1 + 1e-6)) and rounded outward; the kernel's slab
             # constants (o + dm) rcp(d) and (o - dm) rcp(d)
             w = 2e-3 * mt.astype(np.float64) * (1.0 + 1e-6)
             lo = np.nextafter((lo.astype(np.float64) - w[:, None]).astype(F), F(-np.inf))

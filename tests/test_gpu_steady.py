@@ -258,3 +258,33 @@ def test_emitted_frame_must_match_its_emit():
     _lib.check(L.rfx_render_frame_emitted(rr._h, C.byref(f), C.c_void_p(img.data_ptr()), None, None, None))
     rr.synchronize()
     rr.close()
+
+
+def test_one_renderer_across_sizes_and_scenes():
+    """One Render object through stored goldens of changing size, scene and sampling, never recreated: every workspace
+    of the renderer is met grown-earlier-and-smaller-now as well as growing (randDir and pre-pass block arrays, the
+    regroup queue of the large scene, per-view masks, the mesh scene's hierarchies), and every frame still equals its
+    golden byte for byte."""
+    import os
+
+    from helpers import GOLDEN
+    from reflaxman_amd.render import Render, build_scene
+    cases = manifest()["cases"]
+    r = Render(load_default_scene=False)
+    for key in ["render_default_7x3_d8", "render_default_160x120_d8", "render_stress4096_64x36_d12",
+                "render_default_7x3_d8", "render_default_64x40_d8_ss4", "render_mesh100_160x90_d8",
+                "render_default_17x9_d8_ss16_add2"]:
+        c = cases[key]
+        r.scene, r.camera = build_scene(scenes.get_scene(c["scene"]))
+        r.setImageSize(c["W"], c["H"])
+        r._r.set_rng(c["sphere_seed"], c.get("jitter_seed", 0))
+        for _ in range(c["frames"]):
+            r.renderBegin(c["depth"], c["ss"], c["additive"])
+            while r.renderNext(c["W"] * c["H"]):
+                pass
+        r.synchronize()
+        g = np.load(os.path.join(GOLDEN, key + ".npz"))
+        assert r.imagePixels().tobytes() == g["rgb"].tobytes(), key
+        assert r.copyImage().tobytes() == g["argb"].tobytes(), key
+    r._r.get_rng()  # raises on an error left by any pre-pass
+    r._r.close()

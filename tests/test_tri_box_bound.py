@@ -1,6 +1,6 @@
 """The BVH box test (rfx_trace.h ray_inv, bvh_box) keeps the box of every triangle a ray is reported to hit.
 
-The triangle tree (rfx_host.cpp build_tri_tree) holds the triangles whose basis has cond < 300; a child box is the
+The triangle tree (rfx_scene.cpp build_tri_tree) holds the triangles whose basis has cond < 300; a child box is the
 AABB of its triangles' vertices, widened like the sphere boxes by kCullRel (|o - centre| + half-diagonal) + 1e-6.
 That is sound if a ray the reference's float test (Triangle.cpp:53-108) reports as a hit passes within that margin of
 the vertices' box.  This test takes the reference's verdict from the oracle's triangle known-answer entry

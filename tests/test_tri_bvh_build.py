@@ -2,7 +2,7 @@
 
 Every triangle sits in exactly one leaf or in the residual list; ill-conditioned and singular triangles are
 residual; each child box holds every vertex beneath it; depth and node count stay within what the kernels' int16
-stack of RFX_BVH_STACK = 16 slots can walk; rfx_scene_add_mesh builds the scene the per-triangle calls build.
+stack of kBvhStack = 16 slots can walk; rfx_scene_add_mesh builds the scene the per-triangle calls build.
 """
 import ctypes as C
 
