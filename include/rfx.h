@@ -177,6 +177,16 @@ int rfx_renderer_accel_info(const rfx_renderer *r, rfx_accel_info *out);
  * sampleNum > 8 (a wave per pixel) take one closest-hit mask per pixel, built for every view and every launch of a split
  * frame under 1 and 2.  Any call forgets the views seen so far. */
 int rfx_renderer_set_prim_masks(rfx_renderer *r, int mode);
+/* The masks of a still view narrowed to its primary hits, which depend on the view alone (no pixel changes): 1 (default)
+ * = where those hits are known ahead (no jitter, sampleNum <= 8) the closest-hit mask is the set of the tile's winners
+ * and each shadow mask drops the one object that all the tile's lit hits lie on (its answer is discarded anyway); 0 = the
+ * conservative bundle culls alone.  Any call drops the masks held, so the next frame of the view builds them again. */
+int rfx_renderer_set_prim_exact(rfx_renderer *r, int on);
+/* Copy the masks the renderer holds for the current view to `host`, after synchronising the stream they were built on:
+ * *words = their length in 64-bit words (5 per 8x8 wave tile of a small scene: the closest-hit mask, then one shadow
+ * mask per light up to 4, 0 past the scene's lights and where a frame takes no shadow masks; bit (i & 1) * 16 + (i >> 1)
+ * is sphere i, bit 32 + i triangle i), 0 when no view's masks are held.  `host` may be NULL to ask for the length alone; a capacity below it is RFX_ERR_ARG. */
+int rfx_renderer_get_prim_masks(rfx_renderer *r, uint64_t *host, uint64_t capacity, uint64_t *words);
 /* The reference's two LCG streams (trace_math.h:34-39): Vector3.cpp's (randomInsideSphere) and
  * Render.cpp's (additive jitter).  Both persist across frames exactly as the reference's would. */
 int rfx_renderer_set_rng(rfx_renderer *r, uint32_t sphere_seed, uint32_t jitter_seed);

@@ -106,6 +106,8 @@ SIGNATURES = [
     ("rfx_renderer_set_timing", C.c_int, [C.c_void_p, C.c_int]),
     ("rfx_renderer_set_tile_order", C.c_int, [C.c_void_p, C.c_int]),
     ("rfx_renderer_set_prim_masks", C.c_int, [C.c_void_p, C.c_int]),
+    ("rfx_renderer_set_prim_exact", C.c_int, [C.c_void_p, C.c_int]),
+    ("rfx_renderer_get_prim_masks", C.c_int, [C.c_void_p, _u64p, C.c_uint64, _u64p]),
     ("rfx_renderer_set_regroup", C.c_int, [C.c_void_p, C.c_int]),
     ("rfx_renderer_set_regroup_sort", C.c_int, [C.c_void_p, C.c_int]),
     ("rfx_renderer_set_launch_traces", C.c_int, [C.c_void_p, C.c_uint64]),

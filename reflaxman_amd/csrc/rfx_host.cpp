@@ -245,6 +245,28 @@ extern "C" int rfx_renderer_set_prim_masks(rfx_renderer *r, int mode)
   return RFX_OK;
 }
 
+extern "C" int rfx_renderer_set_prim_exact(rfx_renderer *r, int on)
+{
+  if (!r || on < 0 || on > 1) return fail(RFX_ERR_ARG, "renderer_set_prim_exact: 0 or 1");
+  r->prim_exact = on;
+  r->prim_key.clear();  // the next frame builds its masks again (the views seen stay: a repeated view still counts)
+  return RFX_OK;
+}
+
+extern "C" int rfx_renderer_get_prim_masks(rfx_renderer *r, uint64_t *host, uint64_t capacity, uint64_t *words)
+{
+  if (!r || !words) return fail(RFX_ERR_ARG, "renderer_get_prim_masks: null argument");
+  int rc;
+  if ((rc = set_dev(r)) != RFX_OK) return rc;
+  const uint64_t n = r->prim_key.empty() ? 0 : r->prim_words;
+  *words = n;
+  if (!n || !host) return RFX_OK;  // nothing held, or the length alone was asked for
+  if (capacity < n) return fail(RFX_ERR_ARG, "renderer_get_prim_masks: the host array is too short");
+  HIP_CHECK(hipStreamSynchronize(r->prim_on));
+  HIP_CHECK(hipMemcpy(host, r->prim_mask.p, n * sizeof(uint64_t), hipMemcpyDeviceToHost));
+  return RFX_OK;
+}
+
 extern "C" int rfx_renderer_set_rng_prepass(rfx_renderer *r, int mode)
 {
   if (!r || mode < 0 || mode > 1) return fail(RFX_ERR_ARG, "renderer_set_rng_prepass: mode 0 or 1");
@@ -758,7 +780,7 @@ static int select_view_masks(rfx_renderer *r, FramePlan &pl, bool small, bool pl
   {
     DevBuf<uint64_t> &mask = r->split_mask[pl.split_side];
     if ((rc = mask.reserve((size_t)trace_tiles(P) * kPrimStride)) < 0) return rc;
-    HIP_CHECK(launch_prim_cull(r->dev, P, mask, st));
+    HIP_CHECK(launch_prim_cull(r->dev, P, mask, r->prim_exact != 0, st));
     P.prim_mask = mask;
     P.prim_shadow = 0;
   }
@@ -792,8 +814,10 @@ static int select_view_masks(rfx_renderer *r, FramePlan &pl, bool small, bool pl
       r->prim_key.clear();
       if (repeat || r->prim_mode == 2 || chunks)
       {
-        HIP_CHECK(launch_prim_cull(r->dev, P, r->prim_mask, st));
+        HIP_CHECK(launch_prim_cull(r->dev, P, r->prim_mask, r->prim_exact != 0, st));
         r->prim_key = kb;
+        r->prim_words = (size_t)trace_tiles(P) * (small ? kPrimStride : kPrimLargeStride);
+        r->prim_on = st;
       }
     }
     if (!r->prim_key.empty())

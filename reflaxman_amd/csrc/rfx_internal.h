@@ -185,6 +185,9 @@ struct rfx_renderer {
   std::vector<uint8_t> prim_seen;  // the view of the last plain small-scene launch
   uint64_t scene_gen = 0;  // bumped by every set_scene
   int prim_mode = 1;       // rfx_renderer_set_prim_masks
+  int prim_exact = 1;      // rfx_renderer_set_prim_exact: the masks narrowed to the view's known primary hits
+  size_t prim_words = 0;   // words of prim_mask that hold prim_key's masks, built on stream prim_on
+  hipStream_t prim_on = nullptr;
   int tri_accel = -1;      // rfx_renderer_set_tri_accel: -1 automatic (RFX_TRI_BVH_AUTO_MIN triangles), 0 off, 1 on,
                            // 2 on with the narrow bundles walking the tree too
   rfx_accel_info accel{};  // the uploaded scene's hierarchies (rfx_renderer_accel_info)

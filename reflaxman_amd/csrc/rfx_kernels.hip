@@ -1523,22 +1523,24 @@ bool trace_chunks(const FrameParams &P)
 
 // the per-view masks of a small scene's plain or SSAA frame (prim_cull_kernel, kPrimStride words per wave tile), or
 // a large scene's chunk lists (prim_cull_large_kernel, kPrimLargeStride words)
-hipError_t launch_prim_cull(const DevScene &S, const FrameParams &P, uint64_t *masks, hipStream_t st)
+// narrow: prim_cull_kernel's exact rules on top of the conservative words (rfx_renderer_set_prim_exact)
+hipError_t launch_prim_cull(const DevScene &S, const FrameParams &P, uint64_t *masks, bool narrow, hipStream_t st)
 {
+  const int nw = narrow ? 1 : 0;
   const dim3 grid = trace_grid(P);
   if (!(S.n_sph <= 32 && S.n_tri <= 32))  // large scenes: the primary bundles' chunk lists
     hipLaunchKernelGGL(prim_cull_large_kernel<0>, grid, dim3(kWgThreads), 0, st, S, P, masks);
   else if (trace_lanes(P) || trace_chunks(P))
   {
     if (S.n_pln > 0)
-      hipLaunchKernelGGL((prim_cull_kernel<true, true>), grid, dim3(kWgThreads), 0, st, S, P, masks);
+      hipLaunchKernelGGL((prim_cull_kernel<true, true>), grid, dim3(kWgThreads), 0, st, S, P, masks, nw);
     else
-      hipLaunchKernelGGL((prim_cull_kernel<false, true>), grid, dim3(kWgThreads), 0, st, S, P, masks);
+      hipLaunchKernelGGL((prim_cull_kernel<false, true>), grid, dim3(kWgThreads), 0, st, S, P, masks, nw);
   }
   else if (S.n_pln > 0)
-    hipLaunchKernelGGL(prim_cull_kernel<true>, grid, dim3(kWgThreads), 0, st, S, P, masks);
+    hipLaunchKernelGGL(prim_cull_kernel<true>, grid, dim3(kWgThreads), 0, st, S, P, masks, nw);
   else
-    hipLaunchKernelGGL(prim_cull_kernel<false>, grid, dim3(kWgThreads), 0, st, S, P, masks);
+    hipLaunchKernelGGL(prim_cull_kernel<false>, grid, dim3(kWgThreads), 0, st, S, P, masks, nw);
   return hipGetLastError();
 }
 

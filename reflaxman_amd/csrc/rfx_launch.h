@@ -36,7 +36,7 @@ hipError_t launch_rng_emit_seq(const uint32_t *d_pos, const uint32_t *d_hdr, con
                                uint32_t *d_next_pos, int *d_err, hipStream_t st);
 // ---- rfx_kernels.hip: the trace launch, its per-view masks, the tile and regroup sorts, the known-answer kernels
 hipError_t launch_trace(const DevScene &S, const FrameParams &P, bool stats, hipStream_t st);
-hipError_t launch_prim_cull(const DevScene &S, const FrameParams &P, uint64_t *masks, hipStream_t st);
+hipError_t launch_prim_cull(const DevScene &S, const FrameParams &P, uint64_t *masks, bool narrow, hipStream_t st);
 hipError_t launch_queue_sort(const uint32_t *count, const uint32_t *key, uint32_t *hist, uint32_t *order, hipStream_t st);
 uint32_t trace_tiles(const FrameParams &P);
 bool trace_lanes(const FrameParams &P);

@@ -2553,8 +2553,10 @@ __global__ __launch_bounds__(kWgThreads) __attribute__((amdgpu_waves_per_eu(
 // unit jitter square), so the shadow masks need one primary hit per lane.  A kModeSsaaChunks frame (sampleNum > 8, the
 // wave is one pixel): the closest-hit mask of the pixel's whole sample rectangle, which every chunk of its samples reuses;
 // no shadow masks (they would need the primary hit of every sample).
+// narrow (rfx_renderer_set_prim_exact): where the hits are known ahead (no jitter, no chunks) the conservative words are
+// narrowed to what those hits need -- [0] to the tile's winners, [1 + q] without the one object all its facing hits lie on.
 template <bool PLANES, bool LANES = false>
-__global__ RFX_TRACE_BOUNDS void prim_cull_kernel(DevScene S, FrameParams P, uint64_t *masks)
+__global__ RFX_TRACE_BOUNDS void prim_cull_kernel(DevScene S, FrameParams P, uint64_t *masks, int narrow)
 {
   stage_small_scene(S);
   __syncthreads();
@@ -2617,15 +2619,23 @@ __global__ RFX_TRACE_BOUNDS void prim_cull_kernel(DevScene S, FrameParams P, uin
     }
     om = B.ok ? cull_small<true>(T.cull(), S.cull_valid, B, S.cull_tri) : S.cull_valid;
   }
-  if (lane == 0) out[0] = om;
   // the primary hits of every sample, as trace_from's first segment finds them with this mask (Scene.cpp:86-106), and
-  // per light the union of their shadow bundles' masks.  Jittered frames: the hits are not known ahead, no shadow masks
-  // (FrameParams::prim_shadow; the trace kernel builds those bundles itself).
-  const int nl = P.additive || chunks ? 0 : min(S.n_light, kPrimLights);
+  // per light the union of their shadow bundles' masks.  Jittered frames and chunks: the hits are not known ahead, no
+  // shadow masks (FrameParams::prim_shadow; the trace kernel builds those bundles itself).
+  const bool known = !P.additive && !chunks;
+  const int nl = known ? min(S.n_light, kPrimLights) : 0;
   uint64_t sm[kPrimLights] = {0, 0, 0, 0};
+  // narrow: the two exact rules on top of the conservative words.  win: the union of the tile's winners' bits -- the
+  // closest-hit rule (distance, then object index) does not depend on the order or on the losers tested beside the
+  // winner, so every lane finds the same Hit among the winners alone.  own[q]: the one object that every facing
+  // (lane, sample) toward light q hit (kOwnNone: no facing lane yet, kOwnMixed: more than one object) -- the any-hit
+  // test discards that object's answer (occluded_small: skip_sph / skip_tri), so its bit only costs a test.
+  constexpr int kOwnNone = -1, kOwnMixed = -2, kOwnPlane = 64;
+  uint64_t win = 0;
+  int own[kPrimLights] = {kOwnNone, kOwnNone, kOwnNone, kOwnNone};
   const float ssf = (float)ss;
   const int nss = LANES ? 1 : ss;  // LANES: the lane's one sample
-  for (int sx = 0; nl > 0 && sx < nss; ++sx)
+  for (int sx = 0; known && (nl > 0 || narrow) && sx < nss; ++sx)
     for (int sy = 0; sy < nss; ++sy)
     {
       // the sample's ray exactly as trace_kernel forms it (plain: rx + 0 + 0; SSAA: rx + float(sx) / ss + 0)
@@ -2636,6 +2646,13 @@ __global__ RFX_TRACE_BOUNDS void prim_cull_kernel(DevScene S, FrameParams P, uin
       if (valid) closest_hit_small<false, PLANES>(S, eye, ray, om, h, cnt);
       else h.obj = -1;
       const bool hit = valid && h.obj >= 0;
+      // the winner's bit in the lane layout of the masks (small_pairs / small_tris); planes are in no mask
+      const int bit = !hit ? kOwnPlane : h.kind == 0 ? (h.i & 1) * 16 + (h.i >> 1) : h.kind == 1 ? 32 + h.i : kOwnPlane;
+      for (uint64_t c = narrow ? om : 0; c; c &= c - 1ull)  // the winners are among the mask's objects
+      {
+        const int b = __builtin_ctzll(c);
+        if (__ballot(bit == b)) win |= 1ull << b;
+      }
       v3 drop = eye, norm = mk(0.0f, 0.0f, 0.0f);
       if (hit)
       {
@@ -2661,14 +2678,26 @@ __global__ RFX_TRACE_BOUNDS void prim_cull_kernel(DevScene S, FrameParams P, uin
         const LightRec L = S.lights[q];
         const v3 dtl = sub(mk(L.ox, L.oy, L.oz), drop);
         const bool facing = hit && dot(dtl, norm) > kVerySmall;                  // Scene.cpp:125
-        if (__ballot(facing))
+        const uint64_t fb = __ballot(facing);
+        if (fb)
         {
           const Bundle SB = make_bundle_ball(drop, dtl, L.radius, facing);
           sm[q] |= SB.ok ? cull_small(T.cull(), S.cull_valid, SB) : S.cull_valid;
+          const int first = __builtin_amdgcn_readlane(bit, __builtin_ctzll(fb));
+          const int now = __ballot(facing && bit != first) ? kOwnMixed : first;
+          own[q] = own[q] == kOwnNone || own[q] == now ? now : kOwnMixed;
         }
       }
     }
-  for (int q = 0; q < nl; ++q)
+  if (known && narrow)
+  {
+    om = win;
+    // a sphere loses its own bit only: its pair is still tested where the partner's bit is set (small_pairs ORs the two)
+    for (int q = 0; q < nl; ++q)
+      if (own[q] >= 0 && own[q] < kOwnPlane) sm[q] &= ~(1ull << own[q]);
+  }
+  if (lane == 0) out[0] = om;
+  for (int q = 0; q < kPrimLights; ++q)  // the words past the scene's lights are 0 (never read; a defined read-back)
     if (lane == 0) out[1 + q] = sm[q];
 }
 

@@ -342,6 +342,22 @@ class Renderer:
         call forgets the views seen so far."""
         check(_lib.load().rfx_renderer_set_prim_masks(self._h, int(mode)), "set_prim_masks")
 
+    def set_prim_exact(self, on: bool):
+        """The per-view masks narrowed to the view's known primary hits (rfx.h rfx_renderer_set_prim_exact): on by
+        default; off leaves the conservative bundle culls.  No pixel changes.  Any call drops the masks held."""
+        check(_lib.load().rfx_renderer_set_prim_exact(self._h, int(bool(on))), "set_prim_exact")
+
+    def prim_masks(self) -> np.ndarray:
+        """The masks held for the current view (rfx.h rfx_renderer_get_prim_masks) as a flat uint64 array -- a small
+        scene's: 5 words per 8x8 wave tile, tiles in raster order -- or an empty one when none are held.  Synchronises."""
+        L = _lib.load()
+        n = C.c_uint64()
+        check(L.rfx_renderer_get_prim_masks(self._h, None, 0, C.byref(n)), "get_prim_masks")
+        out = np.zeros(n.value, np.uint64)
+        if n.value:
+            check(L.rfx_renderer_get_prim_masks(self._h, _lib.u64ptr(out), n.value, C.byref(n)), "get_prim_masks")
+        return out
+
     def set_regroup(self, park_after: int):
         """Ray regrouping (rfx.h rfx_renderer_set_regroup): -1 default (large scenes, after 2 segments), 0 off,
         n >= 1 park traces alive after n segments for the packed bounce kernel.  No pixel changes."""

@@ -115,7 +115,7 @@ VARIANTS = {
     "seq0": ["RFX_RNG_SEQ=0"],  # every frame's pre-pass by the count / emit kernels (no cycle table)
     "seqsplit0": ["RFX_RNG_SEQ_SPLIT=0"],  # the spans of split frames keep the count / scan / emit kernels
     "seqbig": ["RFX_RNG_SEQ_MIN_BLOCKS=257"],  # the table only where rng_fused does not apply
-    "trinonarrow": ["RFX_TRI_BVH_NARROW_MIN=(1<<30)"],  # narrow bundles always keep the bundle-culled chunk loop (base)
+    "trinonarrow":["RFX_TRI_BVH_NARROW_MIN=(1<<30)"],  # narrow bundles always keep the bundle-culled chunk loop (base)
 }
 
 
@@ -155,7 +155,7 @@ def build_scene_with(L, desc):
 
 class Runner:
     def __init__(self, name, path, desc, W, H, depth, seed, tile_order=None, regroup=None, prim=None, ss=1, additive=0,
-                 tri_accel=None):
+                 tri_accel=None, exact=None):
         self.name = name
         L = self.L = _lib.bind(path, partial=True)
         self.scene, eye, view, fov = build_scene_with(L, desc)
@@ -172,6 +172,8 @@ class Runner:
             assert L.rfx_renderer_set_regroup(self.r, regroup) == 0
         if prim is not None:
             assert L.rfx_renderer_set_prim_masks(self.r, prim) == 0
+        if exact is not None:
+            assert L.rfx_renderer_set_prim_exact(self.r, exact) == 0
         self.W, self.H = W, H
         self.img, self.argb = C.c_void_p(), C.c_void_p()
         assert L.rfx_device_alloc(self.r, W * H * 12, C.byref(self.img)) == 0
@@ -238,11 +240,14 @@ def cmd_run(args):
     regroups = [None] if not args.regroup else [int(v) for v in args.regroup.split(",")]
     prims = [None] if not args.prim else [int(v) for v in args.prim.split(",")]
     tris = [None] if not args.tri_accel else [int(v) for v in args.tri_accel.split(",")]
+    exacts = [None] if not args.exact else [int(v) for v in args.exact.split(",")]
     runners = [Runner(n + ("" if g is None else f"@park{g}") + ("" if q is None else f"@prim{q}") +
-                      ("" if t is None else f"@tri{t}"), p, desc, args.width,
+                      ("" if t is None else f"@tri{t}") + ("" if e is None else f"@exact{e}"), p, desc, args.width,
                       args.height, args.depth, 1350490027, regroup=g, prim=q, ss=args.ss, additive=args.additive,
-                      tri_accel=t)
-               for n, p in zip(names, paths) for g in regroups for q in prims for t in tris]
+                      tri_accel=t, exact=e)
+               for n, p in zip(names, paths) for g in regroups for q in prims for t in tris
+               # a build from before the switch (tools/build_rev.py) runs once, as it is
+               for e in (exacts if hasattr(C.CDLL(p), "rfx_renderer_set_prim_exact") else [None])]
     # parity of every variant: frame 1 against the reference's full-frame hash (when the manifest has one), and
     # frame 1 + LATER frames (rendered in the learned longest-tile-first order, after the tile sorts) against
     # the product build rendering the same frames in raster order
@@ -277,8 +282,10 @@ def cmd_run(args):
         med = statistics.median(times[r.name])
         out.append({"variant": r.name, "defines": VARIANTS.get(r.name.split("@")[0]), "parity_sha_ok": parity[r.name],
                     "trace_ms_median": round(med, 4), "trace_ms_min": round(min(times[r.name]), 4),
+                    "trace_ms_max": round(max(times[r.name]), 4),
                     "prepass_ms_median": round(statistics.median(pre[r.name]), 4),
                     "frame_ms_median": round(statistics.median(wall[r.name]), 4),
+                    "frame_ms_min": round(min(wall[r.name]), 4), "frame_ms_max": round(max(wall[r.name]), 4),
                     "vs_first": round(med / base, 4),
                     "mrays_trace_only": round(args.width * args.height * args.ss ** 2 / (med * 1e-3) / 1e6, 1)})
     for o in out:
@@ -303,6 +310,8 @@ def main():
     ap.add_argument("--regroup", default="", help="comma list of park_after settings to run each build with (0 = off)")
     ap.add_argument("--prim", default="", help="comma list of rfx_renderer_set_prim_masks modes to run each build with")
     ap.add_argument("--tri-accel", default="", help="comma list of rfx_renderer_set_tri_accel modes to run each build with")
+    ap.add_argument("--exact", default="", help="comma list of rfx_renderer_set_prim_exact settings to run each build with "
+                    "(1: the masks narrowed to the view's primary hits, 0: the conservative masks)")
     args = ap.parse_args()
     if args.cmd == "build":
         cmd_build(args.variants.split(","))
