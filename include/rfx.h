@@ -106,6 +106,15 @@ int rfx_scene_counts(const rfx_scene *scene, int *spheres, int *triangles, int *
  * for the leaf size), < 0 on error. */
 int rfx_scene_tri_bvh_dump(const rfx_scene *scene, int32_t counts[5], float *boxes, int32_t *children,
                            int32_t *leaf_ids, int32_t *residual);
+/* Mate groups of the scene's triangles (host only; DESIGN.md "Coplanar mates"): triangles whose plane-crossing half of
+ * Triangle::trace gives one value for every ray -- the third row of axTrans finite and bitwise equal, v0 finite and
+ * bitwise equal on every axis whose row-3 coefficient is not zero.  The small-scene kernels compute that half once per
+ * group and ray.  rfx_scene_set_tri_mates(scene, 0) makes every triangle its own group (the same pixels; on by default;
+ * read by the next rfx_renderer_set_scene).  rfx_scene_tri_mates returns the triangle count and writes, where given,
+ * each triangle's leader -- the lowest triangle index (0 = the scene's first triangle) of its group -- into
+ * leader[0 .. triangles - 1], and the operands the rule compares into plane[6 t .. 6 t + 5] = v0 x y z, a31 a32 a33. */
+int rfx_scene_set_tri_mates(rfx_scene *scene, int on);
+int rfx_scene_tri_mates(const rfx_scene *scene, int32_t *leader, float *plane);
 
 /* ---------------------------------------------------------------- Camera */
 /* Camera(eye, at, fov): view = [ox | oy | oz] columns, row-major _11.._33 -- Camera.cpp:24-38 */

@@ -10,7 +10,9 @@
 #include <string.h>
 
 #include <algorithm>
+#include <array>
 #include <cmath>
+#include <map>
 #include <string>
 #include <vector>
 
@@ -59,6 +61,7 @@ struct rfx_scene {
   float diff_power;
   float half_tile_w, half_tile_h;
   int skybox = -1;
+  int tri_mates = 1;  // rfx_scene_set_tri_mates
   std::vector<HostSphere> spheres;
   std::vector<HostTri> tris;
   std::vector<HostPlane> planes;
@@ -687,6 +690,60 @@ extern "C" int rfx_scene_tri_bvh_dump(const rfx_scene *s, int32_t counts[5], flo
   return 1;
 }
 
+// ============================================================== coplanar mates
+// Triangle::trace (Triangle.cpp:53-108) starts with the z row of axTrans (o - v0) and of axTrans ray:
+//   aoz = (o.x - v0x) a31 + (o.y - v0y) a32 + (o.z - v0z) a33,   arz = ray.x a31 + ray.y a32 + ray.z a33,
+// and everything up to t = -aoz / arz and `t > VERY_SMALL_NUMBER` is a function of those two and the ray (rfx_trace.h
+// tri_z).  Triangles A and B are mates iff (a31, a32, a33) are finite and bitwise equal in both, all six v0 components
+// are finite, and on each axis i either v0_i is bitwise equal or a3i == 0.  Then for one ray:
+//   arz has identical operands in both, so it is identical;
+//   aoz differs only in the terms of the axes with a3i == 0: there d a3i is +-0 for a finite difference d (a zero term
+//     leaves the float sum's value as it is, only the sign of a zero sum can change), and NaN in both for an infinite
+//     or NaN o_i (o_i - v0_i is then the same infinity, or NaN, for any finite v0_i);
+//   so aoz, arz and all that tri_z derives from them are equal as values, or NaN in both; every use is blind to the
+//   sign of a zero (fabsf, compares with 0, nz nz, the quotient of non-zero operands).
+// (A finite o_i whose difference from one v0_i overflows and from the other does not, |o_i| >= 2^127, is outside the rule.)
+// The relation is an equivalence (equal keys below), a group's leader its lowest index.  Needs FP contraction off.
+static std::vector<int32_t> tri_mate_leaders(const std::vector<HostTri> &tris, bool on)
+{
+  std::vector<int32_t> leader(tris.size());
+  std::map<std::array<uint32_t, 6>, int32_t> first;
+  for (size_t i = 0; i < tris.size(); ++i)
+  {
+    const HostTri &t = tris[i];
+    leader[i] = (int32_t)i;
+    const float row[3] = {t.ax.m31, t.ax.m32, t.ax.m33}, v0[3] = {t.v0.x, t.v0.y, t.v0.z};
+    bool finite = on;
+    std::array<uint32_t, 6> key{};
+    for (int a = 0; a < 3; ++a)
+    {
+      finite = finite && std::isfinite(row[a]) && std::isfinite(v0[a]);
+      memcpy(&key[a], &row[a], 4);
+      if (row[a] != 0.0f) memcpy(&key[3 + a], &v0[a], 4);
+    }
+    if (finite) leader[i] = first.emplace(key, (int32_t)i).first->second;
+  }
+  return leader;
+}
+
+extern "C" int rfx_scene_set_tri_mates(rfx_scene *s, int on)
+{
+  if (!s || on < 0 || on > 1) return fail(RFX_ERR_ARG, "scene_set_tri_mates: 0 or 1");
+  s->tri_mates = on;
+  return RFX_OK;
+}
+
+extern "C" int rfx_scene_tri_mates(const rfx_scene *s, int32_t *leader, float *plane)
+{
+  if (!s) return fail(RFX_ERR_ARG, "scene_tri_mates: null scene");
+  const std::vector<int32_t> l = tri_mate_leaders(s->tris, s->tri_mates != 0);
+  if (leader) std::copy(l.begin(), l.end(), leader);
+  if (plane)
+    for (const HostTri &t : s->tris)
+      for (float f : {t.v0.x, t.v0.y, t.v0.z, t.ax.m31, t.ax.m32, t.ax.m33}) *plane++ = f;
+  return (int)l.size();
+}
+
 // ============================================================== the device form of a scene
 SceneBuild::SceneBuild(const rfx_scene &scene, int tri_accel)
 {
@@ -739,6 +796,9 @@ SceneBuild::SceneBuild(const rfx_scene &scene, int tri_accel)
     ts.push_back(h);
     tm.push_back({t.mat.r, t.mat.g, t.mat.b, t.mat.refl});
   }
+  // the mate group's leader in the record's padding (the BVH leaf copies below overwrite theirs)
+  const std::vector<int32_t> leader = tri_mate_leaders(s->tris, s->tri_mates != 0);
+  for (size_t i = 0; i < tg.size(); ++i) memcpy(&tg[i].pad[0], &leader[i], 4);
   // bounding spheres for the wave-bundle cull: a sphere's own (radius grown by a relative 1e-5), a
   // triangle's centroid and farthest vertex; a triangle whose axTrans is ill-conditioned (the reference
   // falls back to the identity for a singular basis, Matrix33.cpp:58-79) may report hits far from its

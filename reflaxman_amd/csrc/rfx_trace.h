@@ -400,9 +400,12 @@ __device__ __forceinline__ bool sphere_tail(float b, float d, v3 ray, const RayC
 // ((aox, aoy), (arx, ary), (u, v)), each half rounding exactly as the scalar expression.
 // PRE: reject plane crossings outside the triangle before the divide (below).  tools/ab.py, trace ms: large-scene
 // shadow rays 3.399 -> 3.327 on C5 (-2.1%); small scenes (C3) +0.6% in either loop, closest hit on C5 0%.
-template <bool STATS, bool SHADOW, bool PRE = false>
-__device__ __forceinline__ bool tri_hit(const TriGeo &g, v3 o, v3 ray, float &t_out, float &u_out, float &v_out,
-                                        float &sq_out, Cnt &cnt, const RayConst &k, float best_sq = INFINITY)
+// The z stage: everything that depends on the triangle only through its plane -- the third row of axTrans and the
+// components of v0 that row weighs (coplanar mates, rfx_scene.cpp tri_mate_leaders, share it: tri_z of any member
+// gives every member's answer and t).  False: no hit, whatever (u, v).
+template <bool STATS, bool SHADOW>
+__device__ __forceinline__ bool tri_z(const TriGeo &g, v3 o, v3 ray, const RayConst &k, float best_sq, Cnt &cnt,
+                                      float &nz_out, float &arz_out)
 {
   RFX_CNT(SHADOW ? C_SH_TRI_TESTS : C_TRI_TESTS);
   const float dx = o.x - g.v0x, dy = o.y - g.v0y, dz = o.z - g.v0z;
@@ -431,12 +434,51 @@ __device__ __forceinline__ bool tri_hit(const TriGeo &g, v3 o, v3 ray, float &t_
     if constexpr (!SHADOW)
       if (n2a > best_sq * r2 * 2.0000305f) return false;
   }
+  nz_out = nz; arz_out = arz;
+  return true;
+}
+// ... and its end: the quotient, one eleven-instruction IEEE divide (DESIGN "Division fast path")
+template <bool STATS, bool SHADOW>
+__device__ __forceinline__ bool tri_zt(float nz, float arz, float &t_out, Cnt &cnt)
+{
+  const float t = qdiv(nz, arz);
+  if (!(t > kVerySmall)) return false;
+  RFX_CNT(SHADOW ? C_SH_TRI_T : C_TRI_T);
+  t_out = t;
+  return true;
+}
+// The (u, v) rows of g: axTrans rows 1-2 of (o - v0) and of the ray as one packed chain
+__device__ __forceinline__ void tri_rows(const TriGeo &g, v3 o, v3 ray, f2 &ao, f2 &ar)
+{
+  const float dx = o.x - g.v0x, dy = o.y - g.v0y, dz = o.z - g.v0z;
   const f2 c1{g.a11, g.a21}, c2{g.a12, g.a22}, c3{g.a13, g.a23};
+  ao = dx * c1 + dy * c2 + dz * c3;                         // (aox, aoy)
+  ar = ray.x * c1 + ray.y * c2 + ray.z * c3;                // (arx, ary)
+}
+// The uv stage, the triangle's own: is the crossing at t inside, and farther than DELTA (Triangle.cpp:91-104)?
+template <bool STATS, bool SHADOW>
+__device__ __forceinline__ bool tri_uv(f2 ao, f2 ar, v3 ray, float t, float &u_out, float &v_out, float &sq_out, Cnt &cnt)
+{
+  const f2 uv = ao + t * ar;                                  // (u, v)
+  const float u = uv.x, v = uv.y;
+  if (!(u >= 0.0f && v >= 0.0f && u + v < 1.0f)) return false;
+  RFX_CNT(SHADOW ? C_SH_TRI_IN : C_TRI_IN);
+  const float sq = sqlen(mul(ray, t));
+  if (!(sq > kDelta * kDelta)) return false;
+  u_out = u; v_out = v; sq_out = sq;
+  return true;
+}
+
+template <bool STATS, bool SHADOW, bool PRE = false>
+__device__ __forceinline__ bool tri_hit(const TriGeo &g, v3 o, v3 ray, float &t_out, float &u_out, float &v_out,
+                                        float &sq_out, Cnt &cnt, const RayConst &k, float best_sq = INFINITY)
+{
+  float nz, arz;
+  if (!tri_z<STATS, SHADOW>(g, o, ray, k, best_sq, cnt, nz, arz)) return false;
   f2 ao, ar;
   if constexpr (PRE && !STATS)
   {
-    ao = dx * c1 + dy * c2 + dz * c3;                         // (aox, aoy)
-    ar = ray.x * c1 + ray.y * c2 + ray.z * c3;                // (arx, ary)
+    tri_rows(g, o, ray, ao, ar);
     // exact reject of a plane crossing outside the triangle before the correctly rounded divide: with t' = nz rcp(arz)
     // (v_rcp_f32: 1 ulp), u' = aox + t' arx is within (|aox| + |t' arx|) 2^-19 of the reference's rounded u (t
     // within 2^-21 relative, three roundings); the margins are 4x that, so u' < -mu means u < 0, and u' + v' above
@@ -446,23 +488,51 @@ __device__ __forceinline__ bool tri_hit(const TriGeo &g, v3 o, v3 ray, float &t_
     const float mu = (fabsf(ao.x) + fabsf(pp.x)) * 0x1p-17f, mv = (fabsf(ao.y) + fabsf(pp.y)) * 0x1p-17f;
     if (uvp.x < -mu || uvp.y < -mv || uvp.x + uvp.y > 1.0f + (mu + mv) + 0x1p-20f) return false;
   }
-  const float t = qdiv(nz, arz);
-  if (!(t > kVerySmall)) return false;
-  RFX_CNT(SHADOW ? C_SH_TRI_T : C_TRI_T);
-  if constexpr (!(PRE && !STATS))
-  {
-    ao = dx * c1 + dy * c2 + dz * c3;                         // (aox, aoy)
-    ar = ray.x * c1 + ray.y * c2 + ray.z * c3;                // (arx, ary)
-  }
-  const f2 uv = ao + t * ar;                                  // (u, v)
-  const float u = uv.x, v = uv.y;
-  if (!(u >= 0.0f && v >= 0.0f && u + v < 1.0f)) return false;
-  RFX_CNT(SHADOW ? C_SH_TRI_IN : C_TRI_IN);
-  const float sq = sqlen(mul(ray, t));
-  if (!(sq > kDelta * kDelta)) return false;
-  t_out = t; u_out = u; v_out = v; sq_out = sq;
-  return true;
+  if (!tri_zt<STATS, SHADOW>(nz, arz, t_out, cnt)) return false;
+  if constexpr (!(PRE && !STATS)) tri_rows(g, o, ray, ao, ar);
+  return tri_uv<STATS, SHADOW>(ao, ar, ray, t_out, u_out, v_out, sq_out, cnt);
 }
+
+// Coplanar mates in the small-scene loops (DESIGN.md "Coplanar mates"): the triangle index of those loops is
+// wave-uniform, so the group's leader (TriGeo::pad[0], rfx_scene.cpp tri_mate_leaders) is a scalar.  The loop keeps the
+// last z stage -- per lane: did it pass, and t -- with its leader; the next kept triangle of the same group goes straight to
+// its own (u, v) rows: 9 dwords and the leader instead of 12, and no second divide.  The visits stay in index order; a
+// member whose leader was culled runs the z stage itself.  Closest hit: the kept z stage was decided against the best
+// distance before the leader's own test, and a stale bound only rejects less; tri_takes settles each member as before.
+// RFX_TRI_MATES: 0 off, 1 both loops, 2 closest hit only (the default), 3 shadow only.  tools/ab.py, C3 trace ms against
+// the parent's 0.5970: 0.5838 (1), 0.5843 (2), 0.5998 (3) -- the any-hit loop on its own loses (a lane leaves it at its
+// first occluder, and its own triangle fails the z stage's DELTA reject before the divide), so it keeps the per-triangle
+// test.  STATS kernels keep it too (their event counters are the reference's).
+#ifndef RFX_TRI_MATES
+#define RFX_TRI_MATES 2
+#endif
+template <bool STATS, bool SHADOW>
+struct TriMates {
+  static constexpr bool kOn = !STATS && (RFX_TRI_MATES == 1 || RFX_TRI_MATES == (SHADOW ? 3 : 2));
+  int lead = -1;
+  bool ok = false;
+  float t = 0.0f;
+  __device__ __forceinline__ bool hit(const TriGeo &g, v3 o, v3 ray, float &t_out, float &u_out, float &v_out,
+                                      float &sq_out, Cnt &cnt, const RayConst &k, float best_sq = INFINITY)
+  {
+    if constexpr (!kOn) return tri_hit<STATS, SHADOW>(g, o, ray, t_out, u_out, v_out, sq_out, cnt, k, best_sq);
+    else
+    {
+      const int l = __builtin_bit_cast(int, g.pad[0]);
+      if (l != lead)
+      {
+        lead = l;
+        float nz, arz;
+        ok = tri_z<STATS, SHADOW>(g, o, ray, k, best_sq, cnt, nz, arz) && tri_zt<STATS, SHADOW>(nz, arz, t, cnt);
+      }
+      if (!ok) return false;
+      f2 ao, ar;
+      tri_rows(g, o, ray, ao, ar);
+      t_out = t;
+      return tri_uv<STATS, SHADOW>(ao, ar, ray, t, u_out, v_out, sq_out, cnt);
+    }
+  }
+};
 
 // Plane::trace (Plane.cpp:36-73) up to its hit decision; on a hit returns t and |ray t|^2.  a = norm . ray,
 // t = norm . (pos - origin) / a, with tri_hit's two exact rejects before the division (opposite signs or a
@@ -1453,12 +1523,13 @@ __device__ __forceinline__ void closest_hit_small(const DevScene &S, v3 origin, 
   RFX_PROF_END(P_SPH);
   RFX_PROF_BEGIN(P_TRI);
   uint64_t tm = small_tris(om);
+  TriMates<STATS, false> zs;
   while (tm)
   {
     const int i = __builtin_ctzll(tm);
     tm &= tm - 1ull;
     float t, u, v, sq;
-    if (tri_hit<STATS, false>(S.tri_geo[i], origin, ray, t, u, v, sq, cnt, k, h.sq))
+    if (zs.hit(S.tri_geo[i], origin, ray, t, u, v, sq, cnt, k, h.sq))
     {
       RFX_CNT(C_TRI_D);
       const int obj = S.tri_shade[i].obj;
@@ -1503,6 +1574,7 @@ __device__ __forceinline__ bool occluded_small(const DevScene &S, v3 o, v3 ray, 
     }
   }
   uint64_t tm = small_tris(om);
+  TriMates<STATS, true> zs;
   while (tm)
   {
     const int i = __builtin_ctzll(tm);
@@ -1511,7 +1583,7 @@ __device__ __forceinline__ bool occluded_small(const DevScene &S, v3 o, v3 ray, 
     {
       if (i != skip_tri && tri_hit<STATS, true>(S.tri_geo[i], o, ray, t, u, v, sq, cnt, k)) return true;
     }
-    else if (tri_hit<STATS, true>(S.tri_geo[i], o, ray, t, u, v, sq, cnt, k) && i != skip_tri)
+    else if (zs.hit(S.tri_geo[i], o, ray, t, u, v, sq, cnt, k) && i != skip_tri)
       return true;
   }
   if constexpr (PLANES) return occluded_planes<STATS>(S, o, ray, k, skip_pln, cnt);

@@ -29,7 +29,7 @@ struct alignas(16) SphereGeo { float cx, cy, cz, sq_radius; };      // Sphere.cp
 struct alignas(32) SpherePair { float cx[2], cy[2], cz[2], r2[2]; };
 struct alignas(16) MatRec { float r, g, b, refl; };                 // Material.h:9-11 (transparency unused)
 // Triangle.cpp:11-21: v0 and axTrans (inverted) -- z row first (every test needs it), then the x and
-// y rows interleaved, (a11,a21), (a12,a22), (a13,a23), so (u, v) come out of one v_pk_* chain.
+// y rows interleaved, (a11,a21), (a12,a22), (a13,a23), so (u, v) come out of one v_pk_* chain.  pad[0] of a tri_geo record: its mate group's leader as int bits (rfx_scene.cpp tri_mate_leaders).
 struct alignas(16) TriGeo {
   float v0x, v0y, v0z, a31, a32, a33;
   float a11, a21, a12, a22, a13, a23;

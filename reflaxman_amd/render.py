@@ -189,6 +189,21 @@ class Scene:
         return {"nodes": nodes, "leaves": leaves, "leaf_size": leaf, "depth": depth, "boxes": boxes,
                 "children": children, "leaf_ids": ids, "residual": res}
 
+    def set_tri_mates(self, on: bool):
+        """Group coplanar triangles whose plane crossing is one value per ray (rfx.h rfx_scene_set_tri_mates): on by
+        default; off makes every triangle its own group.  No pixel changes; read by the next upload of the scene."""
+        check(_lib.load().rfx_scene_set_tri_mates(self._h, int(bool(on))), "Scene.set_tri_mates")
+        self._version += 1
+
+    def tri_mates(self, plane: bool = False):
+        """Each triangle's mate-group leader, the lowest triangle index of its group (rfx.h rfx_scene_tri_mates; host
+        only); plane: also the (triangles, 6) float32 rows v0 x y z, a31 a32 a33 that the grouping rule compares."""
+        L = _lib.load()
+        n = check(L.rfx_scene_tri_mates(self._h, None, None), "Scene.tri_mates")
+        leader, rows = np.zeros(n, np.int32), np.zeros((n, 6), np.float32)
+        check(L.rfx_scene_tri_mates(self._h, leader.ctypes.data_as(_lib._i32p), _lib.fptr(rows)), "Scene.tri_mates")
+        return (leader, rows) if plane else leader
+
     def addPlane(self, pos: Vector3, norm: Vector3, material: Material) -> Plane:
         """Plane(pos, norm, material) (Plane.cpp:9-14) as a scene object, traced by Plane::trace (Plane.cpp:36-73)."""
         obj = check(_lib.load().rfx_scene_add_plane(self._h, farr(Vector3(*pos)), farr(Vector3(*norm)), material.type,

@@ -33,11 +33,13 @@ def main():
                     help="rfx_renderer_set_prim_masks mode (0: no per-view masks, what a moving camera renders with)")
     ap.add_argument("--exact", type=int, default=None,
                     help="rfx_renderer_set_prim_exact setting (0: the conservative per-view masks)")
+    ap.add_argument("--mates", type=int, default=None,
+                    help="rfx_scene_set_tri_mates setting (0: every triangle its own mate group)")
     a = ap.parse_args()
     path = os.path.join(_build.LIBDIR, "diag", a.lib)
     scene = a.scene
     r = ab.Runner("prof", path, scenes.get_scene(scene), a.width, a.height, a.depth, 1350490027, regroup=a.regroup,
-                  prim=a.prim, exact=a.exact)
+                  prim=a.prim, exact=a.exact, mates=a.mates)
     r.render(2)
     assert r.L.rfx_synchronize(r.r) == 0
     buf = (C.c_ulonglong * 16)()
@@ -60,7 +62,7 @@ def main():
         cull["closest_large"] = {"bundles": v[0], "usable": round(v[1] / n, 3), "live_lanes": round(v[2] / n, 1),
                                  "kept_chunks": round(v[3] / n, 2), "kept_spheres": round(v[4] / n, 1),
                                  "pair_tests": round(v[5] / n, 1)}
-    print(json.dumps({"scene": scene, "lib": os.path.basename(path), "prim_masks": a.prim, "prim_exact": a.exact, "cycles": {k: int(v) for k, v in zip(REGIONS, buf[:8])},
+    print(json.dumps({"scene": scene, "lib": os.path.basename(path), "prim_masks": a.prim, "prim_exact": a.exact, "tri_mates": a.mates, "cycles": {k: int(v) for k, v in zip(REGIONS, buf[:8])},
                       "wave_executions": {k: int(v) for k, v in zip(REGIONS, buf[8:])},
                       "share_of_trace": {k: round(v / tot, 4) for k, v in zip(REGIONS, buf[:8])},
                       "cull": cull}))
