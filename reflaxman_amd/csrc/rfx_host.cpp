@@ -16,78 +16,22 @@ using namespace rfx;
 extern "C" int rfx_abi_version(void) { return RFX_ABI_VERSION; }
 
 // ============================================================== renderer
-#ifndef RFX_TILE_ORDER_DEFAULT
-#define RFX_TILE_ORDER_DEFAULT 1
-#endif
-#ifndef RFX_TILE_ORDER_MIN_TILES
-// 8x8 wave tiles: C3 (3840x2160) has 129,600, C2 (1920x1080) 32,400, a C4 rank's strips at N = 8 65,280 (their
-// trace 0.41 ms unsorted vs 0.34 at N = 4 per eighth of the frame, tools/root_overhead.py)
-#define RFX_TILE_ORDER_MIN_TILES 49152
-#endif
-// per-view masks of SSAA frames / chunk lists of large scenes: measured slower, compiled out (rfx_trace.h)
-#ifndef RFX_PRIM_SSAA
-#define RFX_PRIM_SSAA 0
-#endif
-#ifndef RFX_PRIM_LANES
-#define RFX_PRIM_LANES 1  // masks of kModeSsaaLanes frames (the lanes' own small pixel blocks)
-#endif
-#ifndef RFX_PRIM_CHUNKS
-#define RFX_PRIM_CHUNKS 1  // closest-hit masks of kModeSsaaChunks frames (a pixel's sample rectangle), every launch
-#endif
-#ifndef RFX_PRIM_LARGE
-#define RFX_PRIM_LARGE 0
-#endif
-#ifndef RFX_ONE_LIGHT
-#define RFX_ONE_LIGHT 1  // one-light kernel instantiations (rfx_trace.h kCfgOneLight; -DRFX_ONE_LIGHT=0 turns them off)
-#endif
-#ifndef RFX_BOUNCE_GROUPS_PER_CU
-#define RFX_BOUNCE_GROUPS_PER_CU 14
-#endif
-
-#ifndef RFX_QUEUE_SORT
-// regrouped frames: the bounce kernel takes the parked traces bucket by bucket (1) or in park order (0).  tools/ab.py,
-// C5 trace + bounce: park after 3 sorted 3.48 vs 3.40 ms unsorted (+2.3%); after 2: 3.53 vs 3.69 (-4.2%, still
-// above park-3 unsorted).  Park order keeps a tile's survivors together, which a coarse cell key cannot beat.
-#define RFX_QUEUE_SORT 0
-#endif
-#ifndef RFX_PARK_AFTER
-#define RFX_PARK_AFTER 2  // large-scene plain frames: segments before a live trace is parked for the bounce kernel
-#endif
+// RFX_TILE_ORDER_MIN_TILES counts 8x8 wave tiles: C3 (3840x2160) has 129,600, C2 (1920x1080) 32,400, a C4 rank's strips
+// at N = 8 65,280 (their trace 0.41 ms unsorted vs 0.34 at N = 4 per eighth of the frame, tools/root_overhead.py)
+// RFX_QUEUE_SORT: regrouped frames: the bounce kernel takes the parked traces bucket by bucket (1) or in park order (0).
+// tools/ab.py, C5 trace + bounce: park after 3 sorted 3.48 vs 3.40 ms unsorted (+2.3%); after 2: 3.53 vs 3.69 (-4.2%,
+// still above park-3 unsorted).  Park order keeps a tile's survivors together, which a coarse cell key cannot beat.
 // The tile sort: on the trace launch's own stream (RFX_TILE_SORT_MAIN=0: on a side stream beside the next frame's RNG
 // pre-pass, joined by an event pair) every RFX_TILE_SORT_EVERY-th launch.  Trace time against raster order (tools/ab.py,
 // C3): every launch -7.5%, every 4th -9.4%, every 16th -9.8%.  The side stream hid the sort but not its events: a kernel
 // trace shows ~20 us between two traces on a sorting frame beyond a plain one (fork before the count, join before the
 // trace).  Frame ms, interleaved A/B (profiles/r06/ab/*_tile_sort_r6q.jsonl): C3 every 4th beside 0.6556, on the stream
 // 0.6526, every 16th beside 0.6513, every 16th on the stream 0.6485 (-1.1%); C2 d4 -0.9%, the 4x4 screenshot -0.4%.
-#ifndef RFX_TILE_SORT_MAIN
-#define RFX_TILE_SORT_MAIN 1
-#endif
-#ifndef RFX_TILE_SORT_EVERY
-#define RFX_TILE_SORT_EVERY 16
-#endif
-#ifndef RFX_LAUNCH_TRACES
-#define RFX_LAUNCH_TRACES (1ull << 30)  // traces per launch of a split frame (rfx_renderer_set_launch_traces)
-#endif
-#ifndef RFX_SPLIT_STREAMS
-#define RFX_SPLIT_STREAMS 2  // split frames: spans alternate between two streams (1: one stream, no overlap)
-#endif
-#ifndef RFX_RNG_SEQ
-#define RFX_RNG_SEQ 1  // one-device unsplit frames take their randDirs from the cycle table (0: the count / emit kernels)
-#endif
-#ifndef RFX_RNG_SEQ_SPLIT
-#define RFX_RNG_SEQ_SPLIT 1  // the spans of split frames take the table too (0: the count / scan / emit kernels)
-#endif
-#ifndef RFX_RNG_SEQ_MIN_BLOCKS
-#define RFX_RNG_SEQ_MIN_BLOCKS 0  // launches of fewer pre-pass blocks keep rng_fused
-#endif
 constexpr uint64_t kMaxLaunchTraces = 1ull << 31;  // the band scan's 32-bit offsets (rfx_kernels.hip rng_band_range)
-#ifndef RFX_SCAN_EMIT_BLOCKS
-// one-device emits of more RNG blocks than this scan the counts first (rng_band_range) instead of summing them per
-// block (rng_emit: O(nblk^2) reads); C3 has 4,066 blocks, the 4x4 screenshot frame 16,219.  Re-checked with the
-// multi-workgroup tile scan (round 6, profiles/r06/ab/*_scan_emit_threshold_r6x.jsonl): a threshold of 4,096 makes the C4
-// and screenshot pre-passes 0.093 -> 0.104 ms, so the per-block sums stay up to 16,384 blocks
-#define RFX_SCAN_EMIT_BLOCKS 16384
-#endif
+// RFX_SCAN_EMIT_BLOCKS: one-device emits of more RNG blocks than this scan the counts first (rng_band_range) instead of
+// summing them per block (rng_emit: O(nblk^2) reads); C3 has 4,066 blocks, the 4x4 screenshot frame 16,219.  Re-checked
+// with the multi-workgroup tile scan (round 6, profiles/r06/ab/*_scan_emit_threshold_r6x.jsonl): a threshold of 4,096
+// makes the C4 and screenshot pre-passes 0.093 -> 0.104 ms, so the per-block sums stay up to 16,384 blocks
 
 static int timing_event(rfx_renderer *r, hipStream_t st)
 {
@@ -215,7 +159,7 @@ extern "C" void rfx_renderer_destroy(rfx_renderer *r)
 
 extern "C" int rfx_build_options(void)
 {
-  return (RFX_PRIM_LARGE ? RFX_BUILD_PRIM_LARGE : 0) | (RFX_PRIM_SSAA ? RFX_BUILD_PRIM_SSAA : 0) |
+  return (RFX_PRIM_SSAA ? RFX_BUILD_PRIM_SSAA : 0) |  // (bit 0, RFX_BUILD_PRIM_LARGE: reserved, always 0)
          (RFX_PRIM_LANES ? RFX_BUILD_PRIM_LANES : 0) | (RFX_ONE_LIGHT ? RFX_BUILD_ONE_LIGHT : 0) |
          (RFX_BVH_LEAF_PAIRS << 8);
 }
@@ -664,12 +608,6 @@ static int emit_frame(rfx_renderer *r, FramePlan &pl, const uint32_t *d_counts, 
 // workgroup on one word) serialises the launch's start in proportion to the blocks, so it pays only on small launches
 // (interleaved A/B, frame ms, one-pass / two-kernel, profiles/r06/ab/prepass_limit_*_r6e.jsonl): 640x480 (166 blocks)
 // 0.0552 / 0.0565, 960x540 (269) 0.0657 / 0.0643, 1280x720 (466) 0.0841 / 0.0803, 1920x1080 (1,013) 0.0812 / 0.0679.
-#ifndef RFX_RNG_FUSED
-#define RFX_RNG_FUSED 1
-#endif
-#ifndef RFX_RNG_FUSED_MAX_BLOCKS
-#define RFX_RNG_FUSED_MAX_BLOCKS 256
-#endif
 static bool fused_prepass(const FramePlan &pl, uint64_t nblk)
 {
   return RFX_RNG_FUSED && !pl.band && pl.P.nranks <= 1 && nblk <= (uint64_t)RFX_RNG_FUSED_MAX_BLOCKS;
@@ -764,9 +702,8 @@ static int setup_regroup_queue(rfx_renderer *r, FramePlan &pl, int park_after, b
   return RFX_OK;
 }
 
-// 2: primary-bundle cull masks: small scenes, plain and SSAA frames (not block previews), culling launches; large scenes,
-// plain frames: the primary bundles' chunk lists.  Recomputed only when the camera, the frame geometry, the sampling
-// or the scene changed (the bench's frames all reuse one set)
+// 2: primary-bundle cull masks: small scenes, plain and SSAA frames (not block previews), culling launches.  Recomputed
+// only when the camera, the frame geometry, the sampling or the scene changed (the bench's frames all reuse one set)
 // The chunk mode (sampleNum > 8: a wave per pixel) takes closest-hit masks only, over each pixel's sample rectangle:
 // one cheap cull per pixel that every chunk of its samples reuses, so they are built for every view and every span
 // of a split frame (into the span's stream side's buffer: the spans of the two streams overlap).
@@ -784,9 +721,7 @@ static int select_view_masks(rfx_renderer *r, FramePlan &pl, bool small, bool pl
     P.prim_mask = mask;
     P.prim_shadow = 0;
   }
-  else if (((small && (plain || (RFX_PRIM_LANES && (trace_lanes(P) || chunks)) || (RFX_PRIM_SSAA && P.ss >= 1)) &&
-             !park) ||
-            (RFX_PRIM_LARGE && !small && plain)) &&
+  else if (small && (plain || (RFX_PRIM_LANES && (trace_lanes(P) || chunks)) || (RFX_PRIM_SSAA && P.ss >= 1)) && !park &&
            !stats && P.grid_rows && r->prim_mode && !pl.split)
   {
     struct Key { float cam[15]; uint32_t W, H, grid_rows, row0, row_block, rank, nranks; int32_t depth, ss, additive;
@@ -799,7 +734,7 @@ static int select_view_masks(rfx_renderer *r, FramePlan &pl, bool small, bool pl
     k.nranks = P.nranks; k.depth = P.depth > 0 ? 1 : 0; k.p_begin = P.p_begin; k.p_end = P.p_end; k.gen = r->scene_gen;
     k.ss = P.ss; k.additive = P.additive ? 1 : 0;
     std::vector<uint8_t> kb((const uint8_t *)&k, (const uint8_t *)&k + sizeof(k));
-    if ((rc = r->prim_mask.reserve((size_t)trace_tiles(P) * (small ? kPrimStride : kPrimLargeStride))) < 0) return rc;
+    if ((rc = r->prim_mask.reserve((size_t)trace_tiles(P) * kPrimStride)) < 0) return rc;
     if (rc)  // a new array holds no view's masks
     {
       r->prim_key.clear();
@@ -816,7 +751,7 @@ static int select_view_masks(rfx_renderer *r, FramePlan &pl, bool small, bool pl
       {
         HIP_CHECK(launch_prim_cull(r->dev, P, r->prim_mask, r->prim_exact != 0, st));
         r->prim_key = kb;
-        r->prim_words = (size_t)trace_tiles(P) * (small ? kPrimStride : kPrimLargeStride);
+        r->prim_words = (size_t)trace_tiles(P) * kPrimStride;
         r->prim_on = st;
       }
     }

@@ -208,9 +208,6 @@ __device__ __forceinline__ bool float_accept(uint32_t s1, uint32_t s2, uint32_t 
 // |N - 32767^2| <= kSphereShell the integer answer is the float one.  A thread with a triple inside the shell (about 3
 // threads in 10^5) redoes its 16 in float.  Per draw: a bit-field extract and two 24-bit multiply-adds, not eight
 // operations.
-#ifndef RFX_RNG_INT_ACCEPT
-#define RFX_RNG_INT_ACCEPT 1
-#endif
 constexpr uint32_t kSphereN = 32767u * 32767u;
 constexpr uint32_t kSphereShell = 1024u;
 
@@ -679,16 +676,7 @@ __global__ __launch_bounds__(kRngBlock) void rng_emit_band(const uint32_t *seed,
 // path a correct launch takes: past kLookbackSpins polls the block recomputes its offset from the random stream itself
 // (below), so even then the frame's randDirs are exact and no later call is left to report a wrong frame.
 // RFX_RNG_TICKET=0 keeps the blockIdx.x order (timing builds only: it relies on in-order dispatch).
-#ifndef RFX_RNG_TICKET
-#define RFX_RNG_TICKET 1
-#endif
-#ifndef RFX_LOOKBACK_SLEEP
-#define RFX_LOOKBACK_SLEEP 1  // s_sleep between polls of a not yet published status word (units of 64 cycles)
-#endif
 constexpr uint64_t kStatAgg = 1ull << 34, kStatPre = 2ull << 34, kStatVal = (1ull << 34) - 1;
-#ifndef RFX_LOOKBACK_SPINS
-#define RFX_LOOKBACK_SPINS (1u << 22)  // 0: every wait gives up at once (a timing build that exercises the fallback)
-#endif
 constexpr uint32_t kLookbackSpins = RFX_LOOKBACK_SPINS;
 
 // Relaxed device-scope accesses: a status word carries its own value, and no other data is handed over through it, so
@@ -1314,9 +1302,7 @@ hipError_t launch_rng_finish(const uint32_t *d_seed, const uint32_t *d_jump, uin
 // the band partition's emit: traces [lo, hi) (and the frame's last trace's stream state); scratch: nblk offsets,
 // 3 range words and one word per tile of kScanTileCounts blocks (d_tile_sum; null: the one-workgroup scan).  Also the one-device emit of launches with many blocks (lo = 0, hi = traces, the count kernel's
 // accept flags in d_masks): rng_emit's per-block prefix sums cost O(nblk^2) reads, this scan O(nblk).
-#ifndef RFX_SCAN_TILES
-#define RFX_SCAN_TILES 2  // launches of at least this many tiles of kScanTileCounts blocks scan in many workgroups (0: never)
-#endif
+// RFX_SCAN_TILES: launches of at least this many tiles of kScanTileCounts blocks scan in many workgroups (0: never)
 hipError_t launch_rng_finish_band(const uint32_t *d_seed, const uint32_t *d_jump, uint32_t *d_next_seed,
                                   const uint32_t *d_blk_cnt, const uint16_t *d_masks, uint64_t nblk, uint64_t traces,
                                   uint32_t *d_rd_state, int *d_err, uint64_t lo, uint64_t hi, uint64_t *d_off,
@@ -1476,10 +1462,6 @@ hipError_t launch_kat_powf_cube(uint32_t first, uint32_t n, unsigned long long *
   return hipGetLastError();
 }
 
-#ifndef RFX_NOCULL_MAX_TILES
-#define RFX_NOCULL_MAX_TILES 0
-#endif
-
 // the mode of a trace launch (rfx_trace.h TraceMode)
 static int trace_mode(const FrameParams &P)
 {
@@ -1521,16 +1503,15 @@ bool trace_chunks(const FrameParams &P)
   return trace_mode(P) == kModeSsaaChunks;
 }
 
-// the per-view masks of a small scene's plain or SSAA frame (prim_cull_kernel, kPrimStride words per wave tile), or
-// a large scene's chunk lists (prim_cull_large_kernel, kPrimLargeStride words)
+// the per-view masks of a small scene's plain or SSAA frame (prim_cull_kernel, kPrimStride words per wave tile); a
+// large scene has none (rfx_host.cpp select_view_masks never asks)
 // narrow: prim_cull_kernel's exact rules on top of the conservative words (rfx_renderer_set_prim_exact)
 hipError_t launch_prim_cull(const DevScene &S, const FrameParams &P, uint64_t *masks, bool narrow, hipStream_t st)
 {
   const int nw = narrow ? 1 : 0;
   const dim3 grid = trace_grid(P);
-  if (!(S.n_sph <= 32 && S.n_tri <= 32))  // large scenes: the primary bundles' chunk lists
-    hipLaunchKernelGGL(prim_cull_large_kernel<0>, grid, dim3(kWgThreads), 0, st, S, P, masks);
-  else if (trace_lanes(P) || trace_chunks(P))
+  if (!(S.n_sph <= 32 && S.n_tri <= 32)) return hipErrorInvalidValue;
+  if (trace_lanes(P) || trace_chunks(P))
   {
     if (S.n_pln > 0)
       hipLaunchKernelGGL((prim_cull_kernel<true, true>), grid, dim3(kWgThreads), 0, st, S, P, masks, nw);

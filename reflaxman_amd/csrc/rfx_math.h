@@ -5,6 +5,8 @@
 //
 // Citations: /root/reference/src/common/<file>:<line>.
 #pragma once
+#include "rfx_config.h"
+
 #include <stdint.h>
 #include <string.h>
 
@@ -59,9 +61,7 @@ RFX_HD float sqrt_rn(float x)
 // part (r, e, r') is shared by every quotient over one divisor (div_prep); a quotient outside the range is recomputed
 // with '/'.  tests/test_div_guard.py replays the range argument in float32; rfx_kat_div checks the device path against
 // IEEE '/' on 2^27+ operand pairs, both edges of every bound included.
-#ifndef RFX_DIV_FAST
-#define RFX_DIV_FAST 1  // 0: every quotient as the compiler lowers '/'; 2: no guard (timing builds only)
-#endif
+// RFX_DIV_FAST 0: every quotient as the compiler lowers '/'; 2: no guard (timing builds only)
 // the divisor and its refined reciprocal -- NaN when the divisor is outside [2^-40, 2^100], so that every fast quotient
 // by it is NaN and fails the quotient's range test (one register for the guard's divisor half, not two)
 struct DivRcp { float b, r; };
@@ -105,9 +105,6 @@ RFX_HD float div_by(float a, const DivRcp &d)
 RFX_HD float div_rn(float a, float b) { return div_by(a, div_prep(b)); }
 // a lone quotient (no divisor to share): the fast path saves three instructions and pays two compares and a branch for
 // it, so it is a build option (RFX_DIV_SINGLE, tools/ab.py)
-#ifndef RFX_DIV_SINGLE
-#define RFX_DIV_SINGLE 0
-#endif
 RFX_HD float qdiv(float a, float b)
 {
 #if RFX_DIV_SINGLE

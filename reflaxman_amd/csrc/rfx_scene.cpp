@@ -419,17 +419,11 @@ extern "C" uint32_t rfx_strip_row_to_y(uint32_t r, uint32_t rb, uint32_t rank, u
 }
 
 // ============================================================== hierarchies
-#ifndef RFX_TRI_BVH_AUTO_MIN
-// rfx_renderer_set_tri_accel(-1): the triangle count from which a non-small scene gets the triangle BVH (DESIGN.md
-// "Triangle BVH": the smallest measured soup size at which the tree wins)
-#define RFX_TRI_BVH_AUTO_MIN 128
-#endif
-#ifndef RFX_TRI_BVH_NARROW_MIN
-// the triangle count from which narrow bundles (a tile's primary rays) walk the triangle BVH too instead of culling
-// every triangle's bound for the wave: never by default -- the bundle cull won on every soup from 64 to 100,000
-// triangles (0.8% to 15% less trace time) and lost 1% on a 2,560-triangle height field (DESIGN.md "Triangle BVH")
-#define RFX_TRI_BVH_NARROW_MIN (1 << 30)
-#endif
+// RFX_TRI_BVH_AUTO_MIN: rfx_renderer_set_tri_accel(-1): the triangle count from which a non-small scene gets the
+// triangle BVH (DESIGN.md "Triangle BVH": the smallest measured soup size at which the tree wins)
+// RFX_TRI_BVH_NARROW_MIN: the triangle count from which narrow bundles (a tile's primary rays) walk the triangle BVH too
+// instead of culling every triangle's bound for the wave: never by default -- the bundle cull won on every soup from 64
+// to 100,000 triangles (0.8% to 15% less trace time) and lost 1% on a 2,560-triangle height field (DESIGN.md "Triangle BVH")
 // Device order of a large scene's spheres: recursive median splits of the centres along their longest axis,
 // left parts of even size, so pairs (2j, 2j + 1) are neighbours and every aligned run of 2^k spheres is a
 // compact cluster (the 64-sphere chunks of the bundle cull, the leaves of the pair BVH).
@@ -530,7 +524,6 @@ int build_pair_bvh(std::vector<BvhNode> &nodes, std::vector<uint32_t> &pairs, si
     double l[3] = {INFINITY, INFINITY, INFINITY}, h[3] = {-INFINITY, -INFINITY, -INFINITY};
     for (size_t i = range[c][0]; i < range[c][1]; ++i)
       for (int k = 0; k < 3; ++k) { l[k] = fmin(l[k], box[pairs[i]].lo[k]); h[k] = fmax(h[k], box[pairs[i]].hi[k]); }
-#if RFX_BVH_PREWIDE
     if (widen)  // (false: rfx_scene_tri_bvh_dump, the boxes as built)
     {
       // the box grown by the node part of the kernel's margin, kCullRel mt[c] (rfx_trace.h kCullRel = 2e-3), from the
@@ -545,7 +538,6 @@ int build_pair_bvh(std::vector<BvhNode> &nodes, std::vector<uint32_t> &pairs, si
       const double w = 2e-3 * (double)nextafterf((float)((sqrt(cd) + sqrt(hd)) * 1.0001), INFINITY) * (1.0 + 1e-6);
       for (int k = 0; k < 3; ++k) { l[k] -= w; h[k] += w; }
     }
-#endif
     // round outwards to float
     n.lx[c] = nextafterf((float)l[0], -INFINITY); n.ly[c] = nextafterf((float)l[1], -INFINITY);
     n.lz[c] = nextafterf((float)l[2], -INFINITY);

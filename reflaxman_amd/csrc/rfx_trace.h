@@ -206,15 +206,9 @@ __device__ __forceinline__ void stage_small_scene(const DevScene &S)
 // 7 waves per SIMD (<= 72 VGPRs, a few spills): the kernel is VALU-issue bound; more waves hide the
 // scene-load and texel latencies better than spills cost (tools/ab.py, C3 trace kernel: 6 -> 7 -2.6%;
 // 8 waves / 64 VGPRs spill enough to lose 4-7%)
-#ifndef RFX_WAVES_PER_EU
-#define RFX_WAVES_PER_EU 7
-#endif
 // waves per workgroup (1, 2 or 4): a wave is an 8x8 pixel tile, a workgroup 8x8 / 16x8 / 16x16 pixels.
 // Two: a workgroup's slots free when its slower wave ends, and the per-workgroup LDS staging stays cheap
 // (tools/ab.py, C3 trace kernel: 4 -> 2 waves -2.5%, 1 wave +3.6%)
-#ifndef RFX_WG_WAVES
-#define RFX_WG_WAVES 2
-#endif
 constexpr uint32_t kWgWaves = RFX_WG_WAVES, kWgThreads = 64 * kWgWaves;
 constexpr uint32_t kTileWavesX = kWgWaves >= 2 ? 2 : 1, kTileWavesY = kWgWaves / kTileWavesX;
 constexpr uint32_t kTileW = 8 * kTileWavesX, kTileH = 8 * kTileWavesY;
@@ -355,12 +349,8 @@ __device__ __forceinline__ bool pair_may_hit(f2 b, f2 d)
 // decision without the square root (rfx_math.h).
 // SEL (large-scene loops): one branch, the rest computed and decided without branching.  tools/ab.py, trace ms: C5
 // 3.143 -> 3.067 (-2.4%); the small-scene kernel +9% with it (its SGPR spills 23 -> 51), so the small loops keep the
-// early outs.
-// The large scenes' sphere loops (SEL) keep '/': the shared reciprocal of 2a, live across the BVH walk, raised the C5
-// trace kernel's VGPR spills from 15 to 36 and its time by 5.9% (tools/ab.py, profiles/r06/ab/c5_div_sel_prefetch_r6c.jsonl)
-#ifndef RFX_DIV_SEL
-#define RFX_DIV_SEL 0
-#endif
+// early outs.  The SEL tail divides with '/': the shared reciprocal of 2a, live across the BVH walk, raised the C5 trace
+// kernel's VGPR spills from 15 to 36 and its time by 5.9% (tools/ab.py, profiles/r06/ab/c5_div_sel_prefetch_r6c.jsonl)
 template <bool STATS, bool SHADOW, bool SEL = false>
 __device__ __forceinline__ bool sphere_tail(float b, float d, v3 ray, const RayConst &k, float &t_out,
                                             float &sq_out, Cnt &cnt)
@@ -371,8 +361,7 @@ __device__ __forceinline__ bool sphere_tail(float b, float d, v3 ray, const RayC
   if constexpr (!STATS && SEL)
   {
     if (!(d >= 0.0f && k.a_ok && b < 0.0f)) return false;
-    // (RFX_DIV_SEL 0: the large scenes' BVH loops divide with '/', and the shared reciprocal is not live across the walk)
-    const float t = RFX_DIV_SEL ? div_by(-b - sqrt_rn(d), k.a2d) : (-b - sqrt_rn(d)) / k.a2;
+    const float t = (-b - sqrt_rn(d)) / k.a2;
     const float sq = sqlen(mul(ray, t));
     t_out = t;
     sq_out = sq;
@@ -503,9 +492,6 @@ __device__ __forceinline__ bool tri_hit(const TriGeo &g, v3 o, v3 ray, float &t_
 // the parent's 0.5970: 0.5838 (1), 0.5843 (2), 0.5998 (3) -- the any-hit loop on its own loses (a lane leaves it at its
 // first occluder, and its own triangle fails the z stage's DELTA reject before the divide), so it keeps the per-triangle
 // test.  STATS kernels keep it too (their event counters are the reference's).
-#ifndef RFX_TRI_MATES
-#define RFX_TRI_MATES 2
-#endif
 template <bool STATS, bool SHADOW>
 struct TriMates {
   static constexpr bool kOn = !STATS && (RFX_TRI_MATES == 1 || RFX_TRI_MATES == (SHADOW ? 3 : 2));
@@ -572,24 +558,9 @@ constexpr float kCullRel = 2e-3f;
 
 // per-view primary masks (prim_cull_kernel): per wave tile, the closest hit's mask and the shadow masks of the
 // first kPrimLights lights (kPrimStride words, rfx_types.h)
-// Per-view masks of SSAA / additive frames (RFX_PRIM_SSAA) and per-view chunk lists of large scenes (RFX_PRIM_LARGE):
-// built, parity-tested and measured slower in round 4 (the screenshot frame +4.3%, C5 +3.3%; interleaved A/B,
-// profiles/r04/ab/), so compiled out by default
-#ifndef RFX_PRIM_SSAA
-#define RFX_PRIM_SSAA 0
-#endif
-// per-view masks of kModeSsaaLanes frames (sampleNum 1 jittered, 2, 4, 8: the wave's own bw x bw pixels)
-#ifndef RFX_PRIM_LANES
-#define RFX_PRIM_LANES 1
-#endif
-#ifndef RFX_PRIM_LARGE
-#define RFX_PRIM_LARGE 0
-#endif
-// Large scenes (prim_cull_large_kernel): per wave tile, the chunk cull of its primary bundle -- [0] the number of kept
-// 64-sphere chunks (at most kPrimLargeChunks; kPrimLargeNone: no list, the tile culls per launch), [1] the triangle mask,
-// [2] the chunk mask (scenes of at most 64 chunks), [4..] the kept chunks' sphere masks in chunk order (kPrimLargeStride
-// words, rfx_types.h)
-constexpr uint64_t kPrimLargeNone = ~0ull;
+// Per-view masks of SSAA / additive frames (RFX_PRIM_SSAA): built, parity-tested and measured slower in round 4 (the
+// screenshot frame +4.3%; interleaved A/B, profiles/r04/ab/), so compiled out by default.  RFX_PRIM_LANES: per-view masks
+// of kModeSsaaLanes frames (sampleNum 1 jittered, 2, 4, 8: the wave's own bw x bw pixels)
 
 struct Bundle {
   float cx, cy, cz, rw;
@@ -620,9 +591,6 @@ __device__ __forceinline__ float wave_max_nonneg(float v)
 
 // Sums of products in the bundle and cull bounds (RFX_CULL_FMA): these are conservative decisions with margins far above
 // a rounding, not reference values, so they may fuse their multiply-adds.
-#ifndef RFX_CULL_FMA
-#define RFX_CULL_FMA 1
-#endif
 __device__ __forceinline__ float cdot(float ax, float ay, float az, float bx, float by, float bz)
 {
 #if RFX_CULL_FMA
@@ -656,59 +624,6 @@ __device__ __forceinline__ Bundle make_bundle(v3 o, v3 d, bool live)
   B.ok = __ballot(bad) == 0 && B.cosa > 0.1f && B.rw <= 1.0e15f;
   return B;
 }
-
-#ifdef RFX_HALF_BUNDLES
-// make_bundle for each half of the wave (lanes 0-31, 32-63): the DPP scan's row_bcast:15 step leaves each half's maximum
-// in its lane 31 / 63.  A half without a live lane gets ok = false (its lanes test nothing).
-__device__ __forceinline__ void make_bundle_halves(v3 o, v3 d, bool live, Bundle (&H)[2])
-{
-  const uint64_t lm = __ballot(live);
-  const bool hi = (threadIdx.x & 63u) >= 32u;
-  float ax[2], ay[2], az[2], cx[2], cy[2], cz[2];
-#pragma unroll
-  for (int h = 0; h < 2; ++h)
-  {
-    const uint64_t hm = lm & (h ? 0xFFFFFFFF00000000ull : 0xFFFFFFFFull);
-    const int ref = hm ? __ffsll((long long)hm) - 1 : 0;
-    cx[h] = lane_bcast(o.x, ref); cy[h] = lane_bcast(o.y, ref); cz[h] = lane_bcast(o.z, ref);
-    const float dx = lane_bcast(d.x, ref), dy = lane_bcast(d.y, ref), dz = lane_bcast(d.z, ref);
-    const float inv = __builtin_amdgcn_rsqf(dx * dx + dy * dy + dz * dz);
-    ax[h] = dx * inv; ay[h] = dy * inv; az[h] = dz * inv;
-  }
-  const float ex = o.x - (hi ? cx[1] : cx[0]), ey = o.y - (hi ? cy[1] : cy[0]), ez = o.z - (hi ? cz[1] : cz[0]);
-  const float e2 = ex * ex + ey * ey + ez * ez;
-  const float cosl = (d.x * (hi ? ax[1] : ax[0]) + d.y * (hi ? ay[1] : ay[0]) + d.z * (hi ? az[1] : az[0])) *
-                     __builtin_amdgcn_rsqf(d.x * d.x + d.y * d.y + d.z * d.z);
-  const float dev = 1.0f - cosl;
-  const bool bad = live && !(e2 <= 1.0e30f && dev >= -0.5f && dev <= 2.5f);
-  const uint64_t badm = __ballot(bad);
-  const auto half_max = [](float v, float &lo, float &hi_) {
-    uint32_t u = __float_as_uint(v);
-    u = max(u, (uint32_t)__builtin_amdgcn_update_dpp(0, (int)u, 0x111, 0xf, 0xf, false));  // row_shr:1
-    u = max(u, (uint32_t)__builtin_amdgcn_update_dpp(0, (int)u, 0x112, 0xf, 0xf, false));  // row_shr:2
-    u = max(u, (uint32_t)__builtin_amdgcn_update_dpp(0, (int)u, 0x114, 0xf, 0xf, false));  // row_shr:4
-    u = max(u, (uint32_t)__builtin_amdgcn_update_dpp(0, (int)u, 0x118, 0xf, 0xf, false));  // row_shr:8
-    u = max(u, (uint32_t)__builtin_amdgcn_update_dpp(0, (int)u, 0x142, 0xa, 0xf, false));  // row_bcast:15
-    lo = __int_as_float(__builtin_amdgcn_readlane((int)u, 31));
-    hi_ = __int_as_float(__builtin_amdgcn_readlane((int)u, 63));
-  };
-  float e2m[2], devm[2];
-  half_max(live ? e2 : 0.0f, e2m[0], e2m[1]);
-  half_max(live ? fmaxf(dev, 0.0f) : 0.0f, devm[0], devm[1]);
-#pragma unroll
-  for (int h = 0; h < 2; ++h)
-  {
-    Bundle &B = H[h];
-    B.cx = cx[h]; B.cy = cy[h]; B.cz = cz[h];
-    B.ax = ax[h]; B.ay = ay[h]; B.az = az[h];
-    B.rw = __builtin_amdgcn_sqrtf(e2m[h]) * 1.0001f;
-    B.cosa = 1.0f - devm[h] - 4e-6f;                                             // approximate cosines: widen
-    B.sina = __builtin_amdgcn_sqrtf(fmaxf(1.0f - B.cosa * B.cosa, 0.0f) + 1e-7f) * 1.001f;
-    const uint64_t hm = h ? 0xFFFFFFFF00000000ull : 0xFFFFFFFFull;
-    B.ok = (lm & hm) != 0 && (badm & hm) == 0 && B.cosa > 0.1f && B.rw <= 1.0e15f;
-  }
-}
-#endif
 
 // Bundle of every ray (o, d + rd R) with |rd| <= 1 of the `live` lanes (the shadow rays toward a light of radius R
 // for any randDir, Scene.cpp:128-129): make_bundle's cone widened per lane by the angular radius asin(R / |d|) of
@@ -933,9 +848,6 @@ __device__ __forceinline__ bool tri_takes(float sq, float best_sq, int obj, int 
 // the entry distance into their widened box) cannot win or tie and is skipped too.  Leaves run the exact
 // pair test with the (distance, object index) rule, so the visiting order changes no result.  The stack holds kBvhStack
 // (rfx_types.h) levels: the host builds no deeper hierarchy (rfx_scene.cpp: such a scene falls back to the chunk loops).
-#ifndef RFX_NARROW_BUNDLE_COS
-#define RFX_NARROW_BUNDLE_COS 0.9995f
-#endif
 constexpr float kNarrowBundleCos = RFX_NARROW_BUNDLE_COS;
 // Stack slots: int16 node / ~pair indices (the host builds no BVH for 32768 or more nodes or pairs).  Halving the
 // stack's LDS against int32 slots (8 -> 4 KB per workgroup) made C5 6.3% faster (tools/ab.py, round 2): workgroups
@@ -969,98 +881,40 @@ struct BvhLds {
     const uint2 x = aux[i];
     n.child[0] = (int32_t)(int16_t)(x.x & 0xFFFFu);
     n.child[1] = (int32_t)(int16_t)(x.x >> 16);
-#if RFX_BVH_PREWIDE
     n.mt[0] = n.mt[1] = 0.0f;  // the boxes are stored grown by their node margin
-#else
-    n.mt[0] = (float)(x.y & 0xFFFFu) * mstep;
-    n.mt[1] = (float)(x.y >> 16) * mstep;
-#endif
     return n;
   }
   __device__ __forceinline__ BvhSlot *stack() const { return stk + threadIdx.x; }
 };
 
-#ifndef RFX_BVH_FMA
-#define RFX_BVH_FMA 1
-#endif
-#ifndef RFX_BVH_TLIM
-#define RFX_BVH_TLIM 0
-#endif
-// box margins from the node's stored term and one per-ray distance (round 2: C5 -8.5% against a margin per box)
-#if RFX_BVH_PREWIDE
-#if !RFX_BVH_FMA
-#error "RFX_BVH_PREWIDE needs RFX_BVH_FMA (finite reciprocals)"
-#endif
-#ifndef RFX_BVH_PREWIDE_KEEP
-#define RFX_BVH_PREWIDE_KEEP 1  // 1: the six slab constants live across the walk; 0: re-derived per node (fewer registers)
-#endif
-#if RFX_BVH_PREWIDE_KEEP
-// the per-ray slab constants: (o + dm) rcp(d) for the low ends, (o - dm) rcp(d) for the high ends
+// the per-ray slab constants: the reciprocal direction, the per-ray margin dm = kCullRel |o - bvh_ref|_2 + 1e-6
+// (approximate root, widened 1e-4), (o + dm) rcp(d) for the low ends and (o - dm) rcp(d) for the high ends
 struct RayInv { float ix, iy, iz, dm, lx, ly, lz, hx, hy, hz; };
-#else
-struct RayInv { float ix, iy, iz, dm; };
-#endif
-#else
-struct RayInv { float ix, iy, iz, dm; };  // dm: kCullRel |o - bvh_ref|_2 + 1e-6 (approximate root, widened 1e-4)
-#endif
 __device__ __forceinline__ RayInv ray_inv(const DevScene &S, v3 o, v3 ray)
 {
   const float ex = o.x - S.bvh_rx, ey = o.y - S.bvh_ry, ez = o.z - S.bvh_rz;
   const float dm = kCullRel * (__builtin_amdgcn_sqrtf(ex * ex + ey * ey + ez * ez) * 1.0001f) + 1e-6f;
-#if RFX_BVH_FMA
   // finite reciprocals for the fused slabs: with rcp(0) = inf the fused form's inf - inf would leave one NaN slab end, and
   // fminf / fmaxf would then take the other end for both (a false cull of an axis-parallel ray, tests/test_bvh_box_bound.py)
   const auto fin = [](float v) { return fminf(fmaxf(v, -1e30f), 1e30f); };
-#if RFX_BVH_PREWIDE
   const float ix = fin(__builtin_amdgcn_rcpf(ray.x)), iy = fin(__builtin_amdgcn_rcpf(ray.y)),
               iz = fin(__builtin_amdgcn_rcpf(ray.z));
-#if RFX_BVH_PREWIDE_KEEP
   return RayInv{ix, iy, iz, dm, (o.x + dm) * ix, (o.y + dm) * iy, (o.z + dm) * iz,
                 (o.x - dm) * ix, (o.y - dm) * iy, (o.z - dm) * iz};
-#else
-  return RayInv{ix, iy, iz, dm};
-#endif
-#else
-  return RayInv{fin(__builtin_amdgcn_rcpf(ray.x)), fin(__builtin_amdgcn_rcpf(ray.y)), fin(__builtin_amdgcn_rcpf(ray.z)), dm};
-#endif
-#else
-  return RayInv{__builtin_amdgcn_rcpf(ray.x), __builtin_amdgcn_rcpf(ray.y), __builtin_amdgcn_rcpf(ray.z), dm};
-#endif
 }
 
 // child c of node n against the ray: hit (conservative), and the entry parameter t (>= 0) of the widened box.
 // Every decision is a comparison that a NaN fails in the keeping direction.
-__device__ __forceinline__ bool bvh_box(const BvhNode &n, int c, v3 o, const RayInv &ri, float &tn)
+__device__ __forceinline__ bool bvh_box(const BvhNode &n, int c, const RayInv &ri, float &tn)
 {
   const float lx = n.lx[c], ly = n.ly[c], lz = n.lz[c], hx = n.hx[c], hy = n.hy[c], hz = n.hz[c];
-  // |o - c|_2 + half-diagonal <= |o - ref|_2 + mt[c] (c the box centre): the margin is at least
-  // kCullRel (|o - c|_2 + half-diagonal) + 1e-6, the per-box bound of the culling argument
-#if RFX_BVH_PREWIDE
-  // boxes grown by kCullRel mt[c] on the host; the per-ray margin dm sits in the slab constants
-#if RFX_BVH_PREWIDE_KEEP
-  const float olx = ri.lx, oly = ri.ly, olz = ri.lz, ohx = ri.hx, ohy = ri.hy, ohz = ri.hz;
-#else
-  const float olx = (o.x + ri.dm) * ri.ix, oly = (o.y + ri.dm) * ri.iy, olz = (o.z + ri.dm) * ri.iz;
-  const float ohx = (o.x - ri.dm) * ri.ix, ohy = (o.y - ri.dm) * ri.iy, ohz = (o.z - ri.dm) * ri.iz;
-#endif
-  const float ax = __builtin_fmaf(lx, ri.ix, -olx), bx = __builtin_fmaf(hx, ri.ix, -ohx);
-  const float ay = __builtin_fmaf(ly, ri.iy, -oly), by = __builtin_fmaf(hy, ri.iy, -ohy);
-  const float az = __builtin_fmaf(lz, ri.iz, -olz), bz = __builtin_fmaf(hz, ri.iz, -ohz);
-#elif RFX_BVH_FMA
-  // The slab parameters as (bound - m) ix - o ix with one fused multiply-add each.  This is a cull decision with a
-  // margin, not a reference value: it rounds once where the unfused form rounds twice, so the margin covers it as
-  // before.  A 0 * inf NaN (axis-parallel ray, or bound - m and o on the same side) drops that axis: conservative.
-  const float m = __builtin_fmaf(kCullRel, n.mt[c], ri.dm);
-  const float oxi = o.x * ri.ix, oyi = o.y * ri.iy, ozi = o.z * ri.iz;
-  const float ax = __builtin_fmaf(lx - m, ri.ix, -oxi), bx = __builtin_fmaf(hx + m, ri.ix, -oxi);
-  const float ay = __builtin_fmaf(ly - m, ri.iy, -oyi), by = __builtin_fmaf(hy + m, ri.iy, -oyi);
-  const float az = __builtin_fmaf(lz - m, ri.iz, -ozi), bz = __builtin_fmaf(hz + m, ri.iz, -ozi);
-#else
-  const float m = ri.dm + kCullRel * n.mt[c];
-  const float ax = (lx - m - o.x) * ri.ix, bx = (hx + m - o.x) * ri.ix;
-  const float ay = (ly - m - o.y) * ri.iy, by = (hy + m - o.y) * ri.iy;
-  const float az = (lz - m - o.z) * ri.iz, bz = (hz + m - o.z) * ri.iz;
-#endif
+  // The host stores each box grown by kCullRel mt[c] (rfx_scene.cpp build_pair_bvh), and |o - c|_2 + half-diagonal <=
+  // |o - ref|_2 + mt[c] (c the box centre), so with the per-ray margin dm in the slab constants the total margin is at
+  // least kCullRel (|o - c|_2 + half-diagonal) + 1e-6, the per-box bound of the culling argument.  One fused
+  // multiply-add per slab end: a cull decision with a margin, not a reference value, so it may round once.
+  const float ax = __builtin_fmaf(lx, ri.ix, -ri.lx), bx = __builtin_fmaf(hx, ri.ix, -ri.hx);
+  const float ay = __builtin_fmaf(ly, ri.iy, -ri.ly), by = __builtin_fmaf(hy, ri.iy, -ri.hy);
+  const float az = __builtin_fmaf(lz, ri.iz, -ri.lz), bz = __builtin_fmaf(hz, ri.iz, -ri.hz);
   // fminf / fmaxf return the other operand for a NaN (0 * inf on an axis-parallel ray): that axis is ignored
   const float t0 = fmaxf(fmaxf(fminf(ax, bx), fminf(ay, by)), fmaxf(fminf(az, bz), 0.0f));
   const float t1 = fminf(fminf(fmaxf(ax, bx), fmaxf(ay, by)), fmaxf(az, bz));
@@ -1075,13 +929,6 @@ __device__ __forceinline__ void closest_spheres_bvh(const DevScene &S, v3 origin
 {
   const RayInv ri = ray_inv(S, origin, ray);
   const float a = 0.5f * k.a2;                // |ray|^2 (exact: a2 = 2a)
-#if RFX_BVH_TLIM
-  // the entry parameter beyond which a child cannot hold a closer (or tying) sphere, sqrt(1.001 best / a), kept per
-  // ray and re-derived on each new best hit: one compare per child instead of three multiplies.  Approximate rcp and
-  // sqrt (1 ulp each) under a 1e-4 widening keep it above the exact bound, so it skips no child the product form keeps.
-  const float ia = __builtin_amdgcn_rcpf(a);
-  float tlim = __builtin_amdgcn_sqrtf(h.sq * 1.001f * ia) * 1.0001f;
-#endif
   BvhSlot *stack = ns.stack();
   int sp = 0, node = 0;
   for (;;)
@@ -1091,13 +938,8 @@ __device__ __forceinline__ void closest_spheres_bvh(const DevScene &S, v3 origin
       const BvhNode n = ns.node(S, node);
       float t0, t1;
       // a child entered beyond the best hit cannot hold a closer (or tying) sphere
-#if RFX_BVH_TLIM
-      const bool h0 = bvh_box(n, 0, origin, ri, t0) && !(t0 > tlim);
-      const bool h1 = bvh_box(n, 1, origin, ri, t1) && !(t1 > tlim);
-#else
-      const bool h0 = bvh_box(n, 0, origin, ri, t0) && !(t0 * t0 * a > h.sq * 1.001f);
-      const bool h1 = bvh_box(n, 1, origin, ri, t1) && !(t1 * t1 * a > h.sq * 1.001f);
-#endif
+      const bool h0 = bvh_box(n, 0, ri, t0) && !(t0 * t0 * a > h.sq * 1.001f);
+      const bool h1 = bvh_box(n, 1, ri, t1) && !(t1 * t1 * a > h.sq * 1.001f);
       if (h0 && h1)
       {
         const bool first0 = !(t1 < t0);
@@ -1132,9 +974,6 @@ __device__ __forceinline__ void closest_spheres_bvh(const DevScene &S, v3 origin
             const int obj = S.sph_info[4 * j + 2];
             if (tri_takes(sq, h.sq, obj, h.obj)) { h.sq = sq; h.obj = obj; h.i = 2 * j + 1; h.t = t; }
           }
-#if RFX_BVH_TLIM
-          tlim = __builtin_amdgcn_sqrtf(h.sq * 1.001f * ia) * 1.0001f;
-#endif
         }
       }
     }
@@ -1146,9 +985,6 @@ __device__ __forceinline__ void closest_spheres_bvh(const DevScene &S, v3 origin
 // any sphere but skip_sph occludes the shadow ray (Scene.cpp:129-141 restricted to the spheres): the occluding pair's
 // index, or -1.  hint (wave-uniform, RFX_OCC_HINT): a pair that occluded a lane of this wave before, tested first -- an
 // occluder is an occluder whatever the order (Scene.cpp:132-141 breaks at the first), so a lane it occludes skips its walk.
-#ifndef RFX_OCC_HINT
-#define RFX_OCC_HINT 1
-#endif
 template <bool STATS, class NS>
 __device__ __forceinline__ int occluded_spheres_bvh(const DevScene &S, v3 o, v3 ray, const RayConst &k, int skip_sph,
                                                     Cnt &cnt, const NS &ns, int hint = -1)
@@ -1172,7 +1008,7 @@ __device__ __forceinline__ int occluded_spheres_bvh(const DevScene &S, v3 o, v3 
     {
       const BvhNode n = ns.node(S, node);
       float t0, t1;
-      const bool h0 = bvh_box(n, 0, o, ri, t0), h1 = bvh_box(n, 1, o, ri, t1);
+      const bool h0 = bvh_box(n, 0, ri, t0), h1 = bvh_box(n, 1, ri, t1);
       if (h0 && h1)
       {
         stack[NS::kStride * sp++] = n.child[1];
@@ -1233,8 +1069,8 @@ __device__ __forceinline__ void closest_tris_bvh(const DevScene &S, v3 origin, v
       const BvhNode n = S.tri_bvh[node];
       float t0, t1;
       // a child entered beyond the best hit cannot hold a closer (or tying) triangle
-      const bool h0 = bvh_box(n, 0, origin, ri, t0) && !(t0 * t0 * a > h.sq * 1.001f);
-      const bool h1 = bvh_box(n, 1, origin, ri, t1) && !(t1 * t1 * a > h.sq * 1.001f);
+      const bool h0 = bvh_box(n, 0, ri, t0) && !(t0 * t0 * a > h.sq * 1.001f);
+      const bool h1 = bvh_box(n, 1, ri, t1) && !(t1 * t1 * a > h.sq * 1.001f);
       if (h0 && h1)
       {
         const bool first0 = !(t1 < t0);
@@ -1301,7 +1137,7 @@ __device__ __forceinline__ bool occluded_tris_bvh(const DevScene &S, v3 o, v3 ra
     {
       const BvhNode n = S.tri_bvh[node];
       float t0, t1;
-      const bool h0 = bvh_box(n, 0, o, ri, t0), h1 = bvh_box(n, 1, o, ri, t1);
+      const bool h0 = bvh_box(n, 0, ri, t0), h1 = bvh_box(n, 1, ri, t1);
       if (h0 && h1)
       {
         stack[NS::kStride * sp++] = n.child[1];
@@ -1374,7 +1210,7 @@ __device__ __forceinline__ bool occluded_planes(const DevScene &S, v3 o, v3 ray,
 // visiting order is then not the insertion order, so spheres take the general (distance, object) rule.
 template <bool STATS, bool PLANES, bool TBVH = false, class NS = BvhGlobal>
 __device__ __forceinline__ void closest_hit(const DevScene &S, v3 origin, v3 ray, bool live, const Bundle *B, Hit &h,
-                                            Cnt &cnt, const NS &ns = NS{}, const uint64_t *pl = nullptr)
+                                            Cnt &cnt, const NS &ns = NS{})
 {
   if (live) RFX_CNT(C_SEGMENTS);
   h.obj = -1; h.kind = 0; h.i = 0; h.t = 0.0f; h.u = 0.0f; h.v = 0.0f; h.sq = kNoHitKey;
@@ -1386,25 +1222,21 @@ __device__ __forceinline__ void closest_hit(const DevScene &S, v3 origin, v3 ray
   RFX_PROF_BEGIN(P_SPH);
   // a narrow bundle (the primary rays of a tile: one origin, a cone of ~0.1 degree) culls the spatial chunks and
   // their spheres for the whole wave at once; wider ones walk the BVH lane by lane
-  // a per-view list (the tile's primary rays, prim_cull_large_kernel): the kept chunks and their sphere masks as listed
-  const bool listed = pl != nullptr;
-  const bool use_bvh = !listed && !STATS && S.bvh != nullptr && !(cull && B->cosa > kNarrowBundleCos);
+  const bool use_bvh = !STATS && S.bvh != nullptr && !(cull && B->cosa > kNarrowBundleCos);
   if (use_bvh && live) closest_spheres_bvh<STATS>(S, origin, ray, k, h, cnt, ns);
   for (int cfirst = 0; !use_bvh && cfirst < S.n_chunk; cfirst += 64)
   {
-    uint64_t cm = listed ? pl[2]
-                         : cull ? cull_chunk(S.chunk_bound, cfirst, min(64, S.n_chunk - cfirst), *B)
-                                : all_bits(min(64, S.n_chunk - cfirst));
+    uint64_t cm = cull ? cull_chunk(S.chunk_bound, cfirst, min(64, S.n_chunk - cfirst), *B)
+                       : all_bits(min(64, S.n_chunk - cfirst));
 #ifdef RFX_DEBUG_PROF
     st_chunks += __popcll(cm);
 #endif
-    int e = 4;
     while (cm)
     {
       const int first = 64 * (cfirst + __builtin_ctzll(cm));
       cm &= cm - 1ull;
       const int n = min(64, S.n_sph - first);
-      const uint64_t m = listed ? pl[e++] : cull ? cull_chunk(S.bound, first, n, *B) : all_bits(n);
+      const uint64_t m = cull ? cull_chunk(S.bound, first, n, *B) : all_bits(n);
       uint32_t pm = pair_bits(m);
 #ifdef RFX_DEBUG_PROF
       st_sph += __popcll(m);
@@ -1446,14 +1278,14 @@ __device__ __forceinline__ void closest_hit(const DevScene &S, v3 origin, v3 ray
 #if RFX_TRI_BVH
   if constexpr (TBVH && !STATS)
   {
-    use_tbvh = !listed && S.tri_bvh != nullptr && (S.tri_bvh_narrow || !(cull && B->cosa > kNarrowBundleCos));
+    use_tbvh = S.tri_bvh != nullptr && (S.tri_bvh_narrow || !(cull && B->cosa > kNarrowBundleCos));
     if (use_tbvh && live) closest_tris_bvh<STATS>(S, origin, ray, k, h, cnt, ns);
   }
 #endif
   for (int first = 0; !use_tbvh && first < S.n_tri; first += 64)
   {
     const int n = min(64, S.n_tri - first);
-    uint64_t m = listed ? pl[1] : (B && B->ok) ? cull_chunk(S.bound, S.n_sph + first, n, *B) : all_bits(n);
+    uint64_t m = (B && B->ok) ? cull_chunk(S.bound, S.n_sph + first, n, *B) : all_bits(n);
     while (m)
     {
       const int i = first + __builtin_ctzll(m);
@@ -1763,7 +1595,7 @@ __device__ __forceinline__ const DevScene &launder_scene(const DevScene &S)
 #endif
 // The frame parameters (the kernels' second argument, after the DevScene) read through the kernarg segment pointer, laundered
 // by an empty asm: every use reloads them with scalar loads where it stands, so their values are not held in SGPRs
-// across a bounce loop (with RFX_LAUNDER_PARAMS: the epilogue and the park ids; the RFX_SSAA_LDS_STATE sample loop)
+// across a bounce loop (with RFX_LAUNDER_PARAMS: the epilogue and the park ids)
 constexpr size_t kParamsOff = (sizeof(DevScene) + alignof(FrameParams) - 1) / alignof(FrameParams) * alignof(FrameParams);
 // The layout both readers assume, checked where it is defined (host and device passes): by-value kernel arguments are
 // laid out like the members of a struct, so (DevScene, FrameParams, ...) puts the record at 0 and the parameters at
@@ -1827,15 +1659,6 @@ __device__ __forceinline__ col trace_from(const DevScene &RFX_SCENE_PARAM, v3 or
         {
           const Bundle B = make_bundle(origin, ray, alive);
           if (B.ok) om = cull_small(T.cull(), S.cull_valid, B);
-#ifdef RFX_HALF_BUNDLES
-          else  // too wide for one cone: a cone per half wave, and the objects either half may hit
-          {
-            Bundle H[2];
-            make_bundle_halves(origin, ray, alive, H);
-            om = (H[0].ok ? cull_small(T.cull(), S.cull_valid, H[0]) : S.cull_valid) |
-                 (H[1].ok ? cull_small(T.cull(), S.cull_valid, H[1]) : S.cull_valid);
-          }
-#endif
           RFX_CULL_STAT(0, B.ok, __ballot(alive), om, S.cull_valid);
         }
       }
@@ -1844,11 +1667,9 @@ __device__ __forceinline__ col trace_from(const DevScene &RFX_SCENE_PARAM, v3 or
     }
     else
     {
-      // the first segment of a plain trace: the tile's per-view chunk list (prim_cull_large_kernel), when it has one
-      const uint64_t *pl = RFX_PRIM_LARGE && CULL && seg0 && pm_tile[0] != kPrimLargeNone ? pm_tile : nullptr;
       Bundle B;
       if constexpr (CULL) B = make_bundle(origin, ray, alive);
-      closest_hit<STATS, PLANES, TBVH>(S, origin, ray, alive, CULL ? &B : nullptr, h, cnt, park.bvh(), pl);
+      closest_hit<STATS, PLANES, TBVH>(S, origin, ray, alive, CULL ? &B : nullptr, h, cnt, park.bvh());
     }
     const bool hit = alive && h.obj >= 0;
     // re-derive the winner's outputs with the reference's expressions
@@ -2231,27 +2052,18 @@ __host__ __device__ constexpr uint32_t ss_lane_block(int ss)
 {
   return ss == 1 ? 8u : ss == 2 ? 4u : ss == 4 ? 2u : ss >= 8 ? 1u : 0u;
 }
-#ifndef RFX_SSAA_LANES
-#define RFX_SSAA_LANES 1
-#endif
 // CFG bits: kCfgCull -- wave-bundle culling (every non-stats launch); kCfgManyLights -- more than 32 lights;
 // kCfgSmall -- at most 32 spheres and 32 triangles (one lane-layout cull mask for the whole scene)
 // kCfgPlanes -- the scene holds planes (Scene::addPlane extension); kCfgPark -- plain pixels park their traces
 // for the bounce kernel (ray regrouping; rfx_trace_plain_park.hip).  The values: rfx_types.h.
 // kCfgTriBvh -- a non-small scene with a triangle BVH (rfx_types.h RFX_TRI_BVH): its culling configurations carry the
 // triangle walkers; every other scene runs kernels without them (with them C5 traced 3.0% slower)
-#ifndef RFX_ONE_LIGHT
-#define RFX_ONE_LIGHT 1
-#endif
 
 // one workgroup = kTileW x kTileH output pixels (block mode: block corners), one wave = an 8x8 tile (ray coherence).
 // Every lane of a wave reaches trace() -- lanes outside the frame or the cursor span as invalid -- so the
 // bounce loop can use wave-wide bundles.
 #ifndef RFX_WAVES_PER_EU_LARGE
 #define RFX_WAVES_PER_EU_LARGE RFX_WAVES_PER_EU  // large-scene (BVH) trace kernels' occupancy target (experiment)
-#endif
-#ifndef RFX_SSAA_CHANNEL_SUM
-#define RFX_SSAA_CHANNEL_SUM 1  // SSAA epilogues: one lane per colour channel runs the ordered sample sum
 #endif
 template <bool STATS, int MODE, int CFG>
 __global__ __launch_bounds__(kWgThreads) __attribute__((amdgpu_waves_per_eu(
@@ -2474,8 +2286,7 @@ __global__ __launch_bounds__(kWgThreads) __attribute__((amdgpu_waves_per_eu(
       v3 rd = mk(0.0f, 0.0f, 0.0f);
       if (valid) rd = load_rd(P, pr);
       const ParkTile park{P.park_after, P.queue, P.queue_count, P, wv, w8};
-      const uint64_t *pm_tile = (SMALL || RFX_PRIM_LARGE) && CULL && !STATS && P.prim_mask
-                                    ? P.prim_mask + (size_t)(SMALL ? kPrimStride : kPrimLargeStride) * t8 : nullptr;
+      const uint64_t *pm_tile = SMALL && CULL && !STATS && P.prim_mask ? P.prim_mask + (size_t)kPrimStride * t8 : nullptr;
       const col c = trace_from<STATS, CULL, MANYL, SMALL, PLANES, PARK, ParkTile, ONEL, TBVH>(S, eye, ray, mkc(1.0f, 1.0f, 1.0f),
                                                                   mkc(0.0f, 0.0f, 0.0f), 0, P.depth, rd, lut, cnt,
                                                                   valid, park, parked, pm_tile);
@@ -2484,68 +2295,6 @@ __global__ __launch_bounds__(kWgThreads) __attribute__((amdgpu_waves_per_eu(
     else
     {
       // SSAA / additive (Render.cpp:174-194): each lane runs its pixel's ss x ss traces in turn
-#ifdef RFX_SSAA_LDS_STATE
-      // Experiment (round 4, off: +3.7% on the screenshot frame, interleaved A/B).  The per-lane state that outlives
-      // each sample's bounce loop -- the running sum and the additive jitter -- waits in the wave's epilogue staging
-      // slot (s_out: 192 words of sum, 64 of jitter), and the pixel's coordinates are re-derived from the tile index in
-      // LDS for every sample, so the bounce loop runs with fewer live values (22 -> 9 VGPR spills, small scenes).
-      uint32_t *slot = s_out[wv];
-      uint32_t jit = 0;
-      if (P.additive && valid)                                                     // Render.cpp:177-178
-      {
-        const uint32_t s1 = lcg_jump(P.jitter_seed, 2 * pr + 1);
-        jit = lcg_out(s1) | lcg_out(lcg_step(s1)) << 16;  // two 15-bit draws
-      }
-      slot[192 + lane] = jit;
-      slot[3 * lane] = 0u;  // +0.0f: Color finColor(0, 0, 0)
-      slot[3 * lane + 1] = 0u;
-      slot[3 * lane + 2] = 0u;
-      const int ss = P.ss;
-      const float ssf = (float)ss;
-      for (int sx = 0; sx < ss; ++sx)                                              // Render.cpp:181-187
-        for (int sy = 0; sy < ss; ++sy)
-        {
-          const FrameParams &P = kernarg_params();  // shadows the by-value parameter: reloaded per sample
-          m33 view;
-          view.m11 = P.v11; view.m12 = P.v12; view.m13 = P.v13;
-          view.m21 = P.v21; view.m22 = P.v22; view.m23 = P.v23;
-          view.m31 = P.v31; view.m32 = P.v32; view.m33 = P.v33;
-          const v3 eye = mk(P.eye_x, P.eye_y, P.eye_z);
-          const uint32_t t8s = ((volatile uint32_t *)s_tile8)[wv];
-          uint32_t ls = lane;
-          asm volatile("" : "+v"(ls));  // a fresh lane value: the coordinates are recomputed, not kept live
-          const uint32_t sgx = (t8s % w8) * 8u + (ls & 7u), sgy = (t8s / w8) * 8u + (ls >> 3);
-          const uint32_t sy_ = P.nranks > 1 ? strip_row_to_y(sgy, P) : sgy + P.row0;
-          const uint64_t sp = (uint64_t)sy_ * P.W + sgx;
-          const bool svalid = sgx < P.W && sgy < P.grid_rows && sp >= P.p_begin && sp < P.p_end;
-          const uint32_t jw = ((volatile uint32_t *)slot)[192 + ls];
-          const float rndx = P.additive ? (float)(jw & 0xFFFFu) / (float)0x7FFF : 0.0f;
-          const float rndy = P.additive ? (float)(jw >> 16) / (float)0x7FFF : 0.0f;
-          // float(0) / ss == +0 exactly, so the first sample's offsets need no division
-          const float ox = sx ? (float)sx / ssf : 0.0f, oy = sy ? (float)sy / ssf : 0.0f;
-          v3 ray = mk((float)sgx - P.wh + ox + rndx, (float)sy_ - P.hh + oy + rndy, P.rz);
-          ray = mmul(view, ray);
-          v3 rd = mk(0.0f, 0.0f, 0.0f);
-          if (svalid) rd = load_rd(P, (sp - P.p_begin) * (uint64_t)(ss * ss) + (uint64_t)(sx * ss + sy));
-          // the tile's per-view masks cover every sample's primary rays (prim_cull_kernel)
-          const uint64_t *pm = RFX_PRIM_SSAA && SMALL && CULL && !STATS && P.prim_mask
-                                   ? P.prim_mask + (size_t)kPrimStride * t8s : nullptr;
-          const col c = trace<STATS, CULL, MANYL, SMALL, PLANES, false, TBVH>(S, eye, ray, P.depth, rd, lut, cnt, svalid, pm,
-                                                                 P.prim_shadow != 0);
-          float *f = reinterpret_cast<float *>(slot) + 3 * ls;
-          f[0] = f[0] + c.r;
-          f[1] = f[1] + c.g;
-          f[2] = f[2] + c.b;
-        }
-      const float *f = reinterpret_cast<const float *>(slot) + 3 * lane;
-      col fin = mkc(f[0], f[1], f[2]);
-      if (ss != 1)                                                                 // Render.cpp:189 (x / 1.0f == x)
-      {
-        const float sq = (float)(ss * ss);
-        if (fabsf(sq) > kVerySmall) fin = mkc(fin.r / sq, fin.g / sq, fin.b / sq);
-      }
-      out = fin;
-#else
       float rndx = 0.0f, rndy = 0.0f;
       if (P.additive && valid)                                                     // Render.cpp:177-178
       {
@@ -2576,7 +2325,6 @@ __global__ __launch_bounds__(kWgThreads) __attribute__((amdgpu_waves_per_eu(
         if (fabsf(sq) > kVerySmall) fin = mkc(fin.r / sq, fin.g / sq, fin.b / sq);
       }
       out = fin;
-#endif
     }
     // output coordinates again, from the tile index in LDS (volatile: re-read, not kept live)
 #ifdef RFX_LAUNDER_PARAMS
@@ -2771,65 +2519,6 @@ __global__ RFX_TRACE_BOUNDS void prim_cull_kernel(DevScene S, FrameParams P, uin
   if (lane == 0) out[0] = om;
   for (int q = 0; q < kPrimLights; ++q)  // the words past the scene's lights are 0 (never read; a defined read-back)
     if (lane == 0) out[1 + q] = sm[q];
-}
-
-// Per-view chunk lists of a large scene's plain frame (FrameParams::prim_mask, kPrimLargeStride words per wave tile t8):
-// the primary bundle of the tile -- the same rays, validity and bundle as trace_from's first segment -- and, when it is
-// narrow enough for the chunk path (closest_hit), its chunk cull and the sphere cull of each kept chunk, stored as a
-// list the trace kernel walks instead of culling again; the triangle cull too.  More than kPrimLargeChunks kept chunks,
-// more than 64 triangles, or a bundle the chunk path would not take: kPrimLargeNone (the tile culls per launch).
-template <int UNUSED = 0>  // a template, as every kernel this header defines: one definition across the TUs
-__global__ RFX_TRACE_BOUNDS void prim_cull_large_kernel(DevScene S, FrameParams P, uint64_t *masks)
-{
-  const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
-  const uint32_t wv = __builtin_amdgcn_readfirstlane(wave);
-  const uint32_t w8 = kTileWavesX * gridDim.x;
-  const uint32_t t8 = (blockIdx.y * kTileWavesY + wv / kTileWavesX) * w8 + blockIdx.x * kTileWavesX + wv % kTileWavesX;
-  const uint32_t gx = (t8 % w8) * 8u + (lane & 7u), gy = (t8 / w8) * 8u + (lane >> 3);
-  const uint32_t x = gx;
-  const uint32_t y = P.nranks > 1 ? strip_row_to_y(gy, P) : gy + P.row0;
-  const uint64_t p = (uint64_t)y * P.W + x;
-  const bool valid = gx < P.W && gy < P.grid_rows && p >= P.p_begin && p < P.p_end && P.depth > 0;
-  m33 view;
-  view.m11 = P.v11; view.m12 = P.v12; view.m13 = P.v13;
-  view.m21 = P.v21; view.m22 = P.v22; view.m23 = P.v23;
-  view.m31 = P.v31; view.m32 = P.v32; view.m33 = P.v33;
-  const v3 eye = mk(P.eye_x, P.eye_y, P.eye_z);
-  const float rx = (float)x - P.wh, ry = (float)y - P.hh;                       // Render.cpp:152-153
-  const v3 ray = mmul(view, mk(rx + 0.0f + 0.0f, ry + 0.0f + 0.0f, P.rz));     // as trace_kernel (plain)
-  uint64_t *out = masks + (size_t)kPrimLargeStride * t8;
-  uint64_t w[kPrimLargeStride];
-#pragma unroll
-  for (int i = 0; i < kPrimLargeStride; ++i) w[i] = 0;
-  bool listed = false;
-  if (__ballot(valid) && S.n_tri <= 64 && S.n_chunk <= 64)
-  {
-    const Bundle B = make_bundle(eye, ray, valid);
-    // the bundles closest_hit takes through the chunk path (the others walk the BVH per lane)
-    if (B.ok && (S.bvh == nullptr || B.cosa > kNarrowBundleCos))
-    {
-      const uint64_t cm = cull_chunk(S.chunk_bound, 0, S.n_chunk, B);
-      listed = __popcll(cm) <= kPrimLargeChunks;
-      if (listed)
-      {
-        w[0] = (uint64_t)__popcll(cm);
-        w[2] = cm;
-        int e = 4;
-        for (uint64_t c = cm; c; c &= c - 1ull)
-        {
-          const int first = 64 * __builtin_ctzll(c);
-          w[e++] = cull_chunk(S.bound, first, min(64, S.n_sph - first), B);
-        }
-        if (S.n_tri > 0) w[1] = cull_chunk(S.bound, S.n_sph, S.n_tri, B);
-      }
-    }
-  }
-  if (!listed) w[0] = kPrimLargeNone;
-  if (lane == 0)
-  {
-#pragma unroll
-    for (int i = 0; i < kPrimLargeStride; ++i) out[i] = w[i];
-  }
 }
 
 // The parked traces (rfx_types.h QRay) of a plain-pixel launch resumed in packed waves: each wave claims 64

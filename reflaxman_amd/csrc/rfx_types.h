@@ -3,6 +3,8 @@
 // and walked in wave-uniform order by the trace kernel, so the compiler serves
 // them through the scalar cache (s_load_dwordx4) rather than per-lane loads.
 #pragma once
+#include "rfx_config.h"
+
 #include <stddef.h>
 #include <stdint.h>
 
@@ -58,19 +60,14 @@ struct alignas(16) CullTri { float v0x, v0y, v0z, nu, gux, guy, guz, nv, gvx, gv
 // node, c < 0 the leaf pair ~c (spheres 2(~c), 2(~c) + 1 of the device arrays, which are in spatial order).
 // mt[c]: |ref - centre of child c|_2 + its half-diagonal (ref: DevScene::bvh_ref), so that kCullRel (|o - ref|_2 + mt[c])
 // bounds the kernel's per-ray box margin from above with one add per child (triangle inequality)
-// RFX_BVH_PREWIDE (round 4, kept: C5 trace + bounce -4.0%): the host stores each child box already grown by kCullRel
-// mt[c] (rounded outward), so the kernel adds only the per-ray part of the margin, folded into per-ray slab constants.
-#ifndef RFX_BVH_PREWIDE
-#define RFX_BVH_PREWIDE 1
-#endif
+// Pre-widened boxes (round 4: C5 trace + bounce -4.0%): the host stores each child box already grown by kCullRel mt[c]
+// (rounded outward), so the kernel adds only the per-ray part of the margin, folded into per-ray slab constants, and
+// reads neither mt nor the margin half of bvh_aux.
 // the kernels' per-lane traversal stack: the host builders keep both trees within it (a deeper one: the chunk loops)
 constexpr int kBvhStack = 16;
 struct alignas(16) BvhNode { float lx[2], ly[2], lz[2], hx[2], hy[2], hz[2]; int32_t child[2]; float mt[2]; };
 // Sphere pairs per BVH leaf (rfx_scene.cpp build_pair_bvh, rfx_trace.h leaf tests): leaf ~g holds the pairs
 // [RFX_BVH_LEAF_PAIRS g, RFX_BVH_LEAF_PAIRS (g + 1)) of the device order (sph_pair padded with never-hit pairs)
-#ifndef RFX_BVH_LEAF_PAIRS
-#define RFX_BVH_LEAF_PAIRS 4
-#endif
 // Triangle BVH of a non-small scene (rfx_scene.cpp build_tri_tree, rfx_trace.h closest_tris_bvh / occluded_tris_bvh):
 // BvhNode nodes with the sphere tree's conventions (child >= 0 internal, ~g a leaf, boxes pre-widened, the same
 // margin reference point DevScene::bvh_ref), so ray_inv and bvh_box serve both trees.  Leaf ~g holds the records
@@ -78,12 +75,6 @@ struct alignas(16) BvhNode { float lx[2], ly[2], lz[2], hx[2], hy[2], hz[2]; int
 // TriGeo whose padding carries the insertion index (pad[0]) and the object index (pad[1]) as int bits; a padding
 // record is all zero (a31 = a32 = a33 = 0: never hit).  tri_geo / tri_shade stay in insertion order.  RFX_TRI_BVH 0
 // removes the walkers from the kernels.
-#ifndef RFX_TRI_BVH
-#define RFX_TRI_BVH 1
-#endif
-#ifndef RFX_TRI_BVH_LEAF
-#define RFX_TRI_BVH_LEAF 4
-#endif
 // Plane(pos, norm, material) (Plane.h:6-14): the normal as given (the reference never normalises it)
 struct alignas(16) PlaneGeo { float px, py, pz, nx, ny, nz; int32_t obj, dielectric; };
 struct alignas(16) LightRec { float ox, oy, oz, radius, r, g, b, power; }; // OmniLight.h
@@ -191,10 +182,9 @@ struct FrameParams {
   int32_t prim_shadow;
 };
 
-// words per wave tile of the per-view primary masks (rfx_trace.h prim_cull_kernel / prim_cull_large_kernel; the host
-// sizes FrameParams::prim_mask by them)
+// words per wave tile of the per-view primary masks (rfx_trace.h prim_cull_kernel; the host sizes
+// FrameParams::prim_mask by them)
 constexpr int kPrimLights = 4, kPrimStride = 1 + kPrimLights;
-constexpr int kPrimLargeChunks = 8, kPrimLargeStride = 4 + kPrimLargeChunks;
 // the trace and bounce kernels' CFG template bits (rfx_trace.h trace_kernel), chosen per launch by the host
 constexpr int kCfgCull = 1, kCfgManyLights = 2, kCfgSmall = 4, kCfgPlanes = 8, kCfgPark = 16, kCfgOneLight = 32;
 constexpr int kCfgTriBvh = 64;

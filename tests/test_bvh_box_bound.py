@@ -2,13 +2,14 @@
 
 A sphere the reference reports as hit lies within r + 1.25e-3 |o - c| of the ray (tests/test_cull_bound.py), so a ray
 that reports a hit on a sphere inside a BVH child box passes within delta = 1.25e-3 (|o - centre| + half-diagonal) of
-that box at some t > 0.  The kernel widens the box by m = kCullRel (|o - ref| + mt) + 1e-6 >= kCullRel (|o - centre| +
-half-diagonal) + 1e-6 and runs the slab test in float32 with approximate reciprocals.  This test aims rays at points
-inside the box grown by 0.95 delta -- from origins 0.05 .. 200 box sizes away, with unnormalised directions, some
-axis-parallel -- and checks that the kernel's float arithmetic keeps every such box, in both forms: the unfused slab
-((bound - m) - o) * rcp(d) and the fused one fma(bound - m, rcp(d), -(o * rcp(d))) (RFX_BVH_FMA).  The fused form needs
-finite reciprocals: with rcp(0) = inf, inf - inf leaves one slab end NaN and fminf / fmaxf take the other end for both,
-which culls axis-parallel rays that pass through the box (476 of 2^19 here before ray_inv clamped them to +-1e30).
+that box at some t > 0.  The box is widened by m = kCullRel (|o - ref| + mt) + 1e-6 >= kCullRel (|o - centre| +
+half-diagonal) + 1e-6 -- the node part kCullRel mt on the host (rfx_scene.cpp build_pair_bvh), the per-ray part in the
+kernel's slab constants -- and the slab test runs in float32 with approximate reciprocals, one fused multiply-add per
+slab end: fma(bound, rcp(d), -((o +- dm) rcp(d))).  This test aims rays at points inside the box grown by 0.95 delta --
+from origins 0.05 .. 200 box sizes away, with unnormalised directions, some axis-parallel -- and checks that the
+kernel's float arithmetic keeps every such box.  The fused form needs finite reciprocals: with rcp(0) = inf, inf - inf
+leaves one slab end NaN and fminf / fmaxf take the other end for both, which culls axis-parallel rays that pass through
+the box (476 of 2^19 here before ray_inv clamped them to +-1e30).
 """
 import numpy as np
 import pytest
@@ -27,35 +28,19 @@ def fmaf(a, b, c):
     return (a.astype(np.float64) * b.astype(np.float64) + c.astype(np.float64)).astype(F)
 
 
-def kept(lo, hi, o, d, ref, mt, rng, fused):
-    """rfx_trace.h ray_inv + bvh_box for one child, in float32 (fused: False, True or "prewide")."""
+def kept(lo, hi, o, d, ref, mt, rng):
+    """rfx_trace.h ray_inv + bvh_box for one child, in float32."""
     e = o - ref
     dm = K_CULL_REL * (approx(np.sqrt((e * e).sum(1, dtype=F)), rng) * F(1.0001)) + F(1e-6)
     with np.errstate(divide="ignore", invalid="ignore", over="ignore"):
-        inv = approx(F(1) / d, rng)
-        if fused:  # ray_inv clamps the reciprocals to +-1e30 for the fused forms
-            inv = np.clip(inv, F(-1e30), F(1e30))
-        if fused == "prewide":
-            # rfx_scene.cpp: the box grown by kCullRel mt (x (1 + 1e-6)) and rounded outward; the kernel's slab
-            # constants (o + dm) rcp(d) and (o - dm) rcp(d)
-            w = 2e-3 * mt.astype(np.float64) * (1.0 + 1e-6)
-            lo = np.nextafter((lo.astype(np.float64) - w[:, None]).astype(F), F(-np.inf))
-            hi = np.nextafter((hi.astype(np.float64) + w[:, None]).astype(F), F(np.inf))
-            a = fmaf(lo, inv, -((o + dm[:, None]) * inv))
-            b = fmaf(hi, inv, -((o - dm[:, None]) * inv))
-            mn, mx = np.fmin(a, b), np.fmax(a, b)
-            t0 = np.fmax(np.fmax(mn[:, 0], mn[:, 1]), np.fmax(mn[:, 2], F(0)))
-            t1 = np.fmin(np.fmin(mx[:, 0], mx[:, 1]), mx[:, 2])
-            return ~(t0 > t1 * F(1.00001) + F(1e-30))
-        elif fused:  # RFX_BVH_FMA without pre-widening (RFX_BVH_PREWIDE=0)
-            m = fmaf(np.full_like(mt, K_CULL_REL), mt, dm)
-            oi = o * inv
-            a = fmaf(lo - m[:, None], inv, -oi)
-            b = fmaf(hi + m[:, None], inv, -oi)
-        else:
-            m = dm + K_CULL_REL * mt
-            a = (lo - m[:, None] - o) * inv
-            b = (hi + m[:, None] - o) * inv
+        inv = np.clip(approx(F(1) / d, rng), F(-1e30), F(1e30))  # ray_inv clamps the reciprocals to +-1e30
+        # rfx_scene.cpp: the box grown by kCullRel mt (x (1 + 1e-6)) and rounded outward; the kernel's slab
+        # constants (o + dm) rcp(d) and (o - dm) rcp(d)
+        w = 2e-3 * mt.astype(np.float64) * (1.0 + 1e-6)
+        lo = np.nextafter((lo.astype(np.float64) - w[:, None]).astype(F), F(-np.inf))
+        hi = np.nextafter((hi.astype(np.float64) + w[:, None]).astype(F), F(np.inf))
+        a = fmaf(lo, inv, -((o + dm[:, None]) * inv))
+        b = fmaf(hi, inv, -((o - dm[:, None]) * inv))
         # fminf / fmaxf: a NaN operand yields the other one
         mn, mx = np.fmin(a, b), np.fmax(a, b)
         t0 = np.fmax(np.fmax(mn[:, 0], mn[:, 1]), np.fmax(mn[:, 2], F(0)))
@@ -63,9 +48,9 @@ def kept(lo, hi, o, d, ref, mt, rng, fused):
         return ~(t0 > t1 * F(1.00001) + F(1e-30))
 
 
-@pytest.mark.parametrize("fused", [False, True, "prewide"])
-def test_box_test_keeps_every_box_a_reported_hit_lies_in(fused):
-    rng = np.random.default_rng(20261017 + [False, True, "prewide"].index(fused))
+@pytest.mark.parametrize("form", ["prewide"])  # (the one form the kernels have; the id and the seed are its own)
+def test_box_test_keeps_every_box_a_reported_hit_lies_in(form):
+    rng = np.random.default_rng(20261017 + 2)
     n = 1 << 19
     size = np.exp(rng.uniform(np.log(0.02), np.log(5.0), (n, 3)))         # half extents
     centre = rng.uniform(-20.0, 20.0, (n, 3))
@@ -94,20 +79,6 @@ def test_box_test_keeps_every_box_a_reported_hit_lies_in(fused):
     inside = (np.abs(q - centre) <= size + 0.96 * delta[:, None]).all(1)
     assert inside.sum() > n - n // 8
     lo, hi = (centre - size).astype(F), (centre + size).astype(F)
-    k = kept(lo, hi, o.astype(F), d.astype(F), ref.astype(F), mt, rng, fused)
+    k = kept(lo, hi, o.astype(F), d.astype(F), ref.astype(F), mt, rng)
     assert k[inside].all(), int((~k[inside]).sum())
 
-
-def test_entry_limit_keeps_what_the_product_form_keeps():
-    """RFX_BVH_TLIM: a child is skipped when its entry parameter t0 exceeds tlim = sqrt(1.001 best / a) 1.0001 (approximate
-    rcp and sqrt); the product form skips it when t0^2 a > 1.001 best.  Every child the product form keeps, tlim keeps."""
-    rng = np.random.default_rng(7)
-    n = 1 << 20
-    a = np.exp(rng.uniform(np.log(1e-4), np.log(1e6), n)).astype(F)            # |ray|^2
-    best = np.exp(rng.uniform(np.log(1e-8), np.log(1e8), n)).astype(F)         # best |ray t|^2 so far
-    t0 = (np.sqrt(best.astype(np.float64) * 1.001 / a) * np.exp(rng.normal(0.0, 1e-5, n))).astype(F)
-    keep_product = ~(t0 * t0 * a > best * F(1.001))
-    tlim = approx(np.sqrt(best * F(1.001) * approx(F(1) / a, rng)), rng) * F(1.0001)
-    keep_tlim = ~(t0 > tlim)
-    assert keep_product.sum() > n // 4
-    assert not (keep_product & ~keep_tlim).any()

@@ -544,23 +544,6 @@ def test_stress_band_other_regrouping(key, regroup, qsort):
     r.close()
 
 
-@pytest.mark.parametrize("key", sorted(k for k, c in CASES.items() if c["kind"] == "band" and c["scene"] == "stress4096"))
-def test_stress_band_chunk_lists(key):
-    """C5 with prim_masks 2: the per-view chunk lists of the primary bundles (prim_cull_large_kernel).  They exist only
-    in an RFX_PRIM_LARGE build (measured slower, compiled out by default): in the default build this path has no parity
-    coverage, and the test is skipped rather than repeating test_stress_band."""
-    from reflaxman_amd import _lib
-    if not _lib.load().rfx_build_options() & 1:  # RFX_BUILD_PRIM_LARGE
-        pytest.skip("default build: RFX_PRIM_LARGE compiled out (no per-view chunk lists to test)")
-    c = CASES[key]
-    rgb, argb, r = gpu_render(scene(c["scene"]), c["W"], c["H"], c["depth"], sphere_seed=c["sphere_seed"], prim_masks=2)
-    g = np.load(os.path.join(GOLDEN, key + ".npz"))
-    y0, rows = c["y0"], c["rows"]
-    assert np.array_equal(argb[y0:y0 + rows], g["argb"])
-    assert rgb[y0:y0 + rows].tobytes() == g["rgb"].tobytes()
-    r.close()
-
-
 @pytest.mark.parametrize("big", [False, True])
 def test_regrouped_large_scene_equals_unregrouped(big):
     """The bounce kernel's two forms on large scenes: with the BVH staged in LDS (4096 spheres fit) and walking it in

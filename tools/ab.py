@@ -60,17 +60,9 @@ VARIANTS = {
     "launderscene": ["RFX_NO_LAUNDER", "RFX_LAUNDER_SCENE"],
     "launderparams": ["RFX_NO_LAUNDER", "RFX_LAUNDER_PARAMS"],
     "primssaa": ["RFX_PRIM_SSAA=1"],
-    "primlarge": ["RFX_PRIM_LARGE=1"],
-    "ssaalds": ["RFX_SSAA_LDS_STATE"],
     "nolanes": ["RFX_SSAA_LANES=0"],
-    "halves": ["RFX_HALF_BUNDLES"],
     "nolight1": ["RFX_ONE_LIGHT=0"],
     "noprimlanes": ["RFX_PRIM_LANES=0"],
-    "nobvhfma": ["RFX_BVH_FMA=0"],
-    "tlim": ["RFX_BVH_TLIM=1"],
-    "noprewide": ["RFX_BVH_PREWIDE=0"],
-    "pwlite": ["RFX_BVH_PREWIDE_KEEP=0"],
-    "tlimlite": ["RFX_BVH_TLIM=1", "RFX_BVH_PREWIDE_KEEP=0"],
     "nocullfma": ["RFX_CULL_FMA=0"],
     "lanes8": ["RFX_LANES_WAVES_PER_EU=8"],
     "nb999": ["RFX_NARROW_BUNDLE_COS=0.999f"],
@@ -97,7 +89,6 @@ VARIANTS = {
     "tiles0": ["RFX_SCAN_TILES=0"],
     "fmax256": ["RFX_RNG_FUSED_MAX_BLOCKS=256"],
     "fmax512": ["RFX_RNG_FUSED_MAX_BLOCKS=512"],
-    "divsel1": ["RFX_DIV_SEL=1"],
     "divfast2": ["RFX_DIV_FAST=2"],
     "intacc0": ["RFX_RNG_INT_ACCEPT=0"],
     "se4096": ["RFX_SCAN_EMIT_BLOCKS=4096"],
