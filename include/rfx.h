@@ -385,7 +385,7 @@ int rfx_kat_powf(rfx_renderer *r, const float *xy, uint64_t n, float *out);
 int rfx_kat_argb(rfx_renderer *r, const float *rgb, uint64_t n, uint32_t *out);
 int rfx_kat_powf_cube(rfx_renderer *r, uint64_t counts[2]);
 int rfx_kat_div(rfx_renderer *r, uint64_t first, uint64_t n, uint64_t counts[3]);
-/* The kernel-argument layout the bounce loops rely on (rfx_trace.h launder_scene / kernarg_params: DevScene at kernarg
+/* The kernel-argument layout the bounce loops rely on (rfx_bounce.h launder_scene / kernarg_params: DevScene at kernarg
  * offset 0, FrameParams after it): a one-lane kernel of the trace kernels' signature compares the records read through
  * the kernarg segment pointer with its by-value arguments.  out[0] / out[1] = differing words of the scene record / the
  * frame parameters (0 expected), out[2] = 1 if the build reads the scene record that way.  swapped = 1 runs the same

@@ -31,15 +31,15 @@
 #define RFX_TRI_BVH_NARROW_MIN (1 << 30)  // triangles from which narrow bundles walk the tree too; 0: always (DESIGN.md "Triangle BVH")
 #endif
 
-// ---- trace kernels (rfx_trace.h)
+// ---- trace kernels (rfx_trace.h and the device headers it includes)
 #if !defined(RFX_WAVES_PER_EU) && defined(RFX_LANES_WAVES_PER_EU) && defined(RFX_UNIT_LANES_FAST)
 #define RFX_WAVES_PER_EU RFX_LANES_WAVES_PER_EU  // rfx_trace_lanes_fast.hip alone (it defines RFX_UNIT_LANES_FAST): that family's own target
 #endif
 #ifndef RFX_WAVES_PER_EU
-#define RFX_WAVES_PER_EU 7  // the trace kernels' occupancy target: 6 or 8 (rfx_trace.h, at kWgWaves; DESIGN.md "Large scenes", occupancy re-checked)
+#define RFX_WAVES_PER_EU 7  // the trace kernels' occupancy target: 6 or 8 (rfx_shade_inputs.h, at kWgWaves; DESIGN.md "Large scenes", occupancy re-checked)
 #endif
 #ifndef RFX_WG_WAVES
-#define RFX_WG_WAVES 2  // waves per workgroup: 1 or 4 (measurements in rfx_trace.h, at kWgWaves)
+#define RFX_WG_WAVES 2  // waves per workgroup: 1 or 4 (measurements in rfx_shade_inputs.h, at kWgWaves)
 #endif
 #ifndef RFX_TRI_MATES
 #define RFX_TRI_MATES 2  // coplanar mates share the z stage: 0 never, 1 both small-scene loops, 3 shadow loop only (DESIGN.md "Exact work skipping", coplanar mates)
@@ -145,8 +145,8 @@
 
 // ---- presence flags: defined or not, no value
 //   RFX_NO_LAUNDER      the kernel arguments held in registers across the bounce loops: neither flag below is derived
-//   RFX_LAUNDER_SCENE   the DevScene re-read from the kernarg segment in every segment (derived in rfx_trace.h)
-//   RFX_LAUNDER_PARAMS  the FrameParams re-read after the bounce loop (derived in rfx_trace.h)
+//   RFX_LAUNDER_SCENE   the DevScene re-read from the kernarg segment in every segment (derived in rfx_bounce.h)
+//   RFX_LAUNDER_PARAMS  the FrameParams re-read after the bounce loop (derived in rfx_bounce.h)
 //   RFX_DEBUG_PROF      per-phase cycle counters and cull statistics (tools/build_diag.py)
 //   RFX_DEBUG_SEGS      per-trace segment counts
 //   RFX_DEBUG_WAVES     per-wave start / end timestamps

@@ -681,7 +681,7 @@ static int run_prepass(rfx_renderer *r, FramePlan &pl, uint64_t nblk, uint32_t *
 }
 
 // trace_frame's stages.  1: ray regrouping -- plain pixels of a large scene park their traces after park_after segments
-// in the queue set up here; the bounce kernel resumes them in packed waves (rfx_trace.h bounce_kernel).
+// in the queue set up here; the bounce kernel resumes them in packed waves (rfx_parked.h bounce_kernel).
 static int setup_regroup_queue(rfx_renderer *r, FramePlan &pl, int park_after, bool sort_queue)
 {
   int rc;

@@ -5,8 +5,10 @@
 //   lpt_hist / lpt_scan / lpt_scatter : the longest-tile-first schedule of the trace launch;
 //   qs_hist / qs_scan / qs_scatter : the regroup queue's bucket order (ray regrouping of large scenes);
 //   kat_* : the trace kernel's primitive code on known-answer inputs (rfx.h rfx_kat_*);
+//   prim_cull_kernel (rfx_prim_cull.h) : the per-view masks, instantiated and launched here;
 // and the library-internal launchers.
 #include "rfx_trace.h"
+#include "rfx_prim_cull.h"
 
 #include <vector>
 
@@ -93,7 +95,7 @@ hipError_t launch_tile_order(const uint32_t *cost, uint32_t n, uint32_t *order, 
 }
 
 // ------------------------------------------------------------- regroup queue sort
-// The parked traces of a frame (QRay queue, count on the device) listed bucket by bucket (rfx_trace.h queue_key:
+// The parked traces of a frame (QRay queue, count on the device) listed bucket by bucket (rfx_bounce.h queue_key:
 // direction octant, origin cell), so that the bounce kernel's packed waves take traces that walk similar BVH paths.
 // A counting sort over kQsGroups workgroups: per-group LDS histograms added into a global one, one scan, then each
 // group reserves its range of every bucket with one atomic and ranks its entries in LDS.  The order within a bucket
@@ -1205,7 +1207,7 @@ __global__ __launch_bounds__(kKatThreads) void kat_div(uint64_t first, uint32_t 
   }
 }
 
-// The kernel-argument layout the bounce loops read through the kernarg segment pointer (rfx_trace.h launder_scene,
+// The kernel-argument layout the bounce loops read through the kernarg segment pointer (rfx_bounce.h launder_scene,
 // kernarg_params): the laundered DevScene and FrameParams against the by-value arguments, word by word.  out[0] / out[1]:
 // words of the DevScene / FrameParams that differ (0 expected), out[2]: 1 when the build reads the record laundered.
 // kat_kernarg_swapped takes the arguments the other way round -- what a kernel with a swapped signature would read --

@@ -526,7 +526,7 @@ int build_pair_bvh(std::vector<BvhNode> &nodes, std::vector<uint32_t> &pairs, si
       for (int k = 0; k < 3; ++k) { l[k] = fmin(l[k], box[pairs[i]].lo[k]); h[k] = fmax(h[k], box[pairs[i]].hi[k]); }
     if (widen)  // (false: rfx_scene_tri_bvh_dump, the boxes as built)
     {
-      // the box grown by the node part of the kernel's margin, kCullRel mt[c] (rfx_trace.h kCullRel = 2e-3), from the
+      // the box grown by the node part of the kernel's margin, kCullRel mt[c] (rfx_bundle.h kCullRel = 2e-3), from the
       // float mt the kernel would have used, with a relative 1e-6 on top
       double cd = 0.0, hd = 0.0;
       for (int k = 0; k < 3; ++k)
@@ -685,7 +685,7 @@ extern "C" int rfx_scene_tri_bvh_dump(const rfx_scene *s, int32_t counts[5], flo
 // ============================================================== coplanar mates
 // Triangle::trace (Triangle.cpp:53-108) starts with the z row of axTrans (o - v0) and of axTrans ray:
 //   aoz = (o.x - v0x) a31 + (o.y - v0y) a32 + (o.z - v0z) a33,   arz = ray.x a31 + ray.y a32 + ray.z a33,
-// and everything up to t = -aoz / arz and `t > VERY_SMALL_NUMBER` is a function of those two and the ray (rfx_trace.h
+// and everything up to t = -aoz / arz and `t > VERY_SMALL_NUMBER` is a function of those two and the ray (rfx_intersect.h
 // tri_z).  Triangles A and B are mates iff (a31, a32, a33) are finite and bitwise equal in both, all six v0 components
 // are finite, and on each axis i either v0_i is bitwise equal or a3i == 0.  Then for one ray:
 //   arz has identical operands in both, so it is identical;
@@ -926,7 +926,7 @@ SceneBuild::SceneBuild(const rfx_scene &scene, int tri_accel)
     }
     build_pair_bvh(bvh, pairs, 0, npairs, box, bvh_ref, 0, bvh_depth);
     if (bvh_depth > kBvhStack) { bvh.clear(); bvh_depth = 0; }  // deeper than the kernel's stack: chunk loops
-    if (bvh.size() > 32767 || npairs > 32768) { bvh.clear(); bvh_depth = 0; }  // int16 stack slots (rfx_trace.h)
+    if (bvh.size() > 32767 || npairs > 32768) { bvh.clear(); bvh_depth = 0; }  // int16 stack slots (rfx_bvh.h)
   }
   // triangle BVH (rfx_types.h RFX_TRI_BVH), when rfx_renderer_set_tri_accel asks for it: the nodes, the leaves' copy
   // of the triangle records and the residual list

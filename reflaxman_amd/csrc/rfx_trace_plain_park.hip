@@ -2,6 +2,7 @@
 // FrameParams::park_after segments (kCfgPark) and the bounce kernel that resumes the parked traces in packed
 // waves -- its own TU so it compiles in parallel with the other families (reflaxman_amd/_build.py).
 #include "rfx_trace.h"
+#include "rfx_parked.h"
 
 #include <atomic>
 
@@ -43,14 +44,14 @@ void launch_trace_plain_park(int cfg, dim3 grid, const DevScene &S, const FrameP
   }
 }
 
-// the bounce kernel of the parked traces (rfx_trace.h bounce_kernel)
+// the bounce kernel of the parked traces (rfx_parked.h bounce_kernel)
 template <int CFG>
 static void launch_bounce_one(dim3 grid, const DevScene &S, const FrameParams &P, hipStream_t st)
 {
   hipLaunchKernelGGL((bounce_kernel<CFG>), grid, dim3(kWgThreads), 0, st, S, P);
 }
 
-// the LDS-staged bounce kernel (large scenes, rfx_trace.h bounce_kernel_lds): one workgroup per CU
+// the LDS-staged bounce kernel (large scenes, rfx_parked.h bounce_kernel_lds): one workgroup per CU
 template <int CFG>
 static hipError_t launch_bounce_lds_one(uint32_t groups, const DevScene &S, const FrameParams &P, hipStream_t st)
 {

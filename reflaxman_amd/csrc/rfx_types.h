@@ -1,5 +1,5 @@
 // POD layouts and constants shared by the host C-ABI (rfx_host.cpp, rfx_scene.cpp) and the gfx950 kernels
-// (rfx_trace.h, rfx_kernels.hip).  All device arrays are structure-of-arrays, 16-B aligned,
+// (rfx_trace.h and the device headers it includes, rfx_kernels.hip).  All device arrays are structure-of-arrays, 16-B aligned,
 // and walked in wave-uniform order by the trace kernel, so the compiler serves
 // them through the scalar cache (s_load_dwordx4) rather than per-lane loads.
 #pragma once
@@ -42,7 +42,7 @@ struct alignas(16) TriShade {                                        // Triangle
   float t11, t12, t21, t22;   // tuvTrans _11 _12 _21 _22 (_13 = _23 = 0 by construction)
   float tv0; int32_t tex; int32_t dielectric; int32_t obj;
 };
-// Bounding sphere of an object for the wave-bundle cull (rfx_trace.h): spheres first, then triangles.
+// Bounding sphere of an object for the wave-bundle cull (rfx_bundle.h): spheres first, then triangles.
 // r = +inf marks an object that is never culled (an ill-conditioned triangle, see rfx_scene.cpp).
 struct alignas(16) Bound { float x, y, z, r; };
 // Small scenes (<= 32 spheres, <= 32 triangles): one cull record per lane of a wave.  Lanes 0-15 hold
@@ -66,9 +66,9 @@ struct alignas(16) CullTri { float v0x, v0y, v0z, nu, gux, guy, guz, nv, gvx, gv
 // the kernels' per-lane traversal stack: the host builders keep both trees within it (a deeper one: the chunk loops)
 constexpr int kBvhStack = 16;
 struct alignas(16) BvhNode { float lx[2], ly[2], lz[2], hx[2], hy[2], hz[2]; int32_t child[2]; float mt[2]; };
-// Sphere pairs per BVH leaf (rfx_scene.cpp build_pair_bvh, rfx_trace.h leaf tests): leaf ~g holds the pairs
+// Sphere pairs per BVH leaf (rfx_scene.cpp build_pair_bvh, rfx_bvh.h leaf tests): leaf ~g holds the pairs
 // [RFX_BVH_LEAF_PAIRS g, RFX_BVH_LEAF_PAIRS (g + 1)) of the device order (sph_pair padded with never-hit pairs)
-// Triangle BVH of a non-small scene (rfx_scene.cpp build_tri_tree, rfx_trace.h closest_tris_bvh / occluded_tris_bvh):
+// Triangle BVH of a non-small scene (rfx_scene.cpp build_tri_tree, rfx_bvh.h closest_tris_bvh / occluded_tris_bvh):
 // BvhNode nodes with the sphere tree's conventions (child >= 0 internal, ~g a leaf, boxes pre-widened, the same
 // margin reference point DevScene::bvh_ref), so ray_inv and bvh_box serve both trees.  Leaf ~g holds the records
 // [RFX_TRI_BVH_LEAF g, RFX_TRI_BVH_LEAF (g + 1)) of DevScene::tri_leaf: a spatially ordered copy of the triangles'
@@ -122,7 +122,7 @@ struct DevScene {
   int32_t tri_bvh_narrow;     // narrow bundles (a tile's primary rays) walk the tree too (else: the bundle-culled chunks)
 };
 
-// The bounce kernel with the BVH staged in LDS (rfx_trace.h bounce_kernel_lds): one workgroup of kLdsBvhWaves waves
+// The bounce kernel with the BVH staged in LDS (rfx_parked.h bounce_kernel_lds): one workgroup of kLdsBvhWaves waves
 // per CU; its dynamic LDS holds the node boxes (48 B each), DevScene::bvh_aux (8 B each), the lanes' traversal stacks
 // (kLdsBvhStackSlots int16 each) and one output slot (u32) per lane.
 constexpr int kLdsBvhWaves = 16, kLdsBvhStackSlots = 16;
@@ -136,7 +136,7 @@ constexpr bool lds_bvh_fits(int n_bvh) { return n_bvh > 0 && lds_bvh_bytes(n_bvh
 // A trace parked between bounce segments (large scenes, plain pixels): the state Scene::trace carries from
 // one segment to the next (Scene.cpp:80-234: origin, ray, mulColor, pixelColor, refl), the trace index of its
 // randDir and the output pixel.  64 B: one lane stores / loads it with four 16-B accesses.
-constexpr uint32_t kQueueBuckets = 4096;  // regroup sort buckets (rfx_trace.h queue_key)
+constexpr uint32_t kQueueBuckets = 4096;  // regroup sort buckets (rfx_bounce.h queue_key)
 struct alignas(16) QRay {
   float ox, oy, oz, dx;
   float dy, dz, mr, mg;
@@ -182,7 +182,7 @@ struct FrameParams {
   int32_t prim_shadow;
 };
 
-// words per wave tile of the per-view primary masks (rfx_trace.h prim_cull_kernel; the host sizes
+// words per wave tile of the per-view primary masks (rfx_prim_cull.h prim_cull_kernel; the host sizes
 // FrameParams::prim_mask by them)
 constexpr int kPrimLights = 4, kPrimStride = 1 + kPrimLights;
 // the trace and bounce kernels' CFG template bits (rfx_trace.h trace_kernel), chosen per launch by the host

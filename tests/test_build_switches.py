@@ -18,7 +18,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "reflaxman_amd", "csrc")
 CONFIG = os.path.join(CSRC, "rfx_config.h")
 
-# the flags rfx_trace.h defines itself unless RFX_NO_LAUNDER is given (a variant may also pass either alone): the one
+# the flags rfx_bounce.h defines itself unless RFX_NO_LAUNDER is given (a variant may also pass either alone): the one
 # exception to "no #define of a switch outside rfx_config.h"
 DERIVED_FROM_NO_LAUNDER = {"RFX_LAUNDER_SCENE", "RFX_LAUNDER_PARAMS"}
 
@@ -74,15 +74,16 @@ def test_no_switch_is_defined_outside_the_header():
         for m in re.finditer(r"^[ \t]*#[ \t]*define[ \t]+(\w+)", read(path), re.M):
             if m.group(1) in names:
                 second.append((os.path.basename(path), m.group(1)))
-    # a switch that takes another's value when unset has its (only) default where that value is in scope
+    # a switch that takes another's value when unset has its (only) default where that value is in scope: at trace_kernel
     assert second == [("rfx_trace.h", "RFX_WAVES_PER_EU_LARGE")], second
-    # and the exception is what it says: rfx_trace.h derives both flags under #ifndef RFX_NO_LAUNDER, nothing else does
-    trace = read(os.path.join(CSRC, "rfx_trace.h"))
-    assert "#ifndef RFX_NO_LAUNDER\n#define RFX_LAUNDER_SCENE\n#define RFX_LAUNDER_PARAMS\n#endif\n" in trace
+    # and the exception is what it says: rfx_bounce.h (the bounce loop, which reads the laundered arguments) derives both
+    # flags under #ifndef RFX_NO_LAUNDER, nothing else does
+    bounce = read(os.path.join(CSRC, "rfx_bounce.h"))
+    assert "#ifndef RFX_NO_LAUNDER\n#define RFX_LAUNDER_SCENE\n#define RFX_LAUNDER_PARAMS\n#endif\n" in bounce
     for path in sorted(glob.glob(os.path.join(CSRC, "*"))):
         if not os.path.isdir(path):
             n = len(re.findall(r"^[ \t]*#[ \t]*define[ \t]+(?:%s)\b" % "|".join(DERIVED_FROM_NO_LAUNDER), read(path), re.M))
-            assert n == (2 if os.path.basename(path) == "rfx_trace.h" else 0), path
+            assert n == (2 if os.path.basename(path) == "rfx_bounce.h" else 0), path
 
 
 @pytest.mark.parametrize("name", REMOVED)

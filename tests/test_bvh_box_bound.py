@@ -1,4 +1,4 @@
-"""The BVH box test (rfx_trace.h bvh_box, ray_inv) keeps every box a reported sphere hit can lie in.
+"""The BVH box test (rfx_bvh.h bvh_box, ray_inv) keeps every box a reported sphere hit can lie in.
 
 A sphere the reference reports as hit lies within r + 1.25e-3 |o - c| of the ray (tests/test_cull_bound.py), so a ray
 that reports a hit on a sphere inside a BVH child box passes within delta = 1.25e-3 (|o - centre| + half-diagonal) of
@@ -15,7 +15,7 @@ import numpy as np
 import pytest
 
 F = np.float32
-K_CULL_REL = F(2e-3)  # rfx_trace.h kCullRel
+K_CULL_REL = F(2e-3)  # rfx_bundle.h kCullRel
 
 
 def approx(x, rng, ulps=1.0):
@@ -29,7 +29,7 @@ def fmaf(a, b, c):
 
 
 def kept(lo, hi, o, d, ref, mt, rng):
-    """rfx_trace.h ray_inv + bvh_box for one child, in float32."""
+    """rfx_bvh.h ray_inv + bvh_box for one child, in float32."""
     e = o - ref
     dm = K_CULL_REL * (approx(np.sqrt((e * e).sum(1, dtype=F)), rng) * F(1.0001)) + F(1e-6)
     with np.errstate(divide="ignore", invalid="ignore", over="ignore"):

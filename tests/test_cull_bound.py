@@ -1,4 +1,4 @@
-"""The rounding bound behind the exact culls (rfx_trace.h kCullRel).
+"""The rounding bound behind the exact culls (rfx_bundle.h kCullRel).
 
 A bundle or BVH box may skip a sphere only if no ray the reference tests could be *reported* as hitting it.
 The reference's float test (Sphere.cpp:44-60: vco = o - c, b = 2 ray . vco, c = |vco|^2 - r^2, d = b^2 - 4ac)
@@ -12,7 +12,7 @@ hit over rays aimed within 1e-7 .. 1e-2 (relative) of the silhouettes of spheres
 import numpy as np
 
 F = np.float32
-K_CULL_REL = 2e-3        # rfx_trace.h kCullRel
+K_CULL_REL = 2e-3        # rfx_bundle.h kCullRel
 ANALYTIC = np.sqrt(26 * 2.0 ** -24)
 
 
@@ -30,7 +30,7 @@ def worst_reported_miss(n, seed):
     eps = rng.normal(0.0, 1.0, n) * np.exp(rng.uniform(np.log(1e-7), np.log(1e-2), n))
     ray = (c + w * (r * (1.0 + eps))[:, None] - o) * np.exp(rng.uniform(np.log(0.1), np.log(10.0), n))[:, None]
     o, c, ray, r = o.astype(F), c.astype(F), ray.astype(F), r.astype(F)
-    # the reference's float ops, in its order (rfx_trace.h pair_bd restates them)
+    # the reference's float ops, in its order (rfx_intersect.h pair_bd restates them)
     vx, vy, vz = o[:, 0] - c[:, 0], o[:, 1] - c[:, 1], o[:, 2] - c[:, 2]
     a = ray[:, 0] * ray[:, 0] + ray[:, 1] * ray[:, 1] + ray[:, 2] * ray[:, 2]
     b = (ray[:, 0] * F(2)) * vx + (ray[:, 1] * F(2)) * vy + (ray[:, 2] * F(2)) * vz

@@ -174,7 +174,7 @@ def test_kat_argb():
 
 def test_triangle_reject_before_divide_decides_like_the_divide():
     """Large-scene shadow rays reject plane crossings outside a triangle before the correctly rounded divide
-    (rfx_trace.h tri_hit PRE); the KAT kernel evaluates both forms and writes NaN where they disagree.  2^20 rays
+    (rfx_intersect.h tri_hit PRE); the KAT kernel evaluates both forms and writes NaN where they disagree.  2^20 rays
     aimed within a few ulp of the edges u = 0, v = 0, u + v = 1 (and at random points), from random origins and
     ray lengths: no disagreement."""
     rng = np.random.default_rng(7)
@@ -212,7 +212,7 @@ def test_triangle_reject_before_divide_decides_like_the_divide():
 @pytest.mark.parametrize("scene_name", ["default", "stress4096"])
 def test_kernarg_layout(scene_name):
     """The bounce loops read the scene record and the frame parameters through the kernarg segment pointer
-    (rfx_trace.h launder_scene / kernarg_params), assuming DevScene at offset 0 and FrameParams after it.  A kernel of
+    (rfx_bounce.h launder_scene / kernarg_params), assuming DevScene at offset 0 and FrameParams after it.  A kernel of
     the trace kernels' signature finds every word of both equal to its by-value arguments; one declared with the two
     arguments swapped finds differences, so the check would catch a kernel whose signature moved them."""
     import ctypes as C

@@ -1,4 +1,4 @@
-"""Coplanar mates on the device (rfx_trace.h TriMates): the small-scene loops compute a mate group's z stage once per
+"""Coplanar mates on the device (rfx_intersect.h TriMates): the small-scene loops compute a mate group's z stage once per
 ray.  The same scene rendered with the groups on and off (rfx_scene_set_tri_mates: off makes every triangle its own
 leader, so the kernels recompute every z stage) gives the same bits, frame after frame of the random stream, with the
 per-view masks built before the first frame and after a repeat; the frames with the groups on equal the CPU oracle's; the

@@ -71,12 +71,12 @@ def test_strictly_closer_equals_rounded_distance_compare():
         assert ref == mine, (sq, best_sq)
 
 
-K_TAKE_BELOW = F32(float.fromhex("0x1.ffffep-1"))  # rfx_trace.h kTakeBelow = 1 - 2^-20
-K_TAKE_ABOVE = F32(float.fromhex("0x1.00001p+0"))  # rfx_trace.h kTakeAbove = 1 + 2^-20
+K_TAKE_BELOW = F32(float.fromhex("0x1.ffffep-1"))  # rfx_intersect.h kTakeBelow = 1 - 2^-20
+K_TAKE_ABOVE = F32(float.fromhex("0x1.00001p+0"))  # rfx_intersect.h kTakeAbove = 1 + 2^-20
 
 
 def test_take_band_orders_rounded_distances():
-    """rfx_trace.h sph_takes / tri_takes decide outside a 2^-20 band around best_sq without square roots:
+    """rfx_intersect.h sph_takes / tri_takes decide outside a 2^-20 band around best_sq without square roots:
     sq < RN(best_sq (1 - 2^-20)) must give sqrt_rn(sq) < sqrt_rn(best_sq), sq > RN(best_sq (1 + 2^-20)) must give
     sqrt_rn(sq) > sqrt_rn(best_sq).  Checked at the band's edges (the floats just outside it) for best_sq over the
     normal range of squared distances, every significand pattern near binade edges included."""

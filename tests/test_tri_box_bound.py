@@ -1,4 +1,4 @@
-"""The BVH box test (rfx_trace.h ray_inv, bvh_box) keeps the box of every triangle a ray is reported to hit.
+"""The BVH box test (rfx_bvh.h ray_inv, bvh_box) keeps the box of every triangle a ray is reported to hit.
 
 The triangle tree (rfx_scene.cpp build_tri_tree) holds the triangles whose basis has cond < 300; a child box is the
 AABB of its triangles' vertices, widened like the sphere boxes by kCullRel (|o - centre| + half-diagonal) + 1e-6.

@@ -1,5 +1,5 @@
 """Coplanar mates (rfx_scene.cpp tri_mate_leaders, rfx.h rfx_scene_tri_mates): the host's grouping rule, bit for bit,
-and a float32 replay of the z stage of Triangle::trace (rfx_trace.h tri_z / tri_zt) showing that every member of a group
+and a float32 replay of the z stage of Triangle::trace (rfx_intersect.h tri_z / tri_zt) showing that every member of a group
 the host reports gives the same plane crossing for the same ray.  No GPU: the scene builder is host code."""
 from __future__ import annotations
 

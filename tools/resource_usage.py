@@ -6,7 +6,7 @@ lane and occupancy, from the compiler's kernel-resource-usage remarks, for every
     python tools/resource_usage.py --json OUT    # also write the table as JSON
 
 Kernel names are shortened to trace<STATS,MODE,CFG> / bounce<CFG> / bounce_lds<CFG> (the LDS-staged BVH form); CFG bits
-(rfx_trace.h kCfg*): 1 cull, 2 >32 lights, 4 small scene, 8 planes, 16 park, 32 one light.
+(rfx_types.h kCfg*): 1 cull, 2 >32 lights, 4 small scene, 8 planes, 16 park, 32 one light.
 """
 from __future__ import annotations
 
