@@ -13,7 +13,8 @@
 //
 // Differences a well-behaved caller cannot see: Scene is movable, not copyable (the reference's implicit
 // copy double-deletes, so its callers only ever assign a fresh temporary: Render.cpp:32); Sphere and
-// Triangle are handles (the caller never calls trace() on them: Scene::trace is the renderer's).
+// Triangle are handles (the caller never calls trace() on them: Scene::trace is the renderer's -- a caller that
+// wants it on rays of its own calls rfx_trace_rays on the renderer, include/rfx.h).
 #pragma once
 #include <atomic>
 #include <map>

@@ -25,7 +25,7 @@
 extern "C" {
 #endif
 
-#define RFX_ABI_VERSION 4
+#define RFX_ABI_VERSION 5
 
 typedef enum {
   RFX_OK = 0,
@@ -299,6 +299,33 @@ int rfx_frame_rng_discard(rfx_renderer *r);
  * that frame (bench.py's steady-state parity check). */
 int rfx_frame_rng_pending(rfx_renderer *r, uint32_t *frame_start);
 
+/*
+ * Ray batches: Scene::trace(origin, ray, reflNumber) (Scene.h:39, Scene.cpp:73-236) on rays the caller chose -- a
+ * panorama or fisheye camera, a lens model, a probe, a pick, a set of pixels traced again.  The call is exactly n
+ * consecutive calls Scene::trace(origin_i, ray_i, reflect_num) in index order, stream-ordered with no host sync:
+ *   d_rays : device, 6 floats per ray: origin x y z, then direction x y z (rfx_kat_objects' record).  The direction is
+ *            used as given, not normalised, as Scene::trace uses it.
+ *   d_rgb  : device, 3 floats per ray: the returned colour (overwritten, nothing accumulates)
+ *   d_argb : device uint32 per ray, Color::argb of that colour, or NULL
+ *   d_counters : device uint64[RFX_NCOUNTERS] accumulated event counters (stats kernel), or NULL
+ * Random streams: ray i takes the i-th randomInsideSphere draw of the sphere stream counted from the renderer's current
+ * state, and the stream then stands n accepted triples later; the jitter stream is not touched.  A following
+ * rfx_render_frame, or another batch, continues where the reference would after those n calls.  The pre-pass is the
+ * one an unsplit one-device rfx_render_frame launch of n traces takes (rfx_renderer_set_rng_prepass,
+ * rfx_renderer_prepass_form).  A batch is no rfx_render_frame: rfx_frame_rng_rewind after it is RFX_ERR_STATE.
+ * raster_width changes the schedule only, never a value: 0 = a wave takes 64 consecutive rays; W > 0 = the batch is a
+ * row-major W x ceil(n / W) raster (its last row may be partial) and a wave takes an 8x8 tile of it, the frame
+ * kernel's coherence, for rays that come from a camera model.  Either way ray i takes draw i and writes output i.
+ * A batch of more rays than the launch limit (rfx_renderer_set_launch_traces, rounded down to whole waves or whole
+ * tile rows of 8 W rays, and at least one) runs as consecutive launches on the one stream, the random stream running on.
+ * Errors: n == 0, NULL d_rays or d_rgb, reflect_num <= 0: RFX_ERR_ARG; no scene uploaded, or an emitted frame pending
+ * (rfx_frame_rng_emit): RFX_ERR_STATE.
+ */
+int rfx_trace_rays(rfx_renderer *r, const float *d_rays, uint64_t n, int32_t reflect_num, uint32_t raster_width,
+                   float *d_rgb, uint32_t *d_argb, uint64_t *d_counters, void *stream);
+/* The same on host arrays: copies in and out on the renderer's stream and synchronises; counters (or NULL) are added to. */
+int rfx_trace_rays_host(rfx_renderer *r, const float *rays, uint64_t n, int32_t reflect_num, uint32_t raster_width,
+                        float *rgb, uint32_t *argb, uint64_t *counters);
 /* Undo the random-stream advance of the last call, which must be an rfx_render_frame (else RFX_ERR_STATE): both
  * streams return to that frame's start, its pixels stay as written.  The drop-in Render (dropin/Render.h) renders a
  * whole frame at the first renderNext after renderBegin; when the caller leaves that frame early (renderBegin or

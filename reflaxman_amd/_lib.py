@@ -13,7 +13,7 @@ from . import _build
 
 RFX_OK = 0
 RFX_NCOUNTERS = 40
-RFX_ABI_VERSION = 4
+RFX_ABI_VERSION = 5
 METAL, DIELECTRIC = 0, 1
 
 _fp = C.POINTER(C.c_float)
@@ -97,6 +97,9 @@ SIGNATURES = [
     ("rfx_frame_rng_discard", C.c_int, [C.c_void_p]),
     ("rfx_frame_rng_pending", C.c_int, [C.c_void_p, _u32p]),
     ("rfx_frame_rng_rewind", C.c_int, [C.c_void_p]),
+    ("rfx_trace_rays", C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_int32, C.c_uint32, C.c_void_p, C.c_void_p,
+                                 C.c_void_p, C.c_void_p]),
+    ("rfx_trace_rays_host", C.c_int, [C.c_void_p, _fp, C.c_uint64, C.c_int32, C.c_uint32, _fp, _u32p, _u64p]),
     ("rfx_group_create", C.c_int, [C.POINTER(C.c_void_p), C.POINTER(C.c_int), C.c_int]),
     ("rfx_group_destroy", None, [C.c_void_p]),
     ("rfx_group_size", C.c_int, [C.c_void_p]),

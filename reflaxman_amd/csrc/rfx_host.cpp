@@ -680,6 +680,25 @@ static int run_prepass(rfx_renderer *r, FramePlan &pl, uint64_t nblk, uint32_t *
   return emit_frame(r, pl, r->blk_cnt, r->rng_masks, nblk, rd, emitted);
 }
 
+int rfx::prepass_traces(rfx_renderer *r, uint64_t n, hipStream_t st)
+{
+  int rc;
+  if ((rc = no_emitted_frame(r)) != RFX_OK) return rc;
+  r->rng.rewind_ok = false;
+  FramePlan pl;  // one device, no band, not a span of a split frame: run_prepass reads nothing else of it
+  pl.P = FrameParams{};
+  pl.P.nranks = 1;
+  pl.P.ss = 1;
+  pl.P.row_block = 1;
+  pl.traces = n;
+  pl.st = st;
+  const uint64_t nblk = rng_layout(n, 1, nullptr);
+  if ((rc = ensure_rng_workspace(r, n, nblk)) != RFX_OK) return rc;
+  if ((rc = run_prepass(r, pl, nblk, r->rd, nullptr)) != RFX_OK) return rc;
+  r->trace_buf = 0;
+  return RFX_OK;
+}
+
 // trace_frame's stages.  1: ray regrouping -- plain pixels of a large scene park their traces after park_after segments
 // in the queue set up here; the bounce kernel resumes them in packed waves (rfx_parked.h bounce_kernel).
 static int setup_regroup_queue(rfx_renderer *r, FramePlan &pl, int park_after, bool sort_queue)

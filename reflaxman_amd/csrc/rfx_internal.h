@@ -212,4 +212,8 @@ int set_dev(rfx_renderer *r);  // hipSetDevice(r->device)
 int ensure_seq_table(rfx_renderer *r, hipStream_t st);  // the cycle table, built on first use
 // the stream state a frame of several passes starts from, saved on `st` (r's device current) before the first
 int save_rewind_state(rfx_renderer *r, hipStream_t st);
+// The pre-pass of n traces that are no frame (rfx_rays.cpp), in the form an unsplit one-device frame launch of n traces
+// takes: their randDir states into r->rd on `st`, the sphere stream n accepted triples on, the jitter stream untouched.
+// Fails while an emitted frame is pending; the call cannot be undone by rfx_frame_rng_rewind.
+int prepass_traces(rfx_renderer *r, uint64_t n, hipStream_t st);
 }  // namespace rfx

@@ -65,4 +65,7 @@ RFX_DECLARE_TRACE_FAMILY(launch_trace_block_stats);
 RFX_DECLARE_TRACE_FAMILY(launch_trace_plain_park);
 RFX_DECLARE_TRACE_FAMILY(launch_bounce);
 hipError_t launch_bounce_lds(int cfg, uint32_t groups, const DevScene &S, const FrameParams &P, hipStream_t st);
+// ---- rfx_trace_rays.hip: one launch of a ray batch (rfx_rays.h trace_rays_kernel) -- P.p_end rays whose records start
+// at d_rays, P.W the raster width or 0
+hipError_t launch_trace_rays(const DevScene &S, const FrameParams &P, const float *d_rays, bool stats, hipStream_t st);
 }  // namespace rfx

@@ -345,6 +345,58 @@ class Renderer:
     def synchronize(self):
         check(_lib.load().rfx_synchronize(self._h), "rfx_synchronize")
 
+    def trace_rays(self, rays, depth: int, raster_width: int = 0, argb: bool = False, counters=None):
+        """Scene::trace on a batch of rays (rfx.h rfx_trace_rays): ``rays`` is (n, 6) float32 -- origin xyz, then the
+        direction xyz, used as given -- and the result the (n, 3) float32 colours, ray i's from the i-th
+        randomInsideSphere draw of the sphere stream.  A torch tensor on this renderer's device is traced where it
+        lies, on torch's current stream, with no host copy (and, off the legacy default stream, no synchronisation), and a
+        tensor comes back; anything
+        else goes through numpy and the host form (rfx_trace_rays_host), which synchronises.  argb: also return
+        Color::argb of every colour, as (colours, words) -- uint32 (numpy) or the same bits as int32 (torch).
+        counters: the stats kernel's RFX_NCOUNTERS event counters are added to it -- a numpy uint64 array, or a torch
+        int64 tensor on the device.  raster_width W > 0 lays the batch out as a row-major W-wide raster and gives each
+        wave an 8x8 tile of it (rays from a camera model); it changes the schedule only, never a value."""
+        L = _lib.load()
+        try:
+            import torch
+            is_torch = isinstance(rays, torch.Tensor)
+        except ImportError:
+            is_torch = False
+        if is_torch:
+            if not rays.is_cuda or rays.device.index != self.device:
+                raise ValueError("trace_rays: a tensor on the renderer's device (or a numpy array) is required")
+            r = rays.to(torch.float32).reshape(-1, 6).contiguous()
+            n = r.shape[0]
+            rgb = torch.empty((n, 3), dtype=torch.float32, device=r.device)
+            words = torch.empty(n, dtype=torch.int32, device=r.device) if argb else None
+            if counters is not None and not (isinstance(counters, torch.Tensor) and counters.is_cuda and
+                                             counters.dtype == torch.int64 and counters.is_contiguous() and
+                                             counters.numel() >= _lib.RFX_NCOUNTERS):
+                raise ValueError("trace_rays: counters must be a contiguous int64 device tensor of RFX_NCOUNTERS words")
+            # the legacy default stream has no handle to pass on (NULL is the renderer's own stream, which is not
+            # ordered with it): there the call is fenced on both sides instead; on any other stream it is asynchronous
+            stream = torch.cuda.current_stream(r.device).cuda_stream
+            if not stream:
+                torch.cuda.current_stream(r.device).synchronize()
+            check(L.rfx_trace_rays(self._h, C.c_void_p(r.data_ptr()), n, int(depth), int(raster_width),
+                                   C.c_void_p(rgb.data_ptr()), C.c_void_p(words.data_ptr() if argb else None),
+                                   C.c_void_p(counters.data_ptr() if counters is not None else None),
+                                   C.c_void_p(stream or None)), "rfx_trace_rays")
+            if not stream:
+                self.synchronize()
+            return (rgb, words) if argb else rgb
+        r = np.ascontiguousarray(rays, np.float32).reshape(-1, 6)
+        n = r.shape[0]
+        rgb = np.empty((n, 3), np.float32)
+        words = np.empty(n, np.uint32) if argb else None
+        if counters is not None and not (isinstance(counters, np.ndarray) and counters.dtype == np.uint64 and
+                                         counters.flags.c_contiguous and counters.size >= _lib.RFX_NCOUNTERS):
+            raise ValueError("trace_rays: counters must be a contiguous uint64 array of RFX_NCOUNTERS words")
+        check(L.rfx_trace_rays_host(self._h, _lib.fptr(r), n, int(depth), int(raster_width), _lib.fptr(rgb),
+                                    _lib.u32ptr(words) if argb else None,
+                                    _lib.u64ptr(counters) if counters is not None else None), "rfx_trace_rays_host")
+        return (rgb, words) if argb else rgb
+
     def set_tile_order(self, mode: int):
         """Trace-launch schedule (rfx.h rfx_renderer_set_tile_order): 1 longest-tile-first (8x8 wave tiles)
         from earlier launches' tile costs on large launches (default), 3 on every launch, 0 raster order,
@@ -635,6 +687,27 @@ class Render:
     def getRenderProgress(self) -> float:                                   # Render.cpp:223-226
         W, H = self.imageWidth, self.imageHeight
         return float(np.float32(self._curx + self._cury * W) * np.float32(100.0) / np.float32(W) / np.float32(H))
+
+    def traceRays(self, origins, rays, reflNumber: int):
+        """Scene::trace(origin, ray, reflNumber) (Scene.h:39) for every row of ``origins`` and ``rays`` ((n, 3) each, or
+        one origin for all), in order, on this object's scene: the (n, 3) colours, numpy in, numpy out; torch device
+        tensors in, a tensor out (Renderer.trace_rays).  The sphere stream moves n draws on, as after the reference's
+        n calls."""
+        if reflNumber <= 0:
+            raise ValueError("traceRays: reflNumber > 0 required (Scene::trace asserts)")
+        self._r.set_scene(self.scene)
+        try:
+            import torch
+            is_torch = isinstance(rays, torch.Tensor)
+        except ImportError:
+            is_torch = False
+        if is_torch:
+            d = rays.to(torch.float32).reshape(-1, 3)
+            o = torch.as_tensor(origins, dtype=torch.float32, device=d.device).reshape(-1, 3).expand(d.shape[0], 3)
+            return self._r.trace_rays(torch.cat([o, d], dim=1), reflNumber)
+        d = np.asarray(rays, np.float32).reshape(-1, 3)
+        o = np.broadcast_to(np.asarray(origins, np.float32).reshape(-1, 3), d.shape)
+        return self._r.trace_rays(np.concatenate([o, d], axis=1), reflNumber)
 
     def getRng(self):
         return self._r.get_rng()

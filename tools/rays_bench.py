@@ -1,0 +1,138 @@
+#!/usr/bin/env python3
+"""Ray batches against the frame path (GPU box): rfx_trace_rays on a frame's own primary rays, interleaved with
+rfx_render_frame of that frame in ONE process on ONE GPU, in the manner of tools/ab.py.
+
+    python tools/rays_bench.py --config c3 [--rounds R] [--frames F] [--out DIR]
+    python tools/rays_bench.py --config c5 ...
+
+c3: synth16 3840x2160 depth 8 (BASELINE C3); c5: stress4096 3840x2160 depth 12 (C5, the large-scene line).  The rays
+are cameras.pinhole_rays of the scene's camera, so the raster and linear batches compute the frame itself: their
+SHA-256 is checked against the reference's full-frame hash (tests/golden/manifest.json) before anything is timed.
+
+Arms (every one its own renderer on the same scene and stream; a round times F calls of each arm in turn between two
+device events, pre-pass included; medians over the rounds):
+    frame, frame_again  rfx_render_frame with the per-view masks and the tile order off (c5: regrouping off too) --
+                        the same kernel work as a batch; twice, so the pair's difference is the run's own noise band
+    raster              the batch with raster_width = W
+    linear              the batch with raster_width = 0
+    permuted            the batch in a fixed random permutation, raster_width = 0 (c3 only): what incoherent callers get
+One JSON line per arm goes to stdout and to DIR/rays_<config>.jsonl (default profiles/r12).
+"""
+import argparse
+import hashlib
+import json
+import os
+import statistics
+import sys
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+from reflaxman_amd import cameras, scenes  # noqa: E402
+from reflaxman_amd.render import Renderer, build_scene, make_frame  # noqa: E402
+
+CONFIGS = {"c3": ("synth16", 3840, 2160, 8, "hash_synth16_3840x2160_d8"),
+           "c5": ("stress4096", 3840, 2160, 12, "hash_stress4096_3840x2160_d12")}
+SEED = 1350490027
+
+
+def sha(t) -> str:
+    return hashlib.sha256(t.cpu().numpy().tobytes()).hexdigest()
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--config", choices=sorted(CONFIGS), default="c3")
+    ap.add_argument("--rounds", type=int, default=9)
+    ap.add_argument("--frames", type=int, default=0, help="calls per timed window (0: 40 for c3, 8 for c5)")
+    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "r12"))
+    args = ap.parse_args()
+    import torch
+    name, W, H, depth, key = CONFIGS[args.config]
+    frames = args.frames or (40 if args.config == "c3" else 8)
+    case = json.load(open(os.path.join(ROOT, "tests", "golden", "manifest.json")))["cases"][key]
+    scene, cam = build_scene(scenes.get_scene(name))
+    n = W * H
+    host_rays = cameras.pinhole_rays(tuple(cam.eye), cam.view, cam.fov, W, H)
+    perm = np.random.default_rng(12).permutation(n)
+    stream = torch.cuda.Stream()
+    torch.cuda.set_stream(stream)
+    rays = torch.from_numpy(host_rays).cuda()
+    rays_perm = torch.from_numpy(host_rays[perm]).cuda() if args.config == "c3" else None
+    del host_rays
+    rgb = torch.zeros((n, 3), dtype=torch.float32, device="cuda")
+    argb = torch.zeros(n, dtype=torch.int32, device="cuda")
+    frame = make_frame(cam, W, H, depth, 1)
+
+    def renderer():
+        r = Renderer(sphere_seed=SEED, jitter_seed=0)
+        r.set_stream(stream.cuda_stream)
+        r.set_scene(scene)
+        r.set_prim_masks(0)
+        r.set_tile_order(0)
+        r.set_regroup(0)
+        return r
+
+    def frame_arm():
+        r = renderer()
+        return r, lambda: r.render_frame(frame, rgb.data_ptr(), argb.data_ptr(), 0, stream.cuda_stream)
+
+    def batch_arm(src, rw):
+        from reflaxman_amd import _lib
+        import ctypes as C
+        r = renderer()
+        L = _lib.load()
+        return r, lambda: _lib.check(L.rfx_trace_rays(r._h, C.c_void_p(src.data_ptr()), n, depth, rw,
+                                                      C.c_void_p(rgb.data_ptr()), C.c_void_p(argb.data_ptr()), None,
+                                                      C.c_void_p(stream.cuda_stream)), "rfx_trace_rays")
+
+    arms = [("frame", frame_arm()), ("raster", batch_arm(rays, W)), ("linear", batch_arm(rays, 0))]
+    if rays_perm is not None:
+        arms.append(("permuted", batch_arm(rays_perm, 0)))
+    arms.append(("frame_again", frame_arm()))
+
+    # parity of every arm that computes the frame, on its first call from the seed
+    ok = {}
+    for arm, (r, call) in arms:
+        rgb.zero_()
+        argb.zero_()
+        call()
+        stream.synchronize()
+        r.synchronize()
+        if arm != "permuted":
+            ok[arm] = sha(rgb) == case["sha_f32"] and sha(argb) == case["sha_argb"]
+            if not ok[arm]:
+                raise SystemExit(f"{arm}: the output differs from {key}")
+    for arm, (r, call) in arms:  # warm-up: every later call continues the random stream, as the timed ones do
+        for _ in range(3):
+            call()
+    stream.synchronize()
+    ms = {arm: [] for arm, _ in arms}
+    for _ in range(args.rounds):
+        for arm, (r, call) in arms:
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record(stream)
+            for _ in range(frames):
+                call()
+            e1.record(stream)
+            e1.synchronize()
+            ms[arm].append(e0.elapsed_time(e1) / frames)
+    base = statistics.median(ms["frame"])
+    os.makedirs(args.out, exist_ok=True)
+    with open(os.path.join(args.out, f"rays_{args.config}.jsonl"), "w") as f:
+        for arm, (r, call) in arms:
+            med = statistics.median(ms[arm])
+            line = json.dumps({"config": args.config, "scene": name, "W": W, "H": H, "depth": depth, "arm": arm,
+                               "rounds": args.rounds, "calls_per_window": frames, "sha_ok": ok.get(arm),
+                               "ms_median": round(med, 4), "ms_min": round(min(ms[arm]), 4),
+                               "ms_max": round(max(ms[arm]), 4), "mrays_s": round(n / med / 1e3, 1),
+                               "vs_frame": round(med / base, 4)})
+            print(line)
+            f.write(line + "\n")
+            r.close()
+
+
+if __name__ == "__main__":
+    main()
