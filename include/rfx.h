@@ -333,6 +333,50 @@ int rfx_trace_rays_host(rfx_renderer *r, const float *rays, uint64_t n, int32_t 
  * so the streams end where the reference's do (Render.cpp:136-215, trace_math.h:34-39). */
 int rfx_frame_rng_rewind(rfx_renderer *r);
 
+/*
+ * Hit queries: the two questions Scene::trace asks of its objects on every segment, on rays the caller chose -- which
+ * object a ray meets and where (a pick, a depth or object-id image, a probe), and whether anything stands in a ray's
+ * way (a visibility test).  Rays are rfx_trace_rays' records, 6 floats each: origin, then the direction, used as given.
+ * Both calls are stream-ordered with no host sync, and raster_width means what it means for rfx_trace_rays: which rays
+ * share a wave (0 = 64 consecutive rays, W > 0 = an 8x8 tile of the row-major W-wide raster), never a value.  A batch
+ * above rfx_renderer_set_launch_traces runs as consecutive launches on the one stream, rounded as a ray batch's.
+ * These entries were added under RFX_ABI_VERSION 5 without raising it (nothing that existed changed): a caller that
+ * may meet an older version-5 library detects them by symbol (dlsym).
+ *
+ * rfx_query_hits: one pass of the closest-hit loop (Scene.cpp:82-107) per ray.  Every object's trace() is tested, and
+ * the winner is the reference's: strict `<` on curDist in insertion order, so among equal distances the lowest object
+ * index wins.  Each plane of rfx_hit_planes is a device array or NULL (not wanted; at least one is wanted).  Every
+ * word of every requested plane is written -- on a miss object = -1, distance = FLT_MAX and the 3-float planes 0 --
+ * and nothing else is.  Planes need 4-B alignment only.
+ *
+ * rfx_query_occluded: d_occluded[i] = 1 if any object other than d_skip[i] returns true from
+ * trace(origin, ray, NULL, ...) (Scene.cpp:133-143), else 0.  The ray is unbounded, as the reference's shadow ray is:
+ * an object beyond the light still occludes it.  A segment test is rfx_query_hits' distance against the segment's
+ * length.  d_skip NULL skips nothing, and so does a value outside [0, objects).
+ *
+ * Neither call touches the random streams (there is no pre-pass: rfx_renderer_get_rng reads the same before and
+ * after), the per-view masks, the tile costs, the regroup queue, the timing sums, or what rfx_frame_rng_rewind may
+ * undo: a rewind after "frame, then query" still succeeds.
+ * Errors: NULL renderer, rays, out or d_occluded, all planes NULL, n == 0: RFX_ERR_ARG; no scene uploaded: RFX_ERR_STATE.
+ */
+typedef struct {          /* one plane per output, each may be NULL (not wanted); at least one non-NULL */
+  int32_t *object;        /* n    : object index as the add call returned it (insertion order); -1 = no hit */
+  float   *distance;      /* n    : curDist of the winner (Scene.cpp:98-100); FLT_MAX on a miss (Scene.cpp:82) */
+  float   *point;         /* 3 n  : drop */
+  float   *normal;        /* 3 n  : norm as the object returns it (not normalised) */
+  float   *reflected;     /* 3 n  : reflect(ray * t, norm) */
+  float   *colour;        /* 3 n  : dropMaterial.color: the material's, or a textured triangle's texel */
+} rfx_hit_planes;
+int rfx_query_hits(rfx_renderer *r, const float *d_rays, uint64_t n, uint32_t raster_width,
+                   const rfx_hit_planes *out, void *stream);
+int rfx_query_occluded(rfx_renderer *r, const float *d_rays, const int32_t *d_skip, uint64_t n,
+                       uint32_t raster_width, uint8_t *d_occluded, void *stream);
+/* The same on host arrays: they copy in and out on the renderer's stream and synchronise. */
+int rfx_query_hits_host(rfx_renderer *r, const float *rays, uint64_t n, uint32_t raster_width,
+                        const rfx_hit_planes *out /* host pointers */);
+int rfx_query_occluded_host(rfx_renderer *r, const float *rays, const int32_t *skip, uint64_t n,
+                            uint32_t raster_width, uint8_t *occluded);
+
 /* ---------------------------------------------------------------- Device groups (multi-GPU, one process)
  * A group renders the frame of Render::renderNext (Render.cpp:136-215) on several devices of this process: row bands,
  * one per member, each member counting its slice of the frame's random stream and pushing it to the others (the one

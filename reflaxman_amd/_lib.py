@@ -44,6 +44,11 @@ class AccelInfo(C.Structure):
                                          "sph_nodes", "sph_depth", "narrow_tri_bvh")]
 
 
+class HitPlanes(C.Structure):
+    """rfx_hit_planes (include/rfx.h): one device (or, for the host form, host) pointer per output, 0 = not wanted."""
+    _fields_ = [(n, C.c_void_p) for n in ("object", "distance", "point", "normal", "reflected", "colour")]
+
+
 _i32p = C.POINTER(C.c_int32)
 
 # (name, restype, argtypes) for every symbol of include/rfx.h
@@ -100,6 +105,10 @@ SIGNATURES = [
     ("rfx_trace_rays", C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_int32, C.c_uint32, C.c_void_p, C.c_void_p,
                                  C.c_void_p, C.c_void_p]),
     ("rfx_trace_rays_host", C.c_int, [C.c_void_p, _fp, C.c_uint64, C.c_int32, C.c_uint32, _fp, _u32p, _u64p]),
+    ("rfx_query_hits", C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32, C.POINTER(HitPlanes), C.c_void_p]),
+    ("rfx_query_hits_host", C.c_int, [C.c_void_p, _fp, C.c_uint64, C.c_uint32, C.POINTER(HitPlanes)]),
+    ("rfx_query_occluded", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32, C.c_void_p, C.c_void_p]),
+    ("rfx_query_occluded_host", C.c_int, [C.c_void_p, _fp, _i32p, C.c_uint64, C.c_uint32, C.POINTER(C.c_uint8)]),
     ("rfx_group_create", C.c_int, [C.POINTER(C.c_void_p), C.POINTER(C.c_int), C.c_int]),
     ("rfx_group_destroy", None, [C.c_void_p]),
     ("rfx_group_size", C.c_int, [C.c_void_p]),

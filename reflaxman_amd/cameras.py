@@ -49,6 +49,16 @@ def pinhole_rays(eye, view, fov: float, W: int, H: int) -> np.ndarray:
     return _records(eye, d)
 
 
+def pinhole_ray(eye, view, fov: float, W: int, H: int, x: int, y: int) -> np.ndarray:
+    """The one record of ``pinhole_rays`` for pixel (x, y) (row 0 = bottom), by the same float32 operations: what a
+    pick under that pixel traces (Render.pick)."""
+    m = np.asarray(view, np.float32).reshape(3, 3)
+    rz = camera_rz(W, fov)
+    fx, fy = f32(x) - f32(W) / f32(2.0), f32(y) - f32(H) / f32(2.0)
+    d = np.array([[(fx * m[k, 0] + fy * m[k, 1]) + rz * m[k, 2] for k in range(3)]], np.float32)
+    return _records(eye, d)[0]
+
+
 def equirect_rays(eye, W: int, H: int) -> np.ndarray:
     """A 360 x 180 degree panorama from ``eye``: column x looks at longitude (x + 1/2) / W of a turn, measured from +z
     towards +x, row y (row 0 = bottom) at latitude ((y + 1/2) / H - 1/2) pi; unit directions, pixel centres, so no ray

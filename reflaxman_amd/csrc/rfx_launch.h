@@ -68,4 +68,7 @@ hipError_t launch_bounce_lds(int cfg, uint32_t groups, const DevScene &S, const 
 // ---- rfx_trace_rays.hip: one launch of a ray batch (rfx_rays.h trace_rays_kernel) -- P.p_end rays whose records start
 // at d_rays, P.W the raster width or 0
 hipError_t launch_trace_rays(const DevScene &S, const FrameParams &P, const float *d_rays, bool stats, hipStream_t st);
+// ---- rfx_trace_hits.hip: one launch of a hit query (rfx_hits.h) -- P.n rays; any: the any-hit kernel, else the
+// closest-hit one
+hipError_t launch_query_hits(const DevScene &S, const HitParams &P, bool any, hipStream_t st);
 }  // namespace rfx

@@ -182,6 +182,19 @@ struct FrameParams {
   int32_t prim_shadow;
 };
 
+// One launch of a hit query (rfx_hits.h query_hits_kernel, query_occluded_kernel; rfx_hits.cpp fills it): rays [0, n)
+// of the pointers below -- in a batch of several launches every pointer starts at the launch's first ray.
+struct HitParams {
+  const float *rays;     // 6 floats per ray: origin, direction
+  const int32_t *skip;   // any-hit: the object each ray leaves out, or null
+  uint64_t n;
+  uint32_t W;            // 0 = a wave per 64 consecutive rays, else a wave per 8x8 tile of the W-wide raster
+  // closest hit: one plane per output, null = not wanted
+  int32_t *object;
+  float *distance, *point, *normal, *reflected, *colour;
+  uint8_t *occluded;     // any-hit: one byte per ray
+};
+
 // words per wave tile of the per-view primary masks (rfx_prim_cull.h prim_cull_kernel; the host sizes
 // FrameParams::prim_mask by them)
 constexpr int kPrimLights = 4, kPrimStride = 1 + kPrimLights;

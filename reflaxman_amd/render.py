@@ -397,6 +397,90 @@ class Renderer:
                                     _lib.u64ptr(counters) if counters is not None else None), "rfx_trace_rays_host")
         return (rgb, words) if argb else rgb
 
+    HIT_PLANES = ("object", "distance", "point", "normal", "reflected", "colour")
+
+    def _ray_batch(self, rays, what):
+        """(is_torch, the (n, 6) float32 records, torch's current stream handle or None)."""
+        try:
+            import torch
+            is_torch = isinstance(rays, torch.Tensor)
+        except ImportError:
+            is_torch = False
+        if not is_torch:
+            return False, np.ascontiguousarray(rays, np.float32).reshape(-1, 6), None
+        if not rays.is_cuda or rays.device.index != self.device:
+            raise ValueError(f"{what}: a tensor on the renderer's device (or a numpy array) is required")
+        r = rays.to(torch.float32).reshape(-1, 6).contiguous()
+        # the legacy default stream has no handle to pass on (trace_rays): there the call is fenced on both sides
+        stream = torch.cuda.current_stream(r.device).cuda_stream
+        if not stream:
+            torch.cuda.current_stream(r.device).synchronize()
+        return True, r, stream
+
+    def query_hits(self, rays, raster_width: int = 0, want=HIT_PLANES):
+        """The closest hit of every ray (rfx.h rfx_query_hits: one pass of Scene.cpp:82-107): a dict of the planes
+        named in ``want`` -- object (n, int32, -1 = no hit), distance (n, FLT_MAX on a miss), point, normal, reflected,
+        colour ((n, 3), zero on a miss).  ``rays`` as for trace_rays: a torch tensor on this renderer's device is
+        queried where it lies, on torch's current stream, and tensors come back; anything else goes through numpy and
+        the host form, which synchronises.  No random stream moves."""
+        want = tuple(want)
+        if not want or any(k not in self.HIT_PLANES for k in want):
+            raise ValueError(f"query_hits: want names at least one of {self.HIT_PLANES}")
+        L = _lib.load()
+        is_torch, r, stream = self._ray_batch(rays, "query_hits")
+        n = r.shape[0]
+        shape = lambda k: (n,) if k in ("object", "distance") else (n, 3)
+        hp = _lib.HitPlanes()
+        if is_torch:
+            import torch
+            out = {k: torch.empty(shape(k), dtype=torch.int32 if k == "object" else torch.float32, device=r.device)
+                   for k in want}
+            for k in want:
+                setattr(hp, k, out[k].data_ptr())
+            check(L.rfx_query_hits(self._h, C.c_void_p(r.data_ptr()), n, int(raster_width), C.byref(hp),
+                                   C.c_void_p(stream or None)), "rfx_query_hits")
+            if not stream:
+                self.synchronize()
+            return out
+        out = {k: np.empty(shape(k), np.int32 if k == "object" else np.float32) for k in want}
+        for k in want:
+            setattr(hp, k, out[k].ctypes.data)
+        check(L.rfx_query_hits_host(self._h, _lib.fptr(r), n, int(raster_width), C.byref(hp)), "rfx_query_hits_host")
+        return out
+
+    def occluded(self, rays, skip=None, raster_width: int = 0):
+        """Whether anything stands in each ray's way (rfx.h rfx_query_occluded, the shadow rays' any-hit of
+        Scene.cpp:133-143): (n,) uint8, 1 = some object other than ``skip[i]`` is hit.  The ray is unbounded.  skip:
+        (n,) int32 object indices (None, or a value outside [0, objects): nothing is left out), of the kind ``rays``
+        is -- a device tensor with a device tensor, else numpy."""
+        L = _lib.load()
+        is_torch, r, stream = self._ray_batch(rays, "occluded")
+        n = r.shape[0]
+        if is_torch:
+            import torch
+            sk = None
+            if skip is not None:
+                sk = torch.as_tensor(skip, device=r.device).to(torch.int32).reshape(-1).contiguous()
+                if sk.numel() != n:
+                    raise ValueError("occluded: one skip entry per ray")
+            occ = torch.empty(n, dtype=torch.uint8, device=r.device)
+            check(L.rfx_query_occluded(self._h, C.c_void_p(r.data_ptr()), C.c_void_p(sk.data_ptr() if sk is not None else None),
+                                       n, int(raster_width), C.c_void_p(occ.data_ptr()), C.c_void_p(stream or None)),
+                  "rfx_query_occluded")
+            if not stream:
+                self.synchronize()
+            return occ
+        sk = None
+        if skip is not None:
+            sk = np.ascontiguousarray(skip, np.int32).reshape(-1)
+            if sk.size != n:
+                raise ValueError("occluded: one skip entry per ray")
+        occ = np.empty(n, np.uint8)
+        check(L.rfx_query_occluded_host(self._h, _lib.fptr(r), sk.ctypes.data_as(_lib._i32p) if sk is not None else None,
+                                        n, int(raster_width), occ.ctypes.data_as(C.POINTER(C.c_uint8))),
+              "rfx_query_occluded_host")
+        return occ
+
     def set_tile_order(self, mode: int):
         """Trace-launch schedule (rfx.h rfx_renderer_set_tile_order): 1 longest-tile-first (8x8 wave tiles)
         from earlier launches' tile costs on large launches (default), 3 on every launch, 0 raster order,
@@ -708,6 +792,18 @@ class Render:
         d = np.asarray(rays, np.float32).reshape(-1, 3)
         o = np.broadcast_to(np.asarray(origins, np.float32).reshape(-1, 3), d.shape)
         return self._r.trace_rays(np.concatenate([o, d], axis=1), reflNumber)
+
+    def pick(self, x: int, y: int):
+        """What lies under pixel (x, y) of the current camera and image size (row 0 = bottom): (object index as the add
+        call returned it, or -1 for the sky; its distance from the eye, |ray t| -- FLT_MAX for the sky).  The ray is cameras.pinhole_ray's, the pixel loop's own (Render.cpp:146-156)."""
+        from . import cameras
+        W, H = self.imageWidth, self.imageHeight
+        if not (0 <= x < W and 0 <= y < H):
+            raise ValueError("pick: the pixel lies outside the image")
+        self._r.set_scene(self.scene)
+        ray = cameras.pinhole_ray(tuple(self.camera.eye), self.camera.view, self.camera.fov, W, H, x, y)
+        out = self._r.query_hits(ray[None, :], want=("object", "distance"))
+        return int(out["object"][0]), float(out["distance"][0])
 
     def getRng(self):
         return self._r.get_rng()

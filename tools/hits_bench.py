@@ -1,0 +1,162 @@
+#!/usr/bin/env python3
+"""Hit queries against a depth-1 ray batch (GPU box): rfx_query_hits / rfx_query_occluded on a frame's own primary
+rays, interleaved with rfx_trace_rays at reflect_num 1 in ONE process on ONE GPU, in the manner of tools/rays_bench.py.
+
+    python tools/hits_bench.py --config c3 [--rounds R] [--calls F] [--out DIR]
+    python tools/hits_bench.py --config c5 ...
+
+c3: synth16 3840x2160; c5: stress4096 3840x2160.  The rays are cameras.pinhole_rays of the scene's camera.  Before
+anything is timed, the object plane's miss count must equal the number of pixels whose depth-1 colour (rfx_trace_rays)
+is the sky's (sky_pixels below); the any-hit must count the remaining pixels, and the raster and permuted batches must
+give the linear batch's objects.
+
+Arms (every one its own renderer on the same scene and stream; a round times F calls of each arm in turn between two
+device events; medians over the rounds):
+    trace_d1, trace_d1_again   rfx_trace_rays at reflect_num 1, raster -- what a caller had for this question before,
+                               pre-pass included; twice, so the pair's difference is the run's own noise band
+    hits_raster / hits_linear / hits_permuted   rfx_query_hits, all six planes (56 B out per ray): raster_width = W,
+                               0, and 0 on a fixed random permutation of the rays
+    hits_object                rfx_query_hits, the object plane alone (4 B out per ray), raster
+    occluded                   rfx_query_occluded, nothing left out, raster
+One JSON line per arm goes to stdout and to DIR/hits_<config>.jsonl (default profiles/r13).
+"""
+import argparse
+import ctypes as C
+import json
+import os
+import statistics
+import sys
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+from reflaxman_amd import _lib, cameras, scenes  # noqa: E402
+from reflaxman_amd.render import Renderer, build_scene  # noqa: E402
+
+CONFIGS = {"c3": ("synth16", 3840, 2160), "c5": ("stress4096", 3840, 2160)}
+SEED = 1350490027
+PLANES = ("object", "distance", "point", "normal", "reflected", "colour")
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--config", choices=sorted(CONFIGS), default="c3")
+    ap.add_argument("--rounds", type=int, default=9)
+    ap.add_argument("--calls", type=int, default=20, help="calls per timed window")
+    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "r13"))
+    args = ap.parse_args()
+    import torch
+    name, W, H = CONFIGS[args.config]
+    desc = scenes.get_scene(name)
+    scene, cam = build_scene(desc)
+    n = W * H
+    host_rays = cameras.pinhole_rays(tuple(cam.eye), cam.view, cam.fov, W, H)
+    dirs = np.ascontiguousarray(host_rays[:, 3:6])
+    perm = np.random.default_rng(12).permutation(n)
+    stream = torch.cuda.Stream()
+    torch.cuda.set_stream(stream)
+    rays = torch.from_numpy(host_rays).cuda()
+    rays_perm = torch.from_numpy(host_rays[perm]).cuda()
+    del host_rays
+    rgb = torch.zeros((n, 3), dtype=torch.float32, device="cuda")
+    out = {k: torch.zeros((n,) if k in ("object", "distance") else (n, 3),
+                          dtype=torch.int32 if k == "object" else torch.float32, device="cuda") for k in PLANES}
+    occ = torch.zeros(n, dtype=torch.uint8, device="cuda")
+    L = _lib.load()
+    sp = C.c_void_p(stream.cuda_stream)
+
+    def renderer():
+        r = Renderer(sphere_seed=SEED, jitter_seed=0)
+        r.set_stream(stream.cuda_stream)
+        r.set_scene(scene)
+        return r
+
+    def trace_arm():
+        r = renderer()
+        return r, lambda: _lib.check(L.rfx_trace_rays(r._h, C.c_void_p(rays.data_ptr()), n, 1, W,
+                                                      C.c_void_p(rgb.data_ptr()), None, None, sp), "rfx_trace_rays")
+
+    def hits_arm(src, rw, want):
+        r = renderer()
+        hp = _lib.HitPlanes(**{k: out[k].data_ptr() for k in want})
+        return r, lambda: _lib.check(L.rfx_query_hits(r._h, C.c_void_p(src.data_ptr()), n, rw, C.byref(hp), sp),
+                                     "rfx_query_hits")
+
+    def occ_arm():
+        r = renderer()
+        return r, lambda: _lib.check(L.rfx_query_occluded(r._h, C.c_void_p(rays.data_ptr()), None, n, W,
+                                                          C.c_void_p(occ.data_ptr()), sp), "rfx_query_occluded")
+
+    arms = [("trace_d1", trace_arm(), 12), ("hits_raster", hits_arm(rays, W, PLANES), 56),
+            ("hits_linear", hits_arm(rays, 0, PLANES), 56), ("hits_permuted", hits_arm(rays_perm, 0, PLANES), 56),
+            ("hits_object", hits_arm(rays, W, ("object",)), 4), ("occluded", occ_arm(), 1),
+            ("trace_d1_again", trace_arm(), 12)]
+
+    # the check before timing: misses of the object plane = sky-coloured pixels of the depth-1 frame; with it, the
+    # any-hit of the same rays counts the hits, and the permuted batch is the linear one, permuted
+    by = {a: rc for a, rc, _ in arms}
+    for a in ("trace_d1", "hits_linear", "occluded"):
+        by[a][1]()
+    stream.synchronize()
+    lin_obj = out["object"].clone()
+    misses = int((lin_obj < 0).sum())
+    occluded_n = int(occ.sum())
+    sky = sky_pixels(by["trace_d1"][0], desc, dirs, rgb.cpu().numpy())
+    by["hits_permuted"][1]()
+    stream.synchronize()
+    perm_ok = bool(torch.equal(out["object"], lin_obj[torch.from_numpy(perm).cuda()]))
+    by["hits_object"][1]()
+    stream.synchronize()
+    raster_ok = bool(torch.equal(out["object"], lin_obj))
+    check = {"misses": misses, "sky_pixels": sky, "occluded": occluded_n, "permuted_equal": perm_ok,
+             "raster_equal": raster_ok}
+    if misses != sky or n - misses != occluded_n or not (perm_ok and raster_ok):
+        raise SystemExit(f"hits_bench: the check before timing failed: {check}")
+
+    for arm, (r, call), _ in arms:
+        for _ in range(3):
+            call()
+    stream.synchronize()
+    ms = {arm: [] for arm, _, _ in arms}
+    for _ in range(args.rounds):
+        for arm, (r, call), _ in arms:
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record(stream)
+            for _ in range(args.calls):
+                call()
+            e1.record(stream)
+            e1.synchronize()
+            ms[arm].append(e0.elapsed_time(e1) / args.calls)
+    base = statistics.median(ms["trace_d1"])
+    os.makedirs(args.out, exist_ok=True)
+    with open(os.path.join(args.out, f"hits_{args.config}.jsonl"), "w") as f:
+        for arm, (r, call), nbytes in arms:
+            med = statistics.median(ms[arm])
+            line = json.dumps({"config": args.config, "scene": name, "W": W, "H": H, "arm": arm, "rounds": args.rounds,
+                               "calls_per_window": args.calls, "out_bytes_per_ray": nbytes, "check": check,
+                               "ms_median": round(med, 4), "ms_min": round(min(ms[arm]), 4),
+                               "ms_max": round(max(ms[arm]), 4), "mrays_s": round(n / med / 1e3, 1),
+                               "vs_trace_d1": round(med / base, 4)})
+            print(line)
+            f.write(line + "\n")
+            r.close()
+
+
+def sky_pixels(r, desc, dirs, rgb) -> int:
+    """Pixels of the depth-1 frame ``rgb`` whose colour is the sky's.  A miss at depth 1 returns
+    clamp(skybox texel x envColor) (Scene.cpp:226-231) and a hit a shaded colour, so a pixel counts as sky when its
+    colour is that product for its own ray: the texel from the library's skybox known-answer entry, envColor
+    summed as Scene.cpp:12,55 sums it (diffuse colour x power, then every light's colour x power), in float32."""
+    f32 = np.float32
+    texel = r.kat_texels(-1, dirs)
+    env = np.array(desc.diffuse[:3], f32) * f32(desc.diffuse[3])
+    for (_, _, c, power) in desc.lights:
+        env = env + np.array(c, f32) * f32(power)
+    sky = np.clip(texel * env[None, :] + f32(0.0), f32(0.0), f32(1.0)).astype(f32)
+    return int((rgb.reshape(-1, 3).view(np.uint32) == sky.view(np.uint32)).all(axis=1).sum())
+
+
+if __name__ == "__main__":
+    main()

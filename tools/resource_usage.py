@@ -5,8 +5,9 @@ lane and occupancy, from the compiler's kernel-resource-usage remarks, for every
     python tools/resource_usage.py [TU ...]      # default: the plain-mode translation units
     python tools/resource_usage.py --json OUT    # also write the table as JSON
 
-Kernel names are shortened to trace<STATS,MODE,CFG> / bounce<CFG> / bounce_lds<CFG> (the LDS-staged BVH form); CFG bits
-(rfx_types.h kCfg*): 1 cull, 2 >32 lights, 4 small scene, 8 planes, 16 park, 32 one light.
+Kernel names are shortened to trace<STATS,MODE,CFG> / bounce<CFG> / bounce_lds<CFG> (the LDS-staged BVH form) /
+query_hits<CFG> / query_occluded<CFG> (rfx_trace_hits.hip); CFG bits (rfx_types.h kCfg*): 1 cull, 2 >32 lights, 4 small
+scene, 8 planes, 16 park, 32 one light, 64 triangle BVH.
 """
 from __future__ import annotations
 
@@ -37,6 +38,9 @@ def short(name: str) -> str:
     m = re.match(r"_ZN3rfx17bounce_kernel_ldsILi(\d+)EEEv", name)
     if m:
         return f"bounce_lds<{m.group(1)}>"
+    m = re.match(r"_ZN3rfx(?:17query_hits|21query_occluded)_kernelILi(\d+)EEEv", name)
+    if m:
+        return f"{'query_hits' if 'query_hits' in name else 'query_occluded'}<{m.group(1)}>"
     return name
 
 
@@ -59,7 +63,7 @@ def usage(tu: str):
             out.append(cur)
         elif cur is not None and key in FIELDS:
             cur[FIELDS[key]] = int(val)
-    return [k for k in out if k["kernel"].startswith(("trace<", "bounce<", "bounce_lds<"))]
+    return [k for k in out if k["kernel"].startswith(("trace<", "bounce<", "bounce_lds<", "query_hits<", "query_occluded<"))]
 
 
 def main():
@@ -68,10 +72,10 @@ def main():
     ap.add_argument("--json", default=None)
     args = ap.parse_args()
     rows = [k for tu in args.tus for k in usage(tu)]
-    print(f"{'kernel':28s} {'vgpr':>5s} {'spill':>6s} {'sgpr_sp':>7s} {'scratch':>8s} {'occ':>4s}")
+    print(f"{'kernel':28s} {'vgpr':>5s} {'spill':>6s} {'sgpr_sp':>7s} {'scratch':>8s} {'occ':>4s} {'lds':>6s}")
     for k in rows:
         print(f"{k['kernel']:28s} {k.get('vgpr', 0):5d} {k.get('vgpr_spill', 0):6d} {k.get('sgpr_spill', 0):7d} "
-              f"{k.get('scratch', 0):8d} {k.get('occ', 0):4d}")
+              f"{k.get('scratch', 0):8d} {k.get('occ', 0):4d} {k.get('lds', 0):6d}")
     if args.json:
         os.makedirs(os.path.dirname(os.path.abspath(args.json)), exist_ok=True)
         json.dump(rows, open(args.json, "w"), indent=1)
