@@ -377,6 +377,70 @@ int rfx_query_hits_host(rfx_renderer *r, const float *rays, uint64_t n, uint32_t
 int rfx_query_occluded_host(rfx_renderer *r, const float *rays, const int32_t *skip, uint64_t n,
                             uint32_t raster_width, uint8_t *occluded);
 
+/*
+ * Coherent order: rfx_trace_rays and the hit queries run one lane per ray, and a wave is fast only when its 64 rays are
+ * alike.  Rays from bounces, probes or a sampler are not.  rfx_rays_order sorts a batch's indices by a 32-bit key of
+ * origin cell and direction, and the ordered calls below run wave w on the rays d_order[64 w .. 64 w + 63] -- the
+ * values, the outputs' places and the random draws stay those of the unordered calls.  Added under RFX_ABI_VERSION 5
+ * without raising it, as the hit queries were: detect by symbol (dlsym).
+ *
+ * The key, key = cellMorton << (2 DB) | dirMorton with CB = RFX_ORDER_CELL_BITS and DB = RFX_ORDER_DIR_BITS, origin
+ * major (rays from one place lie together, then go by direction).  Every operation below is an IEEE float32 one with no
+ * contraction, so a float32 restatement gives the same bits (tests/order_helpers.py):
+ *   box    : per axis, lo = the minimum over the spheres' centre - radius and the triangles' vertices, hi = the maximum
+ *            over centre + radius and the vertices (float32, insertion order, a NaN never taken); scale = 2^CB / (hi - lo)
+ *            where hi > lo and both are finite, else scale = 0 (and a lo that is not finite is given as 0).  Planes do
+ *            not count; a scene with neither spheres nor triangles has scale 0.  Computed by rfx_renderer_set_scene.
+ *   cell   : c_a = (uint32) fminf(fmaxf((o_a - lo_a) * scale_a, 0), 2^CB - 1) -- a NaN takes the 0 --; cellMorton has
+ *            bit b of c_x at 3 b, of c_y at 3 b + 1, of c_z at 3 b + 2.
+ *   dir    : the octahedral map.  a = (|dx| + |dy|) + |dz|, px = dx / a, py = dy / a; if dz < 0:
+ *            qx = (1 - |py|) * (px < 0 ? -1 : 1), qy = (1 - |px|) * (py < 0 ? -1 : 1), else (qx, qy) = (px, py);
+ *            u = (uint32) fminf(fmaxf((qx + 1) * 2^(DB - 1), 0), 2^DB - 1), v likewise from qy; dirMorton has bit b of
+ *            u at 2 b, of v at 2 b + 1.  Zero, infinite and NaN directions fall out of these expressions as they stand
+ *            (to cell 0 or a clamped cell): that is part of the definition.
+ */
+#define RFX_ORDER_CELL_BITS 4
+#define RFX_ORDER_DIR_BITS 10
+/* rays one workgroup of the sort takes per digit pass (the sizes at which the sort's paths change) */
+#define RFX_ORDER_TILE 4096
+/* The key's box of the uploaded scene; RFX_ERR_STATE without one. */
+int rfx_renderer_order_box(const rfx_renderer *r, float lo[3], float scale[3]);
+/*
+ * d_order[0 .. n) becomes the permutation of [0, n) with nondecreasing keys, equal keys in index order (a stable sort:
+ * the result is a function of the rays alone); d_keys[i], where given, is ray i's key (ray order, not sorted order).
+ * Stream-ordered, no host sync.  A stable LSD radix sort of (key, index) pairs, 8 bits a pass: per-workgroup digit
+ * histograms, one scan over (digit, workgroup), a stable scatter; no kernel waits on another workgroup.  The scratch
+ * (ping-pong keys and indices, histograms) is the renderer's own and grows on demand: two order calls of one renderer
+ * on streams that are not ordered with each other are the caller's error.  The call touches nothing a frame, a batch
+ * or a query keeps: no random stream, no masks, no tile costs, nothing rfx_frame_rng_rewind may undo.
+ * Errors: n == 0, n >= 2^31, NULL renderer, rays or order: RFX_ERR_ARG; no scene uploaded: RFX_ERR_STATE.
+ */
+int rfx_rays_order(rfx_renderer *r, const float *d_rays, uint64_t n, uint32_t *d_order, uint32_t *d_keys /* or NULL */,
+                   void *stream);
+/* The same on host arrays: copies in and out on the renderer's stream and synchronises. */
+int rfx_rays_order_host(rfx_renderer *r, const float *rays, uint64_t n, uint32_t *order, uint32_t *keys /* or NULL */);
+/*
+ * The ordered calls: rfx_trace_rays, rfx_query_hits and rfx_query_occluded with the schedule given by d_order (n
+ * uint32 on the device) instead of raster_width.  Wave w takes slots 64 w .. 64 w + 63, and slot s works on ray
+ * i = d_order[s]; everything per ray is indexed by i -- the record, d_skip[i], every output, and, for the trace, draw i
+ * of the sphere stream.  For a permutation the results and the stream's end state are therefore word for word those of
+ * the unordered call: d_order only moves work between waves.  It need not come from rfx_rays_order.  It must be a
+ * permutation of [0, n); that is not checked, but it is made safe: a slot whose index is >= n is a dead lane that reads
+ * and writes nothing (an index named twice is traced twice and written twice with the same value; an index never named
+ * leaves its outputs unwritten).  Outputs leave per lane (12-B and 4-B stores); there is no counters form.
+ * The hit queries above the launch limit (rfx_renderer_set_launch_traces) run as consecutive slot ranges over the whole
+ * arrays.  The ordered trace above it is RFX_ERR_ARG, returned before any stream advances: the renderer's randDir
+ * state covers that many rays and an ordered launch may name any ray, so a caller splits such a batch and orders each
+ * part.  The other errors are the unordered calls' (NULL d_order, or n >= 2^32: RFX_ERR_ARG), RFX_ERR_STATE with an
+ * emitted frame pending included.
+ */
+int rfx_trace_rays_ordered(rfx_renderer *r, const float *d_rays, const uint32_t *d_order, uint64_t n,
+                           int32_t reflect_num, float *d_rgb, uint32_t *d_argb, void *stream);
+int rfx_query_hits_ordered(rfx_renderer *r, const float *d_rays, const uint32_t *d_order, uint64_t n,
+                           const rfx_hit_planes *out, void *stream);
+int rfx_query_occluded_ordered(rfx_renderer *r, const float *d_rays, const int32_t *d_skip, const uint32_t *d_order,
+                               uint64_t n, uint8_t *d_occluded, void *stream);
+
 /* ---------------------------------------------------------------- Device groups (multi-GPU, one process)
  * A group renders the frame of Render::renderNext (Render.cpp:136-215) on several devices of this process: row bands,
  * one per member, each member counting its slice of the frame's random stream and pushing it to the others (the one

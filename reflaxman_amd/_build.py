@@ -20,7 +20,8 @@ INCLUDE = os.path.join(ROOT, "include")
 
 # the trace kernel families compile as separate TUs in parallel (one hipcc per source), then link
 SOURCES = ["rfx_kernels.hip", "rfx_host.cpp", "rfx_scene.cpp", "rfx_group.cpp", "rfx_kat.cpp", "rfx_rays.cpp", "rfx_trace_rays.hip",
-           "rfx_hits.cpp", "rfx_trace_hits.hip", "rfx_trace_plain_park.hip"] + [
+           "rfx_hits.cpp", "rfx_trace_hits.hip", "rfx_order.cpp", "rfx_order_sort.hip", "rfx_trace_ordered.hip",
+           "rfx_trace_plain_park.hip"] + [
     f"rfx_trace_{m}_{s}.hip" for m in ("plain", "ssaa", "lanes", "chunks", "block") for s in ("fast", "stats")]
 HEADERS = sorted(f for f in os.listdir(CSRC) if f.endswith(".h"))  # every header counts towards _sources_digest
 ARCH = os.environ.get("PYTORCH_ROCM_ARCH", "gfx950").split(";")[0] or "gfx950"

@@ -14,6 +14,8 @@ from . import _build
 RFX_OK = 0
 RFX_NCOUNTERS = 40
 RFX_ABI_VERSION = 5
+# the coherent order's key widths and the sort's rays per workgroup (rfx.h "Coherent order")
+RFX_ORDER_CELL_BITS, RFX_ORDER_DIR_BITS, RFX_ORDER_TILE = 4, 10, 4096
 METAL, DIELECTRIC = 0, 1
 
 _fp = C.POINTER(C.c_float)
@@ -109,6 +111,15 @@ SIGNATURES = [
     ("rfx_query_hits_host", C.c_int, [C.c_void_p, _fp, C.c_uint64, C.c_uint32, C.POINTER(HitPlanes)]),
     ("rfx_query_occluded", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32, C.c_void_p, C.c_void_p]),
     ("rfx_query_occluded_host", C.c_int, [C.c_void_p, _fp, _i32p, C.c_uint64, C.c_uint32, C.POINTER(C.c_uint8)]),
+    ("rfx_renderer_order_box", C.c_int, [C.c_void_p, _fp, _fp]),
+    ("rfx_rays_order", C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p]),
+    ("rfx_rays_order_host", C.c_int, [C.c_void_p, _fp, C.c_uint64, _u32p, _u32p]),
+    ("rfx_trace_rays_ordered", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_int32, C.c_void_p,
+                                         C.c_void_p, C.c_void_p]),
+    ("rfx_query_hits_ordered", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(HitPlanes),
+                                         C.c_void_p]),
+    ("rfx_query_occluded_ordered", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p,
+                                             C.c_void_p]),
     ("rfx_group_create", C.c_int, [C.POINTER(C.c_void_p), C.POINTER(C.c_int), C.c_int]),
     ("rfx_group_destroy", None, [C.c_void_p]),
     ("rfx_group_size", C.c_int, [C.c_void_p]),

@@ -300,6 +300,7 @@ extern "C" int rfx_renderer_set_scene(rfx_renderer *r, const rfx_scene *s)
       (rc = upload(r, B.tt.resid, &d.tri_resid)) || (rc = upload(r, B.aux, &d.bvh_aux)))
     return rc;
   r->accel = B.accel;
+  r->order_box = B.order_box;
   r->dev = d;
   r->has_scene = true;
   ++r->scene_gen;

@@ -197,6 +197,10 @@ struct rfx_renderer {
   rfx::DevBuf<rfx::QRay> queue;
   rfx::DevBuf<uint32_t> qctr, qkey, qorder;
   int queue_sort;  // rfx_renderer_set_regroup_sort
+  // the coherent order (rfx_order.cpp): the uploaded scene's key box, and rfx_rays_order's scratch -- the ping-pong
+  // keys and indices (two halves each) and the digit pass's histogram table with its totals
+  rfx::OrderBox order_box{};
+  rfx::DevBuf<uint32_t> order_keys, order_idx, order_table;
   // per-phase event timing: triples {start, after pre-pass, after trace} on every timing_every-th frame (the events'
   // own cost stays off the other frames: ~10 us per frame for three records at C1's 640x480)
   bool timing = false, timing_this = false;

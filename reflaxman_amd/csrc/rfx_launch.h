@@ -5,6 +5,7 @@
 #include <hip/hip_runtime.h>
 
 #include "rfx_types.h"
+#include "rfx_order_types.h"
 
 namespace rfx {
 // ---- rfx_kernels.hip: the RNG pre-pass (count / emit kernels, the one-pass kernel, the cycle table)
@@ -71,4 +72,17 @@ hipError_t launch_trace_rays(const DevScene &S, const FrameParams &P, const floa
 // ---- rfx_trace_hits.hip: one launch of a hit query (rfx_hits.h) -- P.n rays; any: the any-hit kernel, else the
 // closest-hit one
 hipError_t launch_query_hits(const DevScene &S, const HitParams &P, bool any, hipStream_t st);
+// ---- rfx_order_sort.hip: the ray keys (keys2: a second copy, or null), and one digit pass of the stable radix sort --
+// the pairs (kin[i], iin[i]) (iin null: the index i itself) go to (kout, iout) (kout null: indices only) by the digit
+// at `shift`; table: kOrderDigits x order_groups(n) words, totals: kOrderDigits words of scratch
+uint32_t order_groups(uint32_t n);
+hipError_t launch_order_keys(const OrderBox &B, const float *d_rays, uint32_t n, uint32_t *keys, uint32_t *keys2,
+                             hipStream_t st);
+hipError_t launch_order_pass(const uint32_t *kin, const uint32_t *iin, uint32_t *kout, uint32_t *iout, uint32_t n,
+                             uint32_t shift, uint32_t *table, uint32_t *totals, hipStream_t st);
+// ---- rfx_trace_ordered.hip: one launch of an ordered ray batch (rfx_ordered.h trace_rays_ordered_kernel: P.p_end rays
+// and as many slots of d_order) and of an ordered hit query
+hipError_t launch_trace_rays_ordered(const DevScene &S, const FrameParams &P, const float *d_rays,
+                                     const uint32_t *d_order, hipStream_t st);
+hipError_t launch_query_hits_ordered(const DevScene &S, const HitOrderParams &P, bool any, hipStream_t st);
 }  // namespace rfx

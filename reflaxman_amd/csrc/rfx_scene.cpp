@@ -737,9 +737,48 @@ extern "C" int rfx_scene_tri_mates(const rfx_scene *s, int32_t *leader, float *p
 }
 
 // ============================================================== the device form of a scene
+// The coherent order's key box (rfx.h "Coherent order"): float32 throughout, objects in insertion order, a NaN never
+// taken; planes are unbounded and do not count
+static OrderBox order_box_of(const rfx_scene &s)
+{
+  float lo[3] = {INFINITY, INFINITY, INFINITY}, hi[3] = {-INFINITY, -INFINITY, -INFINITY};
+  const auto take = [&](int a, float l, float h) {
+    if (l < lo[a]) lo[a] = l;
+    if (h > hi[a]) hi[a] = h;
+  };
+  for (size_t k = 0; k < s.obj_kind.size(); ++k)
+  {
+    if (s.obj_kind[k] == 0)
+    {
+      const HostSphere &h = s.spheres[s.obj_idx[k]];
+      const float c[3] = {h.center.x, h.center.y, h.center.z};
+      for (int a = 0; a < 3; ++a) take(a, c[a] - h.radius, c[a] + h.radius);
+    }
+    else if (s.obj_kind[k] == 1)
+    {
+      const HostTri &t = s.tris[s.obj_idx[k]];
+      for (const v3 *v : {&t.v0, &t.v1, &t.v2})
+      {
+        take(0, v->x, v->x);
+        take(1, v->y, v->y);
+        take(2, v->z, v->z);
+      }
+    }
+  }
+  OrderBox b{};
+  for (int a = 0; a < 3; ++a)
+  {
+    const bool ok = hi[a] > lo[a] && std::isfinite(lo[a]) && std::isfinite(hi[a]);
+    b.scale[a] = ok ? (float)(1u << RFX_ORDER_CELL_BITS) / (hi[a] - lo[a]) : 0.0f;
+    b.lo[a] = std::isfinite(lo[a]) ? lo[a] : 0.0f;
+  }
+  return b;
+}
+
 SceneBuild::SceneBuild(const rfx_scene &scene, int tri_accel)
 {
   const rfx_scene *s = &scene;
+  order_box = order_box_of(scene);
   // Large scenes (more than 32 spheres): spheres in spatial order (spatial_order: recursive median splits),
   // so each 64-sphere chunk of the device arrays is compact and its bounding sphere can cull it as a whole,
   // and each pair is a BVH leaf.  Every record keeps its object index (sph_info),

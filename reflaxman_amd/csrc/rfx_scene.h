@@ -7,6 +7,7 @@
 
 #include "../../include/rfx.h"
 #include "rfx_types.h"
+#include "rfx_order_types.h"
 
 namespace rfx {
 
@@ -45,6 +46,7 @@ struct SceneBuild {
   std::vector<TexRec> tr;                    // texs
   DevScene d{};
   rfx_accel_info accel{};
+  OrderBox order_box{};                      // the coherent order's key box (rfx.h "Coherent order")
 };
 
 }  // namespace rfx

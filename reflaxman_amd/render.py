@@ -345,7 +345,96 @@ class Renderer:
     def synchronize(self):
         check(_lib.load().rfx_synchronize(self._h), "rfx_synchronize")
 
-    def trace_rays(self, rays, depth: int, raster_width: int = 0, argb: bool = False, counters=None):
+    class _DeviceArrays:
+        """Device arrays of a numpy call that has no host form (the ordered calls), from the library's own helpers
+        (rfx_device_alloc, rfx_memcpy_h2d / _d2h on the renderer's stream); freed on exit."""
+
+        def __init__(self, renderer):
+            self.r, self.L, self.ptrs = renderer, _lib.load(), []
+
+        def __enter__(self):
+            return self
+
+        def __exit__(self, *exc):
+            self.L.rfx_synchronize(self.r._h)  # (what was enqueued reads and writes the arrays before they go)
+            for p in self.ptrs:
+                self.L.rfx_device_free(self.r._h, p)
+            return False
+
+        def alloc(self, nbytes: int) -> C.c_void_p:
+            p = C.c_void_p()
+            check(self.L.rfx_device_alloc(self.r._h, int(nbytes), C.byref(p)), "rfx_device_alloc")
+            self.ptrs.append(p)
+            return p
+
+        def put(self, a: np.ndarray) -> C.c_void_p:
+            p = self.alloc(a.nbytes)
+            check(self.L.rfx_memcpy_h2d(self.r._h, p, a.ctypes.data_as(C.c_void_p), a.nbytes), "rfx_memcpy_h2d")
+            return p
+
+        def get(self, a: np.ndarray, p) -> np.ndarray:
+            check(self.L.rfx_memcpy_d2h(self.r._h, a.ctypes.data_as(C.c_void_p), p, a.nbytes), "rfx_memcpy_d2h")
+            return a
+
+    def order_box(self):
+        """(lo, scale) of the coherent order's key box for the uploaded scene, float32 (3,) each (rfx.h)."""
+        lo, scale = np.empty(3, np.float32), np.empty(3, np.float32)
+        check(_lib.load().rfx_renderer_order_box(self._h, _lib.fptr(lo), _lib.fptr(scale)), "rfx_renderer_order_box")
+        return lo, scale
+
+    def order_rays(self, rays, keys: bool = False):
+        """The coherent order of a batch (rfx.h rfx_rays_order): the permutation of [0, n) that sorts the rays by their
+        key of origin cell and direction, equal keys in index order -- pass it as ``order=`` to trace_rays, query_hits
+        or occluded.  ``rays`` as for trace_rays: a torch tensor on this renderer's device is sorted where it lies, on
+        torch's current stream, and an int32 tensor comes back; anything else goes through numpy and the host form
+        (uint32).  keys: also return every ray's key in ray order, as (order, keys) -- the same bits as int32 in torch."""
+        L = _lib.load()
+        is_torch, r, stream = self._ray_batch(rays, "order_rays")
+        n = r.shape[0]
+        if is_torch:
+            import torch
+            order = torch.empty(n, dtype=torch.int32, device=r.device)
+            k = torch.empty(n, dtype=torch.int32, device=r.device) if keys else None
+            check(L.rfx_rays_order(self._h, C.c_void_p(r.data_ptr()), n, C.c_void_p(order.data_ptr()),
+                                   C.c_void_p(k.data_ptr() if keys else None), C.c_void_p(stream or None)), "rfx_rays_order")
+            if not stream:
+                self.synchronize()
+            return (order, k) if keys else order
+        order = np.empty(n, np.uint32)
+        k = np.empty(n, np.uint32) if keys else None
+        check(L.rfx_rays_order_host(self._h, _lib.fptr(r), n, _lib.u32ptr(order), _lib.u32ptr(k) if keys else None),
+              "rfx_rays_order_host")
+        return (order, k) if keys else order
+
+    def _order_tensor(self, order, r, what):
+        """``order=`` of a torch call as an int32 device tensor of r's n indices ("coherent": order_rays)."""
+        import torch
+        if isinstance(order, str):
+            if order != "coherent":
+                raise ValueError(f"{what}: order is an index array or \"coherent\"")
+            return self.order_rays(r)
+        if isinstance(order, torch.Tensor):
+            o = order.to(device=r.device, dtype=torch.int32).reshape(-1).contiguous()
+        else:
+            o = torch.from_numpy(np.ascontiguousarray(order).astype(np.uint32).view(np.int32).reshape(-1)).to(r.device)
+        if o.numel() != r.shape[0]:
+            raise ValueError(f"{what}: one order entry per ray")
+        return o
+
+    def _order_array(self, dev, order, d_rays, n, what) -> C.c_void_p:
+        """``order=`` of a numpy call as a device array of n uint32 ("coherent": rfx_rays_order on the device rays)."""
+        if isinstance(order, str):
+            if order != "coherent":
+                raise ValueError(f"{what}: order is an index array or \"coherent\"")
+            d_order = dev.alloc(4 * n)
+            check(dev.L.rfx_rays_order(self._h, d_rays, n, d_order, None, None), "rfx_rays_order")
+            return d_order
+        o = np.ascontiguousarray(order).astype(np.uint32).reshape(-1)
+        if o.size != n:
+            raise ValueError(f"{what}: one order entry per ray")
+        return dev.put(o)
+
+    def trace_rays(self, rays, depth: int, raster_width: int = 0, argb: bool = False, counters=None, order=None):
         """Scene::trace on a batch of rays (rfx.h rfx_trace_rays): ``rays`` is (n, 6) float32 -- origin xyz, then the
         direction xyz, used as given -- and the result the (n, 3) float32 colours, ray i's from the i-th
         randomInsideSphere draw of the sphere stream.  A torch tensor on this renderer's device is traced where it
@@ -355,8 +444,13 @@ class Renderer:
         Color::argb of every colour, as (colours, words) -- uint32 (numpy) or the same bits as int32 (torch).
         counters: the stats kernel's RFX_NCOUNTERS event counters are added to it -- a numpy uint64 array, or a torch
         int64 tensor on the device.  raster_width W > 0 lays the batch out as a row-major W-wide raster and gives each
-        wave an 8x8 tile of it (rays from a camera model); it changes the schedule only, never a value."""
+        wave an 8x8 tile of it (rays from a camera model); it changes the schedule only, never a value.  order: the
+        schedule as an index array instead (rfx.h rfx_trace_rays_ordered) -- wave w traces the rays order[64 w .. 64 w +
+        63]; a tensor or array of the n indices, a permutation of [0, n), or "coherent", which takes order_rays(rays)
+        first.  Every colour and the stream's end state stay the unordered call's.  Not with raster_width or counters."""
         L = _lib.load()
+        if order is not None and (raster_width or counters is not None):
+            raise ValueError("trace_rays: order goes with neither raster_width nor counters")
         try:
             import torch
             is_torch = isinstance(rays, torch.Tensor)
@@ -378,10 +472,16 @@ class Renderer:
             stream = torch.cuda.current_stream(r.device).cuda_stream
             if not stream:
                 torch.cuda.current_stream(r.device).synchronize()
-            check(L.rfx_trace_rays(self._h, C.c_void_p(r.data_ptr()), n, int(depth), int(raster_width),
-                                   C.c_void_p(rgb.data_ptr()), C.c_void_p(words.data_ptr() if argb else None),
-                                   C.c_void_p(counters.data_ptr() if counters is not None else None),
-                                   C.c_void_p(stream or None)), "rfx_trace_rays")
+            if order is not None:
+                o = self._order_tensor(order, r, "trace_rays")
+                check(L.rfx_trace_rays_ordered(self._h, C.c_void_p(r.data_ptr()), C.c_void_p(o.data_ptr()), n, int(depth),
+                                               C.c_void_p(rgb.data_ptr()), C.c_void_p(words.data_ptr() if argb else None),
+                                               C.c_void_p(stream or None)), "rfx_trace_rays_ordered")
+            else:
+                check(L.rfx_trace_rays(self._h, C.c_void_p(r.data_ptr()), n, int(depth), int(raster_width),
+                                       C.c_void_p(rgb.data_ptr()), C.c_void_p(words.data_ptr() if argb else None),
+                                       C.c_void_p(counters.data_ptr() if counters is not None else None),
+                                       C.c_void_p(stream or None)), "rfx_trace_rays")
             if not stream:
                 self.synchronize()
             return (rgb, words) if argb else rgb
@@ -392,6 +492,18 @@ class Renderer:
         if counters is not None and not (isinstance(counters, np.ndarray) and counters.dtype == np.uint64 and
                                          counters.flags.c_contiguous and counters.size >= _lib.RFX_NCOUNTERS):
             raise ValueError("trace_rays: counters must be a contiguous uint64 array of RFX_NCOUNTERS words")
+        if order is not None:
+            with self._DeviceArrays(self) as dev:
+                d_rays = dev.put(r)
+                d_order = self._order_array(dev, order, d_rays, n, "trace_rays")
+                d_rgb, d_argb = dev.alloc(rgb.nbytes), dev.alloc(4 * n) if argb else None
+                check(L.rfx_trace_rays_ordered(self._h, d_rays, d_order, n, int(depth), d_rgb, d_argb, None),
+                      "rfx_trace_rays_ordered")
+                dev.get(rgb, d_rgb)
+                if argb:
+                    dev.get(words, d_argb)
+                self.synchronize()  # (the pre-pass's error word)
+            return (rgb, words) if argb else rgb
         check(L.rfx_trace_rays_host(self._h, _lib.fptr(r), n, int(depth), int(raster_width), _lib.fptr(rgb),
                                     _lib.u32ptr(words) if argb else None,
                                     _lib.u64ptr(counters) if counters is not None else None), "rfx_trace_rays_host")
@@ -417,12 +529,15 @@ class Renderer:
             torch.cuda.current_stream(r.device).synchronize()
         return True, r, stream
 
-    def query_hits(self, rays, raster_width: int = 0, want=HIT_PLANES):
+    def query_hits(self, rays, raster_width: int = 0, want=HIT_PLANES, order=None):
         """The closest hit of every ray (rfx.h rfx_query_hits: one pass of Scene.cpp:82-107): a dict of the planes
         named in ``want`` -- object (n, int32, -1 = no hit), distance (n, FLT_MAX on a miss), point, normal, reflected,
         colour ((n, 3), zero on a miss).  ``rays`` as for trace_rays: a torch tensor on this renderer's device is
         queried where it lies, on torch's current stream, and tensors come back; anything else goes through numpy and
-        the host form, which synchronises.  No random stream moves."""
+        the host form, which synchronises.  No random stream moves.  order: as for trace_rays (rfx.h
+        rfx_query_hits_ordered): an index array or "coherent"; not with raster_width."""
+        if order is not None and raster_width:
+            raise ValueError("query_hits: order goes with no raster_width")
         want = tuple(want)
         if not want or any(k not in self.HIT_PLANES for k in want):
             raise ValueError(f"query_hits: want names at least one of {self.HIT_PLANES}")
@@ -437,22 +552,41 @@ class Renderer:
                    for k in want}
             for k in want:
                 setattr(hp, k, out[k].data_ptr())
-            check(L.rfx_query_hits(self._h, C.c_void_p(r.data_ptr()), n, int(raster_width), C.byref(hp),
-                                   C.c_void_p(stream or None)), "rfx_query_hits")
+            if order is not None:
+                o = self._order_tensor(order, r, "query_hits")
+                check(L.rfx_query_hits_ordered(self._h, C.c_void_p(r.data_ptr()), C.c_void_p(o.data_ptr()), n,
+                                               C.byref(hp), C.c_void_p(stream or None)), "rfx_query_hits_ordered")
+            else:
+                check(L.rfx_query_hits(self._h, C.c_void_p(r.data_ptr()), n, int(raster_width), C.byref(hp),
+                                       C.c_void_p(stream or None)), "rfx_query_hits")
             if not stream:
                 self.synchronize()
             return out
         out = {k: np.empty(shape(k), np.int32 if k == "object" else np.float32) for k in want}
+        if order is not None:
+            with self._DeviceArrays(self) as dev:
+                d_rays = dev.put(r)
+                d_order = self._order_array(dev, order, d_rays, n, "query_hits")
+                d_out = {k: dev.alloc(out[k].nbytes) for k in want}
+                for k in want:
+                    setattr(hp, k, d_out[k].value)
+                check(L.rfx_query_hits_ordered(self._h, d_rays, d_order, n, C.byref(hp), None), "rfx_query_hits_ordered")
+                for k in want:
+                    dev.get(out[k], d_out[k])
+            return out
         for k in want:
             setattr(hp, k, out[k].ctypes.data)
         check(L.rfx_query_hits_host(self._h, _lib.fptr(r), n, int(raster_width), C.byref(hp)), "rfx_query_hits_host")
         return out
 
-    def occluded(self, rays, skip=None, raster_width: int = 0):
+    def occluded(self, rays, skip=None, raster_width: int = 0, order=None):
         """Whether anything stands in each ray's way (rfx.h rfx_query_occluded, the shadow rays' any-hit of
         Scene.cpp:133-143): (n,) uint8, 1 = some object other than ``skip[i]`` is hit.  The ray is unbounded.  skip:
         (n,) int32 object indices (None, or a value outside [0, objects): nothing is left out), of the kind ``rays``
-        is -- a device tensor with a device tensor, else numpy."""
+        is -- a device tensor with a device tensor, else numpy.  order: as for trace_rays (rfx.h
+        rfx_query_occluded_ordered): an index array or "coherent"; not with raster_width."""
+        if order is not None and raster_width:
+            raise ValueError("occluded: order goes with no raster_width")
         L = _lib.load()
         is_torch, r, stream = self._ray_batch(rays, "occluded")
         n = r.shape[0]
@@ -464,9 +598,15 @@ class Renderer:
                 if sk.numel() != n:
                     raise ValueError("occluded: one skip entry per ray")
             occ = torch.empty(n, dtype=torch.uint8, device=r.device)
-            check(L.rfx_query_occluded(self._h, C.c_void_p(r.data_ptr()), C.c_void_p(sk.data_ptr() if sk is not None else None),
-                                       n, int(raster_width), C.c_void_p(occ.data_ptr()), C.c_void_p(stream or None)),
-                  "rfx_query_occluded")
+            d_skip = C.c_void_p(sk.data_ptr() if sk is not None else None)
+            if order is not None:
+                o = self._order_tensor(order, r, "occluded")
+                check(L.rfx_query_occluded_ordered(self._h, C.c_void_p(r.data_ptr()), d_skip, C.c_void_p(o.data_ptr()), n,
+                                                   C.c_void_p(occ.data_ptr()), C.c_void_p(stream or None)),
+                      "rfx_query_occluded_ordered")
+            else:
+                check(L.rfx_query_occluded(self._h, C.c_void_p(r.data_ptr()), d_skip, n, int(raster_width),
+                                           C.c_void_p(occ.data_ptr()), C.c_void_p(stream or None)), "rfx_query_occluded")
             if not stream:
                 self.synchronize()
             return occ
@@ -476,6 +616,16 @@ class Renderer:
             if sk.size != n:
                 raise ValueError("occluded: one skip entry per ray")
         occ = np.empty(n, np.uint8)
+        if order is not None:
+            with self._DeviceArrays(self) as dev:
+                d_rays = dev.put(r)
+                d_order = self._order_array(dev, order, d_rays, n, "occluded")
+                d_skip = dev.put(sk) if sk is not None else None
+                d_occ = dev.alloc(n)
+                check(L.rfx_query_occluded_ordered(self._h, d_rays, d_skip, d_order, n, d_occ, None),
+                      "rfx_query_occluded_ordered")
+                dev.get(occ, d_occ)
+            return occ
         check(L.rfx_query_occluded_host(self._h, _lib.fptr(r), sk.ctypes.data_as(_lib._i32p) if sk is not None else None,
                                         n, int(raster_width), occ.ctypes.data_as(C.POINTER(C.c_uint8))),
               "rfx_query_occluded_host")

@@ -18,6 +18,14 @@ device events; medians over the rounds):
                                0, and 0 on a fixed random permutation of the rays
     hits_object                rfx_query_hits, the object plane alone (4 B out per ray), raster
     occluded                   rfx_query_occluded, nothing left out, raster
+    hits_permuted_order        rfx_rays_order alone on the permuted rays: the sort an incoherent caller would add
+    hits_permuted_ordered      rfx_query_hits_ordered on the permuted rays with that order computed beforehand, all six
+                               planes; hits_permuted_sum (no arm, the two medians added) is what stands against
+                               hits_permuted, with hits_raster as the ceiling.  Before timing the ordered call's six
+                               planes must equal the permuted arm's
+    hits_permuted_object / hits_permuted_ordered_object   the same pair asking for the object plane alone: what the
+                               ordered call's scattered stores cost (it writes each ray's words where the ray lies in
+                               the caller's arrays, not where its wave runs)
 One JSON line per arm goes to stdout and to DIR/hits_<config>.jsonl (default profiles/r13).
 """
 import argparse
@@ -89,9 +97,26 @@ def main():
         return r, lambda: _lib.check(L.rfx_query_occluded(r._h, C.c_void_p(rays.data_ptr()), None, n, W,
                                                           C.c_void_p(occ.data_ptr()), sp), "rfx_query_occluded")
 
+    order = torch.zeros(n, dtype=torch.int32, device="cuda")
+
+    def order_arm():
+        r = renderer()
+        return r, lambda: _lib.check(L.rfx_rays_order(r._h, C.c_void_p(rays_perm.data_ptr()), n,
+                                                      C.c_void_p(order.data_ptr()), None, sp), "rfx_rays_order")
+
+    def ordered_arm(want):
+        r = renderer()
+        hp = _lib.HitPlanes(**{k: out[k].data_ptr() for k in want})
+        return r, lambda: _lib.check(L.rfx_query_hits_ordered(r._h, C.c_void_p(rays_perm.data_ptr()),
+                                                              C.c_void_p(order.data_ptr()), n, C.byref(hp), sp),
+                                     "rfx_query_hits_ordered")
+
     arms = [("trace_d1", trace_arm(), 12), ("hits_raster", hits_arm(rays, W, PLANES), 56),
             ("hits_linear", hits_arm(rays, 0, PLANES), 56), ("hits_permuted", hits_arm(rays_perm, 0, PLANES), 56),
             ("hits_object", hits_arm(rays, W, ("object",)), 4), ("occluded", occ_arm(), 1),
+            ("hits_permuted_order", order_arm(), 4), ("hits_permuted_ordered", ordered_arm(PLANES), 56),
+            ("hits_permuted_object", hits_arm(rays_perm, 0, ("object",)), 4),
+            ("hits_permuted_ordered_object", ordered_arm(("object",)), 4),
             ("trace_d1_again", trace_arm(), 12)]
 
     # the check before timing: misses of the object plane = sky-coloured pixels of the depth-1 frame; with it, the
@@ -107,12 +132,23 @@ def main():
     by["hits_permuted"][1]()
     stream.synchronize()
     perm_ok = bool(torch.equal(out["object"], lin_obj[torch.from_numpy(perm).cuda()]))
+    # the ordered call on the permuted rays, in the library's order: every word of the permuted arm's six planes
+    perm_out = {k: out[k].clone() for k in PLANES}
+    for k in PLANES:
+        out[k].zero_()
+    by["hits_permuted_order"][1]()
+    by["hits_permuted_ordered"][1]()
+    stream.synchronize()
+    bits = lambda t: t.view(torch.int32)
+    ordered_ok = all(bool(torch.equal(bits(out[k]), bits(perm_out[k]))) for k in PLANES)
+    sorted_ok = bool(torch.equal(torch.sort(order.to(torch.int64)).values, torch.arange(n, device="cuda")))
+    del perm_out
     by["hits_object"][1]()
     stream.synchronize()
     raster_ok = bool(torch.equal(out["object"], lin_obj))
     check = {"misses": misses, "sky_pixels": sky, "occluded": occluded_n, "permuted_equal": perm_ok,
-             "raster_equal": raster_ok}
-    if misses != sky or n - misses != occluded_n or not (perm_ok and raster_ok):
+             "raster_equal": raster_ok, "ordered_equal": ordered_ok, "order_is_a_permutation": sorted_ok}
+    if misses != sky or n - misses != occluded_n or not (perm_ok and raster_ok and ordered_ok and sorted_ok):
         raise SystemExit(f"hits_bench: the check before timing failed: {check}")
 
     for arm, (r, call), _ in arms:
@@ -142,6 +178,14 @@ def main():
             print(line)
             f.write(line + "\n")
             r.close()
+        med = statistics.median(ms["hits_permuted_order"]) + statistics.median(ms["hits_permuted_ordered"])
+        line = json.dumps({"config": args.config, "scene": name, "W": W, "H": H, "arm": "hits_permuted_sum",
+                           "of": ["hits_permuted_order", "hits_permuted_ordered"], "ms_median": round(med, 4),
+                           "mrays_s": round(n / med / 1e3, 1), "vs_trace_d1": round(med / base, 4),
+                           "vs_hits_permuted": round(med / statistics.median(ms["hits_permuted"]), 4),
+                           "vs_hits_raster": round(med / statistics.median(ms["hits_raster"]), 4)})
+        print(line)
+        f.write(line + "\n")
 
 
 def sky_pixels(r, desc, dirs, rgb) -> int:

@@ -3,7 +3,7 @@
 rfx_render_frame of that frame in ONE process on ONE GPU, in the manner of tools/ab.py.
 
     python tools/rays_bench.py --config c3 [--rounds R] [--frames F] [--out DIR]
-    python tools/rays_bench.py --config c5 ...
+    python tools/rays_bench.py --config c5 [--permuted] ...
 
 c3: synth16 3840x2160 depth 8 (BASELINE C3); c5: stress4096 3840x2160 depth 12 (C5, the large-scene line).  The rays
 are cameras.pinhole_rays of the scene's camera, so the raster and linear batches compute the frame itself: their
@@ -15,7 +15,12 @@ device events, pre-pass included; medians over the rounds):
                         the same kernel work as a batch; twice, so the pair's difference is the run's own noise band
     raster              the batch with raster_width = W
     linear              the batch with raster_width = 0
-    permuted            the batch in a fixed random permutation, raster_width = 0 (c3 only): what incoherent callers get
+    permuted            the batch in a fixed random permutation, raster_width = 0 (c3; c5 with --permuted): what
+                        incoherent callers get
+    permuted_order      rfx_rays_order alone on the permuted rays: the sort an incoherent caller would add
+    permuted_ordered    rfx_trace_rays_ordered on the permuted rays with that order computed beforehand;
+                        permuted_sum (no arm, the two medians added) is what stands against permuted, with raster as
+                        the ceiling.  Before timing the ordered call's colours and ARGB words must equal the permuted arm's
 One JSON line per arm goes to stdout and to DIR/rays_<config>.jsonl (default profiles/r12).
 """
 import argparse
@@ -48,6 +53,7 @@ def main():
     ap.add_argument("--rounds", type=int, default=9)
     ap.add_argument("--frames", type=int, default=0, help="calls per timed window (0: 40 for c3, 8 for c5)")
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "r12"))
+    ap.add_argument("--permuted", action="store_true", help="the permuted arms on c5 too")
     args = ap.parse_args()
     import torch
     name, W, H, depth, key = CONFIGS[args.config]
@@ -60,7 +66,7 @@ def main():
     stream = torch.cuda.Stream()
     torch.cuda.set_stream(stream)
     rays = torch.from_numpy(host_rays).cuda()
-    rays_perm = torch.from_numpy(host_rays[perm]).cuda() if args.config == "c3" else None
+    rays_perm = torch.from_numpy(host_rays[perm]).cuda() if args.config == "c3" or args.permuted else None
     del host_rays
     rgb = torch.zeros((n, 3), dtype=torch.float32, device="cuda")
     argb = torch.zeros(n, dtype=torch.int32, device="cuda")
@@ -88,9 +94,31 @@ def main():
                                                       C.c_void_p(rgb.data_ptr()), C.c_void_p(argb.data_ptr()), None,
                                                       C.c_void_p(stream.cuda_stream)), "rfx_trace_rays")
 
+    order = torch.zeros(n, dtype=torch.int32, device="cuda")
+
+    def order_arm():
+        from reflaxman_amd import _lib
+        import ctypes as C
+        r = renderer()
+        L = _lib.load()
+        return r, lambda: _lib.check(L.rfx_rays_order(r._h, C.c_void_p(rays_perm.data_ptr()), n,
+                                                      C.c_void_p(order.data_ptr()), None,
+                                                      C.c_void_p(stream.cuda_stream)), "rfx_rays_order")
+
+    def ordered_arm():
+        from reflaxman_amd import _lib
+        import ctypes as C
+        r = renderer()
+        L = _lib.load()
+        return r, lambda: _lib.check(L.rfx_trace_rays_ordered(r._h, C.c_void_p(rays_perm.data_ptr()),
+                                                              C.c_void_p(order.data_ptr()), n, depth,
+                                                              C.c_void_p(rgb.data_ptr()), C.c_void_p(argb.data_ptr()),
+                                                              C.c_void_p(stream.cuda_stream)), "rfx_trace_rays_ordered")
+
     arms = [("frame", frame_arm()), ("raster", batch_arm(rays, W)), ("linear", batch_arm(rays, 0))]
     if rays_perm is not None:
-        arms.append(("permuted", batch_arm(rays_perm, 0)))
+        arms += [("permuted", batch_arm(rays_perm, 0)), ("permuted_order", order_arm()),
+                 ("permuted_ordered", ordered_arm())]
     arms.append(("frame_again", frame_arm()))
 
     # parity of every arm that computes the frame, on its first call from the seed
@@ -101,7 +129,17 @@ def main():
         call()
         stream.synchronize()
         r.synchronize()
-        if arm != "permuted":
+        if arm == "permuted":
+            perm_sha = (sha(rgb), sha(argb))
+        elif arm == "permuted_order":
+            ok[arm] = bool(torch.equal(torch.sort(order.to(torch.int64)).values, torch.arange(n, device="cuda")))
+            if not ok[arm]:
+                raise SystemExit("permuted_order: the order is no permutation")
+        elif arm == "permuted_ordered":  # (its renderer starts from the seed, as the permuted arm's did)
+            ok[arm] = (sha(rgb), sha(argb)) == perm_sha
+            if not ok[arm]:
+                raise SystemExit("permuted_ordered: the output differs from the permuted arm's")
+        else:
             ok[arm] = sha(rgb) == case["sha_f32"] and sha(argb) == case["sha_argb"]
             if not ok[arm]:
                 raise SystemExit(f"{arm}: the output differs from {key}")
@@ -132,6 +170,15 @@ def main():
             print(line)
             f.write(line + "\n")
             r.close()
+        if rays_perm is not None:
+            med = statistics.median(ms["permuted_order"]) + statistics.median(ms["permuted_ordered"])
+            line = json.dumps({"config": args.config, "scene": name, "W": W, "H": H, "depth": depth, "arm": "permuted_sum",
+                               "of": ["permuted_order", "permuted_ordered"], "ms_median": round(med, 4),
+                               "mrays_s": round(n / med / 1e3, 1), "vs_frame": round(med / base, 4),
+                               "vs_permuted": round(med / statistics.median(ms["permuted"]), 4),
+                               "vs_raster": round(med / statistics.median(ms["raster"]), 4)})
+            print(line)
+            f.write(line + "\n")
 
 
 if __name__ == "__main__":
