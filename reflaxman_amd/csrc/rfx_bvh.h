@@ -99,13 +99,31 @@ __device__ __forceinline__ bool bvh_box(const BvhNode &n, int c, const RayInv &r
   return !(t0 > t1 * 1.00001f + 1e-30f);
 }
 
+// The closest-hit walkers' distance prune: a child whose widened box is entered at distance d0 = t0 |ray| beyond the best
+// hit so far (0.1% slack on the squares over the rounding here and in the reference's |ray t|^2) cannot hold a closer or
+// tying hit.  d0 is formed first: it is a scene distance, so d0 * d0 is a normal float wherever h.sq is, whereas
+// t0 * t0 * |ray|^2 overflowed for a caller's ray 1e-18 long (t0 ~ 1e19), was +inf for every t0 > 0 once |ray|^2 was
+// (|ray| >= 1.3e19), and lost its bits to a subnormal t0 * t0 in between -- each pruned boxes holding the closest hit
+// (tests/test_bvh_prune_bound.py).  |ray| = sqrt(a) where a = |ray|^2 is safely a normal float, else 0: such a ray
+// prunes nothing by distance.  A NaN fails the comparison in the keeping direction.
+__device__ __forceinline__ float prune_len(const RayConst &k)
+{
+  const float a = 0.5f * k.a2;                // |ray|^2 (exact: a2 = 2a)
+  return a >= 0x1p-100f && a <= 0x1p100f ? __builtin_amdgcn_sqrtf(a) : 0.0f;
+}
+__device__ __forceinline__ bool bvh_beyond(float t0, float len, float best_sq)
+{
+  const float d0 = t0 * len;
+  return d0 * d0 > best_sq * 1.001f;
+}
+
 // closest sphere hit of one lane's ray over the BVH (Scene.cpp:86-106 restricted to the spheres)
 template <bool STATS, class NS>
 __device__ __forceinline__ void closest_spheres_bvh(const DevScene &S, v3 origin, v3 ray, const RayConst &k, Hit &h,
                                                     Cnt &cnt, const NS &ns)
 {
   const RayInv ri = ray_inv(S, origin, ray);
-  const float a = 0.5f * k.a2;                // |ray|^2 (exact: a2 = 2a)
+  const float len = prune_len(k);
   BvhSlot *stack = ns.stack();
   int sp = 0, node = 0;
   for (;;)
@@ -115,8 +133,8 @@ __device__ __forceinline__ void closest_spheres_bvh(const DevScene &S, v3 origin
       const BvhNode n = ns.node(S, node);
       float t0, t1;
       // a child entered beyond the best hit cannot hold a closer (or tying) sphere
-      const bool h0 = bvh_box(n, 0, ri, t0) && !(t0 * t0 * a > h.sq * 1.001f);
-      const bool h1 = bvh_box(n, 1, ri, t1) && !(t1 * t1 * a > h.sq * 1.001f);
+      const bool h0 = bvh_box(n, 0, ri, t0) && !bvh_beyond(t0, len, h.sq);
+      const bool h1 = bvh_box(n, 1, ri, t1) && !bvh_beyond(t1, len, h.sq);
       if (h0 && h1)
       {
         const bool first0 = !(t1 < t0);
@@ -236,7 +254,7 @@ __device__ __forceinline__ void closest_tris_bvh(const DevScene &S, v3 origin, v
                                                  Cnt &cnt, const NS &ns)
 {
   const RayInv ri = ray_inv(S, origin, ray);
-  const float a = 0.5f * k.a2;                // |ray|^2 (exact: a2 = 2a)
+  const float len = prune_len(k);
   BvhSlot *stack = ns.stack();
   int sp = 0, node = 0;
   for (;;)
@@ -246,8 +264,8 @@ __device__ __forceinline__ void closest_tris_bvh(const DevScene &S, v3 origin, v
       const BvhNode n = S.tri_bvh[node];
       float t0, t1;
       // a child entered beyond the best hit cannot hold a closer (or tying) triangle
-      const bool h0 = bvh_box(n, 0, ri, t0) && !(t0 * t0 * a > h.sq * 1.001f);
-      const bool h1 = bvh_box(n, 1, ri, t1) && !(t1 * t1 * a > h.sq * 1.001f);
+      const bool h0 = bvh_box(n, 0, ri, t0) && !bvh_beyond(t0, len, h.sq);
+      const bool h1 = bvh_box(n, 1, ri, t1) && !bvh_beyond(t1, len, h.sq);
       if (h0 && h1)
       {
         const bool first0 = !(t1 < t0);
@@ -290,10 +308,7 @@ __device__ __forceinline__ void closest_tris_bvh(const DevScene &S, v3 origin, v
     {
       const int obj = S.tri_shade[i].obj;
       const float key = hit_key(sq);
-      if (tri_takes(key, h.sq, obj, h.obj))
-      {
-        h.sq = key; h.obj = obj; h.kind = 1; h.i = i; h.t = t; h.u = u; h.v = v;
-      }
+      hit_take(h, tri_takes(key, h.sq, obj, h.obj), key, obj, 1, i, t, u, v);
     }
   }
 }

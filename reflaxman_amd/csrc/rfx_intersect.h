@@ -28,7 +28,12 @@ __device__ __forceinline__ RayConst ray_const(v3 ray)
   const float a = sqlen(ray);
   k.ray2 = mul(ray, 2.0f);
   k.a4 = 4.0f * a;
-  k.a2 = 2.0f * a;
+  // 2a = +inf (a caller's ray of 1.3e19 or longer) is kept as NaN.  No sphere is hit either way: the reference's
+  // t = x / inf is 0 or NaN, and x / NaN fails `t > VERY_SMALL_NUMBER` as well.  But nz^2 * 2a = +inf against a finite
+  // bound would let the closest-hit rejects before the division (tri_z, plane_hit) drop a crossing that is nearer than
+  // the best hit; with NaN every such comparison fails in the keeping direction.
+  const float a2 = 2.0f * a;
+  k.a2 = a2 < INFINITY ? a2 : __builtin_nanf("");
   k.a_ok = a > kVerySmall;
   k.a2d = div_prep(k.a2);
   return k;
@@ -294,6 +299,24 @@ __device__ __forceinline__ bool tri_takes(float sq, float best_sq, int obj, int 
   if (!(sq <= best_sq * kTakeAbove)) return false;
   return sq < best_sq ? (obj < best_obj || strictly_closer(sq, best_sq))
                       : (obj < best_obj && sqrt_rn(sq) == sqrt_rn(best_sq));
+}
+
+// The winner's record where the candidate's index is wave-uniform (the object loops: a scalar loop counter), written as
+// selects under one mask.  As a branch around the stores -- `if (tri_takes(...)) { h.sq = ...; h.i = i; ... }` -- the
+// small-scene triangle loop compiled (ROCm 6 clang, gfx950) to code that moved the scalar i into Hit::i before
+// tri_takes' 2^-20 band, used that register as scratch inside the band and restored the old Hit::i after it: a
+// candidate that took inside the band got every field but i, and the hit was shaded with another triangle's record
+// (caller rays from 1e7 away, where every distance lies in the band: tests/test_gpu_edge_rays.py).
+__device__ __forceinline__ void hit_take(Hit &h, bool take, float sq, int obj, int kind, int i, float t,
+                                         float u = 0.0f, float v = 0.0f)
+{
+  h.sq = take ? sq : h.sq;
+  h.obj = take ? obj : h.obj;
+  h.kind = take ? kind : h.kind;
+  h.i = take ? i : h.i;
+  h.t = take ? t : h.t;
+  h.u = take ? u : h.u;
+  h.v = take ? v : h.v;
 }
 
 }  // namespace rfx

@@ -23,10 +23,8 @@ __device__ __forceinline__ void closest_planes(const DevScene &S, v3 origin, v3 
   {
     const PlaneGeo g = S.pln_geo[i];
     float t, sq;
-    if (plane_hit<STATS, false>(g, origin, ray, t, sq, cnt, k, h.sq) && tri_takes(sq, h.sq, g.obj, h.obj))
-    {
-      h.sq = sq; h.obj = g.obj; h.kind = 2; h.i = i; h.t = t;
-    }
+    if (plane_hit<STATS, false>(g, origin, ray, t, sq, cnt, k, h.sq))
+      hit_take(h, tri_takes(sq, h.sq, g.obj, h.obj), sq, g.obj, 2, i, t);
   }
 }
 
@@ -99,13 +97,13 @@ __device__ __forceinline__ void closest_hit(const DevScene &S, v3 origin, v3 ray
         {
           const float key = hit_key(sq);
           const int obj = S.sph_info[4 * j];
-          if (tri_takes(key, h.sq, obj, h.obj)) { h.sq = key; h.obj = obj; h.i = 2 * j; h.t = t; }
+          hit_take(h, tri_takes(key, h.sq, obj, h.obj), key, obj, 0, 2 * j, t);
         }
         if ((!STATS || 2 * j + 1 < S.n_sph) && sphere_tail<STATS, false, true>(b.y, d.y, ray, k, t, sq, cnt))
         {
           const float key = hit_key(sq);
           const int obj = S.sph_info[4 * j + 2];
-          if (tri_takes(key, h.sq, obj, h.obj)) { h.sq = key; h.obj = obj; h.i = 2 * j + 1; h.t = t; }
+          hit_take(h, tri_takes(key, h.sq, obj, h.obj), key, obj, 0, 2 * j + 1, t);
         }
       }
     }
@@ -140,10 +138,7 @@ __device__ __forceinline__ void closest_hit(const DevScene &S, v3 origin, v3 ray
         RFX_CNT(C_TRI_D);
         const int obj = S.tri_shade[i].obj;
         const float key = hit_key(sq);
-        if (tri_takes(key, h.sq, obj, h.obj))
-        {
-          h.sq = key; h.obj = obj; h.kind = 1; h.i = i; h.t = t; h.u = u; h.v = v;
-        }
+        hit_take(h, tri_takes(key, h.sq, obj, h.obj), key, obj, 1, i, t, u, v);
       }
     }
   }
@@ -209,10 +204,7 @@ __device__ __forceinline__ void closest_hit_small(const DevScene &S, v3 origin, 
       RFX_CNT(C_TRI_D);
       const int obj = S.tri_shade[i].obj;
       const float key = hit_key(sq);
-      if (tri_takes(key, h.sq, obj, h.obj))
-      {
-        h.sq = key; h.obj = obj; h.kind = 1; h.i = i; h.t = t; h.u = u; h.v = v;
-      }
+      hit_take(h, tri_takes(key, h.sq, obj, h.obj), key, obj, 1, i, t, u, v);
     }
   }
   if constexpr (PLANES) closest_planes<STATS>(S, origin, ray, k, h, cnt);

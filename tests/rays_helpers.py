@@ -2,8 +2,10 @@
 
 The oracle for an arbitrary ray is oracle.OracleRender at image size 1 x 1, which traces exactly one Scene::trace: with
 eye = origin and view = (-2dx, 0, 0, -2dy, 0, 0, -2dz, 0, 0) its one ray is (-2d)(-0.5) + 0 + 0 = d exactly, whatever
-the fov (Render.cpp:146-156, 184-185), and its sphere stream carries on from ray to ray as the reference's would.  The
-trick turns a -0.0 direction component into +0.0, so test rays hold no zero components.
+the fov (Render.cpp:146-156, 184-185), and its sphere stream carries on from ray to ray as the reference's would.  A
++0.0 direction component survives the trick ((-2 * 0)(-0.5) + 0 + 0 = +0.0), a -0.0 one comes out as +0.0, and a
+non-finite word cannot be carried: oracle_trace takes finite rays without -0.0 components (the fixed test rays below
+hold no zero components at all; tests/edge_rays.py derives the ones that do).
 """
 from __future__ import annotations
 
@@ -28,7 +30,8 @@ def oracle_trace(desc, rays, depth, seed, counters=None):
     """n consecutive Scene::trace(origin_i, ray_i, depth) from sphere-stream state `seed`: ((n, 3) float32 colours,
     the state after them).  counters: the oracle's event counters are added to it."""
     rays = np.asarray(rays, np.float32).reshape(-1, 6)
-    assert not (rays[:, 3:6] == 0).any(), "the 1 x 1 oracle cannot carry a zero (or -0.0) direction component"
+    assert np.isfinite(rays).all() and not ((rays[:, 3:6] == 0) & np.signbit(rays[:, 3:6])).any(), \
+        "the 1 x 1 oracle cannot carry a non-finite word or a -0.0 direction component"
     o = orc.OracleRender(desc, seed, 0)
     o.set_image_size(1, 1)
     out = np.empty((rays.shape[0], 3), np.float32)
