@@ -23,7 +23,8 @@ SOURCES = ["rfx_kernels.hip", "rfx_host.cpp", "rfx_scene.cpp", "rfx_group.cpp", 
            "rfx_hits.cpp", "rfx_trace_hits.hip", "rfx_order.cpp", "rfx_order_sort.hip", "rfx_trace_ordered.hip",
            "rfx_trace_plain_park.hip"] + [
     f"rfx_trace_{m}_{s}.hip" for m in ("plain", "ssaa", "lanes", "chunks", "block") for s in ("fast", "stats")]
-HEADERS = sorted(f for f in os.listdir(CSRC) if f.endswith(".h"))  # every header counts towards _sources_digest
+# every header, and every text a header includes (rfx_rays_body.inc), counts towards _sources_digest
+HEADERS = sorted(f for f in os.listdir(CSRC) if f.endswith((".h", ".inc")))
 ARCH = os.environ.get("PYTORCH_ROCM_ARCH", "gfx950").split(";")[0] or "gfx950"
 
 FLAGS = [

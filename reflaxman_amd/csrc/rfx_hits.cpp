@@ -4,25 +4,15 @@
 //
 // A query reads the uploaded scene and nothing else of the renderer: no pre-pass (the random streams stay where they
 // are), no tile schedule, no per-view masks, no regroup queue, no timing sums, and nothing rfx_frame_rng_rewind undoes.
-#include <algorithm>
-
 #include "rfx_internal.h"
 
 using namespace rfx;
 
-// a wave's raster tile is 8 x 8 rays; a raster launch takes whole tile rows, at most this many (rfx_rays.cpp)
-constexpr uint64_t kTileRows = 8, kMaxTileRowsPerLaunch = 32768;
-
-// Launches of at most launch_traces rays, rounded as a ray batch's (rfx_rays.cpp): down to whole waves (linear) or
-// whole tile rows (raster), never below one.  P holds the whole batch's pointers; each launch takes them at its first ray.
+// Launches of a ray batch's size (rays_per_launch).  P holds the whole batch's pointers; each launch takes them at its
+// first ray.
 static int run_query(rfx_renderer *r, const HitParams &P, bool any, hipStream_t st)
 {
-  const uint64_t W = P.W;
-  uint64_t per;
-  if (W)
-    per = std::max<uint64_t>(1, std::min(kMaxTileRowsPerLaunch, r->launch_traces / (kTileRows * W))) * kTileRows * W;
-  else
-    per = std::max<uint64_t>(1, r->launch_traces / 64) * 64;
+  const uint64_t per = rays_per_launch(r, P.W);
   for (uint64_t a = 0; a < P.n; a += per)
   {
     HitParams Q = P;
@@ -41,57 +31,44 @@ static int run_query(rfx_renderer *r, const HitParams &P, bool any, hipStream_t 
   return RFX_OK;
 }
 
-static bool any_plane(const rfx_hit_planes *o)
-{
-  return o->object || o->distance || o->point || o->normal || o->reflected || o->colour;
-}
-
 extern "C" int rfx_query_hits(rfx_renderer *r, const float *d_rays, uint64_t n, uint32_t raster_width,
                               const rfx_hit_planes *out, void *stream)
 {
-  if (!r || !d_rays || !n || !out || !any_plane(out))
-    return fail(RFX_ERR_ARG, "query_hits: renderer, rays, n > 0 and at least one output plane required");
-  if (!r->has_scene) return fail(RFX_ERR_STATE, "query_hits: no scene uploaded");
   int rc;
-  if ((rc = set_dev(r)) != RFX_OK) return rc;
+  if ((rc = enter_call(r, d_rays && n && out && any_plane(out), "query_hits",
+                       "renderer, rays, n > 0 and at least one output plane required")) != RFX_OK)
+    return rc;
   HitParams P{};
   P.rays = d_rays;
   P.n = n;
   P.W = raster_width;
-  P.object = out->object;
-  P.distance = out->distance;
-  P.point = out->point;
-  P.normal = out->normal;
-  P.reflected = out->reflected;
-  P.colour = out->colour;
-  return run_query(r, P, false, stream ? (hipStream_t)stream : r->stream);
+  set_planes(P, out);
+  return run_query(r, P, false, stream_or_own(r, stream));
 }
 
 extern "C" int rfx_query_occluded(rfx_renderer *r, const float *d_rays, const int32_t *d_skip, uint64_t n,
                                   uint32_t raster_width, uint8_t *d_occluded, void *stream)
 {
-  if (!r || !d_rays || !n || !d_occluded)
-    return fail(RFX_ERR_ARG, "query_occluded: renderer, rays, n > 0 and the result array required");
-  if (!r->has_scene) return fail(RFX_ERR_STATE, "query_occluded: no scene uploaded");
   int rc;
-  if ((rc = set_dev(r)) != RFX_OK) return rc;
+  if ((rc = enter_call(r, d_rays && n && d_occluded, "query_occluded",
+                       "renderer, rays, n > 0 and the result array required")) != RFX_OK)
+    return rc;
   HitParams P{};
   P.rays = d_rays;
   P.skip = d_skip;
   P.n = n;
   P.W = raster_width;
   P.occluded = d_occluded;
-  return run_query(r, P, true, stream ? (hipStream_t)stream : r->stream);
+  return run_query(r, P, true, stream_or_own(r, stream));
 }
 
 extern "C" int rfx_query_hits_host(rfx_renderer *r, const float *rays, uint64_t n, uint32_t raster_width,
                                    const rfx_hit_planes *out)
 {
-  if (!r || !rays || !n || !out || !any_plane(out))
-    return fail(RFX_ERR_ARG, "query_hits_host: renderer, rays, n > 0 and at least one output plane required");
-  if (!r->has_scene) return fail(RFX_ERR_STATE, "query_hits_host: no scene uploaded");
   int rc;
-  if ((rc = set_dev(r)) != RFX_OK) return rc;
+  if ((rc = enter_call(r, rays && n && out && any_plane(out), "query_hits_host",
+                       "renderer, rays, n > 0 and at least one output plane required")) != RFX_OK)
+    return rc;
   // one staging array: the rays, then the requested planes one after the other (every plane is made of 4-B words)
   float *const host[6] = {reinterpret_cast<float *>(out->object), out->distance, out->point, out->normal,
                           out->reflected, out->colour};
@@ -129,11 +106,10 @@ extern "C" int rfx_query_hits_host(rfx_renderer *r, const float *rays, uint64_t 
 extern "C" int rfx_query_occluded_host(rfx_renderer *r, const float *rays, const int32_t *skip, uint64_t n,
                                        uint32_t raster_width, uint8_t *occluded)
 {
-  if (!r || !rays || !n || !occluded)
-    return fail(RFX_ERR_ARG, "query_occluded_host: renderer, rays, n > 0 and the result array required");
-  if (!r->has_scene) return fail(RFX_ERR_STATE, "query_occluded_host: no scene uploaded");
   int rc;
-  if ((rc = set_dev(r)) != RFX_OK) return rc;
+  if ((rc = enter_call(r, rays && n && occluded, "query_occluded_host",
+                       "renderer, rays, n > 0 and the result array required")) != RFX_OK)
+    return rc;
   DevBuf<float> d_rays;
   DevBuf<int32_t> d_skip;
   DevBuf<uint8_t> d_occ;

@@ -5,10 +5,11 @@
 //       index, curDist, and what its trace() returned (drop, norm, reflected ray, dropMaterial.color), each plane of
 //       results written only where the caller asked for it.
 //   query_occluded_kernel<CFG> : the shadow any-hit loop (Scene.cpp:133-143) per ray, over every object but skip[i].
-//   launch_hits_cfg            : a run-time cfg to its instantiation (rfx_trace_hits.hip is the one unit that includes
-//       this).
+//   query_hits_body, query_occluded_body : the two kernels' text, written once: the lane's ray and whether it is live
+//       come from the caller (these kernels here, the ordered ones in rfx_ordered.h).  The launch tables are
+//       rfx_batch_launch.h's.
 //
-// One lane per ray, a wave's unit and a lane's ray by ray_slot's rule (rfx_rays.h): 64 consecutive rays, or an 8x8 tile
+// One lane per ray, a wave's unit and a lane's ray by ray_slot's rule (rfx_ray_slot.h): 64 consecutive rays, or an 8x8 tile
 // of the batch read as a row-major raster.  Every lane of a wave reaches the query -- lanes past the batch's end or
 // outside the raster as not live -- so the bundles stay wave-wide, and the queries always take the culling path:
 // make_bundle over the live lanes, then cull_small, or closest_hit / occluded with the bundle.  The kernels take their
@@ -21,6 +22,7 @@
 #include "rfx_types.h"
 #include "rfx_shade_inputs.h"
 #include "rfx_queries.h"
+#include "rfx_ray_slot.h"
 
 #pragma clang fp contract(off)
 
@@ -29,67 +31,36 @@ namespace rfx {
 // the CFG bits a query kernel is instantiated on: never small together with a triangle tree
 constexpr int kHitCfgMask = kCfgSmall | kCfgPlanes | kCfgTriBvh;
 
-// A lane's ray in its wave's unit: ray_slot's rule (rfx_rays.h) on a query's own parameters
-struct HitSlot {
-  uint64_t i;
-  bool live;
-};
-__device__ __forceinline__ uint32_t hit_unit(const HitParams &P, uint32_t wv, uint32_t w8)
-{
-  // raster mode: the plain frame kernel's grid, workgroup (x, y) the kTileWavesX x kTileWavesY tiles at its place
-  return P.W ? (blockIdx.y * kTileWavesY + wv / kTileWavesX) * w8 + blockIdx.x * kTileWavesX + wv % kTileWavesX
-             : kWgWaves * blockIdx.x + wv;
-}
-__device__ __forceinline__ HitSlot hit_slot(const HitParams &P, uint32_t unit, uint32_t w8, uint32_t lane)
-{
-  HitSlot s;
-  if (P.W)
-  {
-    const uint32_t gx = (unit % w8) * 8u + (lane & 7u), gy = (unit / w8) * 8u + (lane >> 3);
-    s.i = (uint64_t)gy * P.W + gx;
-    s.live = gx < P.W && s.i < P.n;  // (the last raster row may be partial)
-  }
-  else
-  {
-    s.i = 64ull * unit + lane;
-    s.live = s.i < P.n;
-  }
-  return s;
-}
-
-// The lane's 24-B record, read first and non-temporally (trace_rays_kernel's order, DESIGN.md "Ray loads"): it comes
-// from HBM once, and the staging that follows runs while it is on its way.
-__device__ __forceinline__ void load_ray(const HitParams &P, const HitSlot &sl, v3 &o, v3 &d)
-{
-  o = mk(0.0f, 0.0f, 0.0f);
-  d = mk(0.0f, 0.0f, 0.0f);
-  if (sl.live)
-  {
-    const float *f = P.rays + 6u * sl.i;
-    o = mk(__builtin_nontemporal_load(f), __builtin_nontemporal_load(f + 1), __builtin_nontemporal_load(f + 2));
-    d = mk(__builtin_nontemporal_load(f + 3), __builtin_nontemporal_load(f + 4), __builtin_nontemporal_load(f + 5));
-  }
-}
-
 __device__ __forceinline__ void store3(float *plane, uint64_t i, v3 v)
 {
   float *p = plane + 3u * i;
   p[0] = v.x; p[1] = v.y; p[2] = v.z;
 }
 
+// The lane's slot of a linear or raster query: ray_slot's rule on the query's own parameters
+__device__ __forceinline__ RaySlot hit_slot(const HitParams &P)
+{
+  const uint32_t lane = threadIdx.x & 63u, wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const uint32_t w8 = kTileWavesX * gridDim.x;
+  return ray_slot(P, ray_unit(P, wv, w8), w8, lane);
+}
+
+// sl: the lane's ray among P's arrays, and whether the lane is live.  lut: the calling kernel's own 256-entry LDS table
+// (declared there, so that each kernel's LDS layout is its own).
 template <int CFG>
-__global__ __launch_bounds__(kWgThreads) void query_hits_kernel(DevScene S, HitParams P)
+__device__ __forceinline__ void query_hits_body(const DevScene &S, const HitParams &P, const RaySlot &sl, float *lut)
 {
   static_assert((CFG & ~kHitCfgMask) == 0 && !((CFG & kCfgSmall) && (CFG & kCfgTriBvh)), "a query's CFG bits");
   constexpr bool SMALL = (CFG & kCfgSmall) != 0, PLANES = (CFG & kCfgPlanes) != 0, TBVH = (CFG & kCfgTriBvh) != 0;
-  const uint32_t lane = threadIdx.x & 63u, wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  const uint32_t w8 = kTileWavesX * gridDim.x;
-  const HitSlot sl = hit_slot(P, hit_unit(P, wv, w8), w8, lane);
-  const bool live = sl.live;
-  v3 o, d;
-  load_ray(P, sl, o, d);
+  const bool live = sl.valid;
+  v3 o = mk(0.0f, 0.0f, 0.0f), d = mk(0.0f, 0.0f, 0.0f);
+  if (live)
+  {
+    const RayRecord r = load_ray(P.rays, sl.i);
+    o = r.o;
+    d = r.d;
+  }
   // the colour plane's texels go through Color(ARGB)'s table; nothing here raises a power
-  __shared__ float lut[256];
   for (uint32_t i = threadIdx.x; i < 256; i += kWgThreads) lut[i] = (float)i / 255.0f;  // Color.cpp:11-13
   if constexpr (SMALL) stage_small_scene(S);
   __syncthreads();
@@ -155,16 +126,18 @@ __global__ __launch_bounds__(kWgThreads) void query_hits_kernel(DevScene S, HitP
 }
 
 template <int CFG>
-__global__ __launch_bounds__(kWgThreads) void query_occluded_kernel(DevScene S, HitParams P)
+__device__ __forceinline__ void query_occluded_body(const DevScene &S, const HitParams &P, const RaySlot &sl)
 {
   static_assert((CFG & ~kHitCfgMask) == 0 && !((CFG & kCfgSmall) && (CFG & kCfgTriBvh)), "a query's CFG bits");
   constexpr bool SMALL = (CFG & kCfgSmall) != 0, PLANES = (CFG & kCfgPlanes) != 0, TBVH = (CFG & kCfgTriBvh) != 0;
-  const uint32_t lane = threadIdx.x & 63u, wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  const uint32_t w8 = kTileWavesX * gridDim.x;
-  const HitSlot sl = hit_slot(P, hit_unit(P, wv, w8), w8, lane);
-  const bool live = sl.live;
-  v3 o, d;
-  load_ray(P, sl, o, d);
+  const bool live = sl.valid;
+  v3 o = mk(0.0f, 0.0f, 0.0f), d = mk(0.0f, 0.0f, 0.0f);
+  if (live)
+  {
+    const RayRecord r = load_ray(P.rays, sl.i);
+    o = r.o;
+    d = r.d;
+  }
   // the object left out, as (kind, index within its kind's device arrays): kat_objects' decode of obj_loc
   int skip_sph = -1, skip_tri = -1, skip_pln = -1;
   if (live && P.skip)
@@ -202,27 +175,17 @@ __global__ __launch_bounds__(kWgThreads) void query_occluded_kernel(DevScene S, 
   if (live) P.occluded[sl.i] = occ ? 1 : 0;
 }
 
-// ------------------------------------------------------------- launch (rfx_trace_hits.hip)
 template <int CFG>
-inline void launch_hits_one(bool any, dim3 grid, const DevScene &S, const HitParams &P, hipStream_t st)
+__global__ __launch_bounds__(kWgThreads) void query_hits_kernel(DevScene S, HitParams P)
 {
-  if (any) hipLaunchKernelGGL((query_occluded_kernel<CFG>), grid, dim3(kWgThreads), 0, st, S, P);
-  else hipLaunchKernelGGL((query_hits_kernel<CFG>), grid, dim3(kWgThreads), 0, st, S, P);
+  __shared__ float lut[256];
+  query_hits_body<CFG>(S, P, hit_slot(P), lut);
 }
 
-inline void launch_hits_cfg(int cfg, bool any, dim3 grid, const DevScene &S, const HitParams &P, hipStream_t st)
+template <int CFG>
+__global__ __launch_bounds__(kWgThreads) void query_occluded_kernel(DevScene S, HitParams P)
 {
-  switch (cfg)
-  {
-    case 0: launch_hits_one<0>(any, grid, S, P, st); break;
-    case kCfgPlanes: launch_hits_one<kCfgPlanes>(any, grid, S, P, st); break;
-    case kCfgSmall: launch_hits_one<kCfgSmall>(any, grid, S, P, st); break;
-    case kCfgSmall | kCfgPlanes: launch_hits_one<kCfgSmall | kCfgPlanes>(any, grid, S, P, st); break;
-#if RFX_TRI_BVH
-    case kCfgTriBvh: launch_hits_one<kCfgTriBvh>(any, grid, S, P, st); break;
-    case kCfgTriBvh | kCfgPlanes: launch_hits_one<kCfgTriBvh | kCfgPlanes>(any, grid, S, P, st); break;
-#endif
-  }
+  query_occluded_body<CFG>(S, P, hit_slot(P));
 }
 
 }  // namespace rfx

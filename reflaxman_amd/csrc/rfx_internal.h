@@ -4,6 +4,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <algorithm>
 #include <vector>
 
 #include "rfx_launch.h"
@@ -220,4 +221,48 @@ int save_rewind_state(rfx_renderer *r, hipStream_t st);
 // takes: their randDir states into r->rd on `st`, the sphere stream n accepted triples on, the jitter stream untouched.
 // Fails while an emitted frame is pending; the call cannot be undone by rfx_frame_rng_rewind.
 int prepass_traces(rfx_renderer *r, uint64_t n, hipStream_t st);
+
+// ---- what the batch entry points share (rfx_rays.cpp, rfx_hits.cpp, rfx_order.cpp)
+// A call's opening tests: its arguments (args_ok false, or no renderer: "<call>: <required>") and an uploaded scene
+inline int check_call(const rfx_renderer *r, bool args_ok, const char *call, const char *required)
+{
+  if (!r || !args_ok) return fail(RFX_ERR_ARG, "%s: %s", call, required);
+  if (!r->has_scene) return fail(RFX_ERR_STATE, "%s: no scene uploaded", call);
+  return RFX_OK;
+}
+// ... and the renderer's device made current
+inline int enter_call(rfx_renderer *r, bool args_ok, const char *call, const char *required)
+{
+  RCHECK(check_call(r, args_ok, call, required));
+  return set_dev(r);
+}
+inline hipStream_t stream_or_own(const rfx_renderer *r, void *stream) { return stream ? (hipStream_t)stream : r->stream; }
+
+// Rays per launch of a batch of raster width W (0: linear): at most launch_traces, rounded down to whole waves
+// (linear) or whole tile rows (raster) and never below one, so that every launch but the last is made of full waves and
+// its outputs start 16-B aligned where the batch's do.  A wave's raster tile is 8 x 8 rays; a raster launch takes whole
+// tile rows, at most kMaxTileRowsPerLaunch (the grid's y limit).
+constexpr uint64_t kTileRows = 8, kMaxTileRowsPerLaunch = 32768;
+inline uint64_t rays_per_launch(const rfx_renderer *r, uint64_t W)
+{
+  const uint64_t unit = W ? kTileRows * W : 64;
+  uint64_t units = std::max<uint64_t>(1, r->launch_traces / unit);
+  if (W) units = std::min(units, kMaxTileRowsPerLaunch);
+  return units * unit;
+}
+
+// a hit query's output planes: whether the caller wants any, and their place in the launch record
+inline bool any_plane(const rfx_hit_planes *o)
+{
+  return o->object || o->distance || o->point || o->normal || o->reflected || o->colour;
+}
+inline void set_planes(HitParams &P, const rfx_hit_planes *o)
+{
+  P.object = o->object;
+  P.distance = o->distance;
+  P.point = o->point;
+  P.normal = o->normal;
+  P.reflected = o->reflected;
+  P.colour = o->colour;
+}
 }  // namespace rfx

@@ -5,8 +5,6 @@
 // The order call reads the uploaded scene's key box and its own scratch and nothing else of the renderer.  The ordered
 // trace is a ray batch (rfx_rays.cpp) in one launch; the ordered queries are hit queries (rfx_hits.cpp) and, like
 // them, leave every stream, mask and timing sum alone.
-#include <algorithm>
-
 #include "rfx_internal.h"
 
 using namespace rfx;
@@ -29,12 +27,11 @@ extern "C" int rfx_renderer_order_box(const rfx_renderer *r, float lo[3], float 
 extern "C" int rfx_rays_order(rfx_renderer *r, const float *d_rays, uint64_t n, uint32_t *d_order, uint32_t *d_keys,
                               void *stream)
 {
-  if (!r || !d_rays || !d_order || !n || n >= (1ull << 31))
-    return fail(RFX_ERR_ARG, "rays_order: renderer, rays, order and 0 < n < 2^31 required");
-  if (!r->has_scene) return fail(RFX_ERR_STATE, "rays_order: no scene uploaded");
   int rc;
-  if ((rc = set_dev(r)) != RFX_OK) return rc;
-  const hipStream_t st = stream ? (hipStream_t)stream : r->stream;
+  if ((rc = enter_call(r, d_rays && d_order && n && n < (1ull << 31), "rays_order",
+                       "renderer, rays, order and 0 < n < 2^31 required")) != RFX_OK)
+    return rc;
+  const hipStream_t st = stream_or_own(r, stream);
   const uint32_t m = (uint32_t)n;
   if ((rc = r->order_keys.reserve(2 * (size_t)m)) < 0 || (rc = r->order_idx.reserve(2 * (size_t)m)) < 0 ||
       (rc = r->order_table.reserve((size_t)kOrderDigits * order_groups(m) + kOrderDigits)) < 0)
@@ -56,11 +53,10 @@ extern "C" int rfx_rays_order(rfx_renderer *r, const float *d_rays, uint64_t n, 
 
 extern "C" int rfx_rays_order_host(rfx_renderer *r, const float *rays, uint64_t n, uint32_t *order, uint32_t *keys)
 {
-  if (!r || !rays || !order || !n || n >= (1ull << 31))
-    return fail(RFX_ERR_ARG, "rays_order_host: renderer, rays, order and 0 < n < 2^31 required");
-  if (!r->has_scene) return fail(RFX_ERR_STATE, "rays_order_host: no scene uploaded");
   int rc;
-  if ((rc = set_dev(r)) != RFX_OK) return rc;
+  if ((rc = enter_call(r, rays && order && n && n < (1ull << 31), "rays_order_host",
+                       "renderer, rays, order and 0 < n < 2^31 required")) != RFX_OK)
+    return rc;
   DevBuf<float> d_rays;
   DevBuf<uint32_t> d_out;  // the order, then the keys
   if ((rc = d_rays.reserve((size_t)n * 6)) < 0 || (rc = d_out.reserve((size_t)n * (keys ? 2 : 1))) < 0) return rc;
@@ -81,16 +77,16 @@ extern "C" int rfx_rays_order_host(rfx_renderer *r, const float *rays, uint64_t 
 extern "C" int rfx_trace_rays_ordered(rfx_renderer *r, const float *d_rays, const uint32_t *d_order, uint64_t n,
                                       int32_t reflect_num, float *d_rgb, uint32_t *d_argb, void *stream)
 {
-  if (!r || !d_rays || !d_order || !d_rgb || !n || n >= (1ull << 32) || reflect_num <= 0)
-    return fail(RFX_ERR_ARG, "trace_rays_ordered: renderer, rays, order, colours, 0 < n < 2^32 and reflect_num > 0 required");
-  if (!r->has_scene) return fail(RFX_ERR_STATE, "trace_rays_ordered: no scene uploaded");
+  int rc;
+  if ((rc = check_call(r, d_rays && d_order && d_rgb && n && n < (1ull << 32) && reflect_num > 0, "trace_rays_ordered",
+                       "renderer, rays, order, colours, 0 < n < 2^32 and reflect_num > 0 required")) != RFX_OK)
+    return rc;
   // one launch: the randDir states of the whole batch must stand, since a slot may name any ray
   if (n > r->launch_traces)
     return fail(RFX_ERR_ARG, "trace_rays_ordered: %llu rays exceed the launch limit of %llu (split the batch and order each part)",
                 (unsigned long long)n, (unsigned long long)r->launch_traces);
-  int rc;
   if ((rc = set_dev(r)) != RFX_OK) return rc;
-  const hipStream_t st = stream ? (hipStream_t)stream : r->stream;
+  const hipStream_t st = stream_or_own(r, stream);
   if ((rc = prepass_traces(r, n, st)) != RFX_OK) return rc;  // ray i takes draw i
   FrameParams P{};
   P.depth = reflect_num;
@@ -104,11 +100,11 @@ extern "C" int rfx_trace_rays_ordered(rfx_renderer *r, const float *d_rays, cons
   return RFX_OK;
 }
 
-// The slots in launches of at most launch_traces, rounded down to whole waves and never below one (rfx_hits.cpp
-// run_query's rule); every launch sees the whole arrays.
+// The slots in launches of a linear batch's size (rays_per_launch, as rfx_hits.cpp run_query); every launch sees the
+// whole arrays.
 static int run_query_ordered(rfx_renderer *r, const HitParams &H, const uint32_t *d_order, bool any, hipStream_t st)
 {
-  const uint64_t per = std::max<uint64_t>(1, r->launch_traces / 64) * 64;
+  const uint64_t per = rays_per_launch(r, 0);
   for (uint64_t a = 0; a < H.n; a += per)
   {
     HitOrderParams Q{};
@@ -124,36 +120,28 @@ static int run_query_ordered(rfx_renderer *r, const HitParams &H, const uint32_t
 extern "C" int rfx_query_hits_ordered(rfx_renderer *r, const float *d_rays, const uint32_t *d_order, uint64_t n,
                                       const rfx_hit_planes *out, void *stream)
 {
-  if (!r || !d_rays || !d_order || !n || n >= (1ull << 32) || !out ||
-      !(out->object || out->distance || out->point || out->normal || out->reflected || out->colour))
-    return fail(RFX_ERR_ARG, "query_hits_ordered: renderer, rays, order, 0 < n < 2^32 and at least one output plane required");
-  if (!r->has_scene) return fail(RFX_ERR_STATE, "query_hits_ordered: no scene uploaded");
   int rc;
-  if ((rc = set_dev(r)) != RFX_OK) return rc;
+  if ((rc = enter_call(r, d_rays && d_order && n && n < (1ull << 32) && out && any_plane(out), "query_hits_ordered",
+                       "renderer, rays, order, 0 < n < 2^32 and at least one output plane required")) != RFX_OK)
+    return rc;
   HitParams H{};
   H.rays = d_rays;
   H.n = n;
-  H.object = out->object;
-  H.distance = out->distance;
-  H.point = out->point;
-  H.normal = out->normal;
-  H.reflected = out->reflected;
-  H.colour = out->colour;
-  return run_query_ordered(r, H, d_order, false, stream ? (hipStream_t)stream : r->stream);
+  set_planes(H, out);
+  return run_query_ordered(r, H, d_order, false, stream_or_own(r, stream));
 }
 
 extern "C" int rfx_query_occluded_ordered(rfx_renderer *r, const float *d_rays, const int32_t *d_skip,
                                           const uint32_t *d_order, uint64_t n, uint8_t *d_occluded, void *stream)
 {
-  if (!r || !d_rays || !d_order || !n || n >= (1ull << 32) || !d_occluded)
-    return fail(RFX_ERR_ARG, "query_occluded_ordered: renderer, rays, order, 0 < n < 2^32 and the result array required");
-  if (!r->has_scene) return fail(RFX_ERR_STATE, "query_occluded_ordered: no scene uploaded");
   int rc;
-  if ((rc = set_dev(r)) != RFX_OK) return rc;
+  if ((rc = enter_call(r, d_rays && d_order && n && n < (1ull << 32) && d_occluded, "query_occluded_ordered",
+                       "renderer, rays, order, 0 < n < 2^32 and the result array required")) != RFX_OK)
+    return rc;
   HitParams H{};
   H.rays = d_rays;
   H.skip = d_skip;
   H.n = n;
   H.occluded = d_occluded;
-  return run_query_ordered(r, H, d_order, true, stream ? (hipStream_t)stream : r->stream);
+  return run_query_ordered(r, H, d_order, true, stream_or_own(r, stream));
 }

@@ -1,8 +1,8 @@
 // The coherent order's sort (include/rfx.h rfx_rays_order): the ray keys and a stable LSD radix sort of (key, index)
 // pairs -- its own TU (reflaxman_amd/_build.py).
 //
-//   order_keys_kernel    : a lane per ray, the 24-B record read non-temporally (rfx_hits.h load_ray's read), the key of
-//                          rfx.h "Coherent order" written in ray order.
+//   order_keys_kernel    : a lane per ray, the 24-B record read non-temporally (rfx_ray_slot.h load_ray's read), the
+//                          key of rfx.h "Coherent order" written in ray order.
 //   order_hist_kernel    : a digit pass's per-workgroup histograms, table[digit][workgroup].
 //   order_scan_kernel    : workgroup d scans row d of the table in place (exclusive) and leaves the row's total.
 //   order_scatter_kernel : the stable scatter.  A pair's place is (the digits below its own, from the scanned totals) +

@@ -4,32 +4,19 @@
 // A batch is the renderer's frame path without a frame: the pre-pass of n traces (rfx_host.cpp prepass_traces, in the
 // form an unsplit frame launch of n traces takes), then trace_rays_kernel (rfx_rays.h) with one lane per ray.  It keeps
 // no per-frame state: no tile schedule, no per-view masks, no regroup queue, no timing sums.
-#include <algorithm>
-
 #include "rfx_internal.h"
 
 using namespace rfx;
 
-// a wave's raster tile is 8 x 8 rays; a raster launch takes whole tile rows, at most this many (the grid's y limit)
-constexpr uint64_t kTileRows = 8, kMaxTileRowsPerLaunch = 32768;
-
 extern "C" int rfx_trace_rays(rfx_renderer *r, const float *d_rays, uint64_t n, int32_t reflect_num,
                               uint32_t raster_width, float *d_rgb, uint32_t *d_argb, uint64_t *d_counters, void *stream)
 {
-  if (!r || !d_rays || !d_rgb || !n || reflect_num <= 0)
-    return fail(RFX_ERR_ARG, "trace_rays: renderer, rays, colours, n > 0 and reflect_num > 0 required");
-  if (!r->has_scene) return fail(RFX_ERR_STATE, "trace_rays: no scene uploaded");
   int rc;
-  if ((rc = set_dev(r)) != RFX_OK) return rc;
-  const hipStream_t st = stream ? (hipStream_t)stream : r->stream;
-  // Launches of at most launch_traces rays, rounded down to whole waves (linear) or whole tile rows (raster) and never
-  // below one: every launch but the last is made of full waves, and its outputs start 16-B aligned where the batch's do
-  const uint64_t W = raster_width;
-  uint64_t per;
-  if (W)
-    per = std::max<uint64_t>(1, std::min(kMaxTileRowsPerLaunch, r->launch_traces / (kTileRows * W))) * kTileRows * W;
-  else
-    per = std::max<uint64_t>(1, r->launch_traces / 64) * 64;
+  if ((rc = enter_call(r, d_rays && d_rgb && n && reflect_num > 0, "trace_rays",
+                       "renderer, rays, colours, n > 0 and reflect_num > 0 required")) != RFX_OK)
+    return rc;
+  const hipStream_t st = stream_or_own(r, stream);
+  const uint64_t per = rays_per_launch(r, raster_width);
   for (uint64_t a = 0; a < n; a += per)
   {
     const uint64_t m = std::min(per, n - a);
@@ -53,11 +40,10 @@ extern "C" int rfx_trace_rays(rfx_renderer *r, const float *d_rays, uint64_t n, 
 extern "C" int rfx_trace_rays_host(rfx_renderer *r, const float *rays, uint64_t n, int32_t reflect_num,
                                    uint32_t raster_width, float *rgb, uint32_t *argb_out, uint64_t *counters)
 {
-  if (!r || !rays || !rgb || !n || reflect_num <= 0)
-    return fail(RFX_ERR_ARG, "trace_rays_host: renderer, rays, colours, n > 0 and reflect_num > 0 required");
-  if (!r->has_scene) return fail(RFX_ERR_STATE, "trace_rays_host: no scene uploaded");
   int rc;
-  if ((rc = set_dev(r)) != RFX_OK) return rc;
+  if ((rc = enter_call(r, rays && rgb && n && reflect_num > 0, "trace_rays_host",
+                       "renderer, rays, colours, n > 0 and reflect_num > 0 required")) != RFX_OK)
+    return rc;
   DevBuf<float> d_rays;
   if ((rc = d_rays.reserve((size_t)n * 6)) < 0 || (rc = r->img.reserve((size_t)n * 3)) < 0 ||
       (rc = r->argb.reserve((size_t)n)) < 0 || (rc = r->cnt.reserve(RFX_NCOUNTERS)) < 0)

@@ -1,11 +1,12 @@
 // The ordered ray-batch and hit-query kernels of librfx.so (rfx_ordered.h) and their launches -- its own TU beside the
 // ray batches and the hit queries (reflaxman_amd/_build.py).
 #include "rfx_ordered.h"
+#include "rfx_batch_launch.h"
 
 namespace rfx {
 
-// One launch of P.p_end rays in the order d_order gives (as many slots).  The cfg by launch_trace_rays' rule for a
-// launch without counters (rfx_trace_rays.hip).
+// One launch of P.p_end rays in the order d_order gives (as many slots), with a ray batch's cfg for a launch without
+// counters.
 hipError_t launch_trace_rays_ordered(const DevScene &S, const FrameParams &P_in, const float *d_rays,
                                      const uint32_t *d_order, hipStream_t st)
 {
@@ -14,24 +15,24 @@ hipError_t launch_trace_rays_ordered(const DevScene &S, const FrameParams &P_in,
   P.W = 0;
   set_ray_records(P, d_rays);
   set_ray_order(P, d_order);
-  const dim3 grid((uint32_t)(((P.p_end + 63) / 64 + kWgWaves - 1) / kWgWaves));
-  const int cfg = (S.n_light > 32 ? kCfgManyLights : 0) | kCfgCull | (S.n_sph <= 32 && S.n_tri <= 32 ? kCfgSmall : 0) |
-                  (S.n_pln > 0 ? kCfgPlanes : 0) | (S.n_light == 1 && RFX_ONE_LIGHT ? kCfgOneLight : 0) |
-                  (RFX_TRI_BVH && S.tri_bvh != nullptr ? kCfgTriBvh : 0);
-  launch_ordered_cfg(cfg, grid, S, P, st);
-  return hipGetLastError();
+  const dim3 grid = batch_grid(P.p_end, 0);
+  const bool found = dispatch_trace_cfg<false>(batch_trace_cfg(S, false), [&](auto c) {
+    hipLaunchKernelGGL((trace_rays_ordered_kernel<decltype(c)::value>), grid, dim3(kWgThreads), 0, st, S, P);
+  });
+  return found ? hipGetLastError() : hipErrorInvalidValue;
 }
 
-// One launch of the slots [P.slot0, P.slot1).  The cfg is launch_query_hits' (rfx_trace_hits.hip).
+// One launch of the slots [P.slot0, P.slot1), with a hit query's cfg
 hipError_t launch_query_hits_ordered(const DevScene &S, const HitOrderParams &P, bool any, hipStream_t st)
 {
   if (P.slot1 <= P.slot0) return hipSuccess;
-  const dim3 grid((uint32_t)(((P.slot1 - P.slot0 + 63) / 64 + kWgWaves - 1) / kWgWaves));
-  const bool small = S.n_sph <= 32 && S.n_tri <= 32;
-  const int cfg = (small ? kCfgSmall : 0) | (S.n_pln > 0 ? kCfgPlanes : 0) |
-                  (RFX_TRI_BVH && !small && S.tri_bvh != nullptr ? kCfgTriBvh : 0);
-  launch_hits_ordered_cfg(cfg, any, grid, S, P, st);
-  return hipGetLastError();
+  const dim3 grid = batch_grid(P.slot1 - P.slot0, 0);
+  const bool found = dispatch_query_cfg(batch_query_cfg(S), [&](auto c) {
+    constexpr int CFG = decltype(c)::value;
+    if (any) hipLaunchKernelGGL((query_occluded_ordered_kernel<CFG>), grid, dim3(kWgThreads), 0, st, S, P);
+    else hipLaunchKernelGGL((query_hits_ordered_kernel<CFG>), grid, dim3(kWgThreads), 0, st, S, P);
+  });
+  return found ? hipGetLastError() : hipErrorInvalidValue;
 }
 
 }  // namespace rfx

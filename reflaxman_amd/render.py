@@ -451,27 +451,19 @@ class Renderer:
         L = _lib.load()
         if order is not None and (raster_width or counters is not None):
             raise ValueError("trace_rays: order goes with neither raster_width nor counters")
-        try:
-            import torch
-            is_torch = isinstance(rays, torch.Tensor)
-        except ImportError:
-            is_torch = False
+        # on any stream but the legacy default one a device tensor is traced asynchronously; that one has no handle to
+        # pass on (NULL is the renderer's own stream, which is not ordered with it): there the call is fenced on both
+        # sides instead, its start by _ray_batch and its end below
+        is_torch, r, stream = self._ray_batch(rays, "trace_rays")
+        n = r.shape[0]
         if is_torch:
-            if not rays.is_cuda or rays.device.index != self.device:
-                raise ValueError("trace_rays: a tensor on the renderer's device (or a numpy array) is required")
-            r = rays.to(torch.float32).reshape(-1, 6).contiguous()
-            n = r.shape[0]
+            import torch
             rgb = torch.empty((n, 3), dtype=torch.float32, device=r.device)
             words = torch.empty(n, dtype=torch.int32, device=r.device) if argb else None
             if counters is not None and not (isinstance(counters, torch.Tensor) and counters.is_cuda and
                                              counters.dtype == torch.int64 and counters.is_contiguous() and
                                              counters.numel() >= _lib.RFX_NCOUNTERS):
                 raise ValueError("trace_rays: counters must be a contiguous int64 device tensor of RFX_NCOUNTERS words")
-            # the legacy default stream has no handle to pass on (NULL is the renderer's own stream, which is not
-            # ordered with it): there the call is fenced on both sides instead; on any other stream it is asynchronous
-            stream = torch.cuda.current_stream(r.device).cuda_stream
-            if not stream:
-                torch.cuda.current_stream(r.device).synchronize()
             if order is not None:
                 o = self._order_tensor(order, r, "trace_rays")
                 check(L.rfx_trace_rays_ordered(self._h, C.c_void_p(r.data_ptr()), C.c_void_p(o.data_ptr()), n, int(depth),
@@ -485,8 +477,6 @@ class Renderer:
             if not stream:
                 self.synchronize()
             return (rgb, words) if argb else rgb
-        r = np.ascontiguousarray(rays, np.float32).reshape(-1, 6)
-        n = r.shape[0]
         rgb = np.empty((n, 3), np.float32)
         words = np.empty(n, np.uint32) if argb else None
         if counters is not None and not (isinstance(counters, np.ndarray) and counters.dtype == np.uint64 and
@@ -523,7 +513,8 @@ class Renderer:
         if not rays.is_cuda or rays.device.index != self.device:
             raise ValueError(f"{what}: a tensor on the renderer's device (or a numpy array) is required")
         r = rays.to(torch.float32).reshape(-1, 6).contiguous()
-        # the legacy default stream has no handle to pass on (trace_rays): there the call is fenced on both sides
+        # the legacy default stream has no handle to pass on (trace_rays): there the call is fenced on both sides, here
+        # and by the caller once it is enqueued
         stream = torch.cuda.current_stream(r.device).cuda_stream
         if not stream:
             torch.cuda.current_stream(r.device).synchronize()

@@ -6,10 +6,10 @@ lane and occupancy, from the compiler's kernel-resource-usage remarks, for every
     python tools/resource_usage.py --json OUT    # also write the table as JSON
 
 Kernel names are shortened to trace<STATS,MODE,CFG> / bounce<CFG> / bounce_lds<CFG> (the LDS-staged BVH form) /
-query_hits<CFG> / query_occluded<CFG> (rfx_trace_hits.hip) / trace_rays_ordered<CFG>, query_hits_ordered<CFG>,
-query_occluded_ordered<CFG> (rfx_trace_ordered.hip) / order_keys, order_hist, order_scan, order_scatter (the coherent
-order's sort, rfx_order_sort.hip); CFG bits (rfx_types.h kCfg*): 1 cull, 2 >32 lights, 4 small
-scene, 8 planes, 16 park, 32 one light, 64 triangle BVH.
+trace_rays<STATS,CFG> (rfx_trace_rays.hip) / query_hits<CFG>, query_occluded<CFG> (rfx_trace_hits.hip) /
+trace_rays_ordered<CFG>, query_hits_ordered<CFG>, query_occluded_ordered<CFG> (rfx_trace_ordered.hip) / order_keys,
+order_hist, order_scan, order_scatter (the coherent order's sort, rfx_order_sort.hip); CFG bits (rfx_types.h kCfg*):
+1 cull, 2 >32 lights, 4 small scene, 8 planes, 16 park, 32 one light, 64 triangle BVH.
 """
 from __future__ import annotations
 
@@ -40,6 +40,9 @@ def short(name: str) -> str:
     m = re.match(r"_ZN3rfx17bounce_kernel_ldsILi(\d+)EEEv", name)
     if m:
         return f"bounce_lds<{m.group(1)}>"
+    m = re.match(r"_ZN3rfx17trace_rays_kernelILb(\d)ELi(\d+)EEEv", name)
+    if m:
+        return f"trace_rays<{'stats' if m.group(1) == '1' else 'fast'},{m.group(2)}>"
     m = re.match(r"_ZN3rfx(?:17query_hits|21query_occluded)_kernelILi(\d+)EEEv", name)
     if m:
         return f"{'query_hits' if 'query_hits' in name else 'query_occluded'}<{m.group(1)}>"
@@ -71,7 +74,7 @@ def usage(tu: str):
             out.append(cur)
         elif cur is not None and key in FIELDS:
             cur[FIELDS[key]] = int(val)
-    return [k for k in out if k["kernel"].startswith(("trace<", "bounce<", "bounce_lds<", "query_hits<", "query_occluded<",
+    return [k for k in out if k["kernel"].startswith(("trace<", "trace_rays<", "bounce<", "bounce_lds<", "query_hits<", "query_occluded<",
                                                       "trace_rays_ordered<", "query_hits_ordered<",
                                                       "query_occluded_ordered<", "order_"))]
 
