@@ -351,8 +351,8 @@ int rfx_frame_rng_rewind(rfx_renderer *r);
  *
  * rfx_query_occluded: d_occluded[i] = 1 if any object other than d_skip[i] returns true from
  * trace(origin, ray, NULL, ...) (Scene.cpp:133-143), else 0.  The ray is unbounded, as the reference's shadow ray is:
- * an object beyond the light still occludes it.  A segment test is rfx_query_hits' distance against the segment's
- * length.  d_skip NULL skips nothing, and so does a value outside [0, objects).
+ * an object beyond the light still occludes it.  A segment test is rfx_query_occluded_span with d_hi ("Ray intervals"
+ * below).  d_skip NULL skips nothing, and so does a value outside [0, objects).
  *
  * Neither call touches the random streams (there is no pre-pass: rfx_renderer_get_rng reads the same before and
  * after), the per-view masks, the tile costs, the regroup queue, the timing sums, or what rfx_frame_rng_rewind may
@@ -376,6 +376,66 @@ int rfx_query_hits_host(rfx_renderer *r, const float *rays, uint64_t n, uint32_t
                         const rfx_hit_planes *out /* host pointers */);
 int rfx_query_occluded_host(rfx_renderer *r, const float *rays, const int32_t *skip, uint64_t n,
                             uint32_t raster_width, uint8_t *occluded);
+
+/*
+ * Ray intervals: the two hit queries on a per-ray interval of distances -- "is B visible from A" (a shadow ray to a
+ * finite light, a portal, a line of sight) and "what lies behind the first hit" (picking through glass, depth peeling,
+ * every hit along a probe).  Added under RFX_ABI_VERSION 5 without raising it, as the hit queries were: detect by
+ * symbol (dlsym).  Nothing that existed changes.
+ *
+ * Candidates: for ray i, object j (the index its add call returned) is a candidate iff the reference's
+ * trace(origin, ray, &drop, ..., &curDist, ...) returns true; its distance dist is that call's curDist, a float.  This
+ * is rfx_query_hits' notion.  rfx_query_occluded_span is defined by the same out-parameter form, not by
+ * trace(origin, ray, NULL, ...).
+ *
+ * The span: three optional per-ray device arrays, indexed by the ray index i in every form (the ordered forms read
+ * d_lo[d_order[s]]).  A candidate is eligible iff
+ *   (d_hi == NULL || dist <= hi[i])   -- the upper end is inclusive -- and
+ *   (d_lo == NULL || dist > lo[i] || (dist == lo[i] && j > after[i]))
+ * i.e. (dist, j) comes after (lo, after) in the reference's own order, distance first, then insertion index.
+ * after = -1 (and d_after NULL) makes the lower end inclusive, after = INT32_MAX exclusive, after = the previous winner
+ * steps through objects at exactly one distance one at a time.  d_after is read only where d_lo is given.  The
+ * comparisons are plain float comparisons on the rounded dist: a NaN end makes nothing eligible, and so do lo = +inf
+ * and hi < 0; lo < 0 bounds nothing, hi >= FLT_MAX bounds nothing (curDist still starts at FLT_MAX, Scene.cpp:82),
+ * and -0.0 equals 0.0.  span NULL, or all its arrays NULL, means no ends.
+ *
+ * rfx_query_hits_span: the winner is the eligible candidate with the least dist, among equal dist the lowest index --
+ * rfx_query_hits' rule on the eligible set.  The planes are written exactly as rfx_query_hits writes them, the miss
+ * values where no candidate is eligible.  Without ends every word is rfx_query_hits'.
+ * Layers: calling again with (lo, after) = (the previous distance, the previous object) enumerates a ray's candidates
+ * in ascending (dist, index), each exactly once; that sequence defines the ray's layers.
+ *
+ * rfx_query_occluded_span: d_occluded[i] = 1 iff an eligible candidate other than d_skip[i] exists; it takes d_lo and
+ * d_hi only (d_after is not read: the lower end is inclusive).  Without ends it equals rfx_query_occluded on every
+ * scene whose objects answer both forms of trace() alike.  A segment test "is b visible from a" is the ray (a, b - a)
+ * with hi = |b - a|: the far end is inclusive, and one float below excludes an object at b itself.
+ *
+ * The ordered and host forms are the hit queries'; launch splitting above rfx_renderer_set_launch_traces advances the
+ * span arrays with the other per-ray arrays (ordered forms: slot ranges over whole arrays).  Errors and state rules are
+ * those of rfx_query_hits and rfx_query_occluded, and like them the calls touch nothing but the uploaded scene: no
+ * random stream, masks, tile costs or rewind state.
+ */
+typedef struct {
+  const float   *d_lo;     /* n, or NULL: no lower end */
+  const int32_t *d_after;  /* n, or NULL: -1 for every ray; read only where d_lo is given */
+  const float   *d_hi;     /* n, or NULL: no upper end */
+} rfx_ray_span;
+int rfx_query_hits_span(rfx_renderer *r, const float *d_rays, const rfx_ray_span *span /* or NULL */, uint64_t n,
+                        uint32_t raster_width, const rfx_hit_planes *out, void *stream);
+int rfx_query_occluded_span(rfx_renderer *r, const float *d_rays, const int32_t *d_skip,
+                            const rfx_ray_span *span /* or NULL */, uint64_t n, uint32_t raster_width,
+                            uint8_t *d_occluded, void *stream);
+int rfx_query_hits_span_ordered(rfx_renderer *r, const float *d_rays, const rfx_ray_span *span /* or NULL */,
+                                const uint32_t *d_order, uint64_t n, const rfx_hit_planes *out, void *stream);
+int rfx_query_occluded_span_ordered(rfx_renderer *r, const float *d_rays, const int32_t *d_skip,
+                                    const rfx_ray_span *span /* or NULL */, const uint32_t *d_order, uint64_t n,
+                                    uint8_t *d_occluded, void *stream);
+/* The same on host arrays (the span's included): they copy in and out on the renderer's stream and synchronise. */
+int rfx_query_hits_span_host(rfx_renderer *r, const float *rays, const rfx_ray_span *span /* host pointers, or NULL */,
+                             uint64_t n, uint32_t raster_width, const rfx_hit_planes *out /* host pointers */);
+int rfx_query_occluded_span_host(rfx_renderer *r, const float *rays, const int32_t *skip,
+                                 const rfx_ray_span *span /* host pointers, or NULL */, uint64_t n,
+                                 uint32_t raster_width, uint8_t *occluded);
 
 /*
  * Coherent order: rfx_trace_rays and the hit queries run one lane per ray, and a wave is fast only when its 64 rays are

@@ -51,6 +51,11 @@ class HitPlanes(C.Structure):
     _fields_ = [(n, C.c_void_p) for n in ("object", "distance", "point", "normal", "reflected", "colour")]
 
 
+class RaySpan(C.Structure):
+    """rfx_ray_span (include/rfx.h "Ray intervals"): one pointer per end of the per-ray interval, 0 = none."""
+    _fields_ = [(n, C.c_void_p) for n in ("d_lo", "d_after", "d_hi")]
+
+
 _i32p = C.POINTER(C.c_int32)
 
 # (name, restype, argtypes) for every symbol of include/rfx.h
@@ -111,6 +116,18 @@ SIGNATURES = [
     ("rfx_query_hits_host", C.c_int, [C.c_void_p, _fp, C.c_uint64, C.c_uint32, C.POINTER(HitPlanes)]),
     ("rfx_query_occluded", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32, C.c_void_p, C.c_void_p]),
     ("rfx_query_occluded_host", C.c_int, [C.c_void_p, _fp, _i32p, C.c_uint64, C.c_uint32, C.POINTER(C.c_uint8)]),
+    ("rfx_query_hits_span", C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(RaySpan), C.c_uint64, C.c_uint32,
+                                      C.POINTER(HitPlanes), C.c_void_p]),
+    ("rfx_query_occluded_span", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(RaySpan), C.c_uint64, C.c_uint32,
+                                          C.c_void_p, C.c_void_p]),
+    ("rfx_query_hits_span_ordered", C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(RaySpan), C.c_void_p, C.c_uint64,
+                                              C.POINTER(HitPlanes), C.c_void_p]),
+    ("rfx_query_occluded_span_ordered", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(RaySpan), C.c_void_p,
+                                                  C.c_uint64, C.c_void_p, C.c_void_p]),
+    ("rfx_query_hits_span_host", C.c_int, [C.c_void_p, _fp, C.POINTER(RaySpan), C.c_uint64, C.c_uint32,
+                                           C.POINTER(HitPlanes)]),
+    ("rfx_query_occluded_span_host", C.c_int, [C.c_void_p, _fp, _i32p, C.POINTER(RaySpan), C.c_uint64, C.c_uint32,
+                                               C.POINTER(C.c_uint8)]),
     ("rfx_renderer_order_box", C.c_int, [C.c_void_p, _fp, _fp]),
     ("rfx_rays_order", C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p]),
     ("rfx_rays_order_host", C.c_int, [C.c_void_p, _fp, C.c_uint64, _u32p, _u32p]),

@@ -8,8 +8,8 @@
 // call's and only the company a ray keeps in its wave changes.  A slot past the launch's end, or one whose index is
 // not a ray of the batch, is a dead lane: it reads and writes nothing, and reaches the wave-wide code as an invalid
 // lane does.  Outputs leave per lane (12-B and 4-B stores): a wave's rays are nowhere near each other, so the staged
-// 16-B forms of the unordered kernels do not apply.  There is no stats form.  rfx_trace_ordered.hip is the one unit
-// that includes this.
+// 16-B forms of the unordered kernels do not apply.  There is no stats form.  rfx_trace_ordered.hip holds these kernels;
+// rfx_span.h includes this for ordered_slot alone.
 #pragma once
 #include <hip/hip_runtime.h>
 

@@ -520,13 +520,44 @@ class Renderer:
             torch.cuda.current_stream(r.device).synchronize()
         return True, r, stream
 
-    def query_hits(self, rays, raster_width: int = 0, want=HIT_PLANES, order=None):
+    def _span(self, what, n, is_torch, device, lo=None, after=None, hi=None):
+        """The interval arrays of a span query (rfx.h rfx_ray_span) as {end: n-entry array of the kind the rays are},
+        or None when no end is given.  A scalar end holds for every ray; ``after`` counts only beside ``lo``."""
+        if after is not None and lo is None:
+            raise ValueError(f"{what}: after goes with lo")
+        if lo is None and hi is None:
+            return None
+        ends = {}
+        for k, v, dt in (("d_lo", lo, "float32"), ("d_after", after, "int32"), ("d_hi", hi, "float32")):
+            if v is None:
+                continue
+            if is_torch:
+                import torch
+                if isinstance(v, np.ndarray):
+                    v = np.array(v)  # (a copy: torch takes no read-only array)
+                a = torch.as_tensor(v, device=device).to(getattr(torch, dt)).reshape(-1)
+                a = (a.expand(n) if a.numel() == 1 else a).contiguous()
+                size = a.numel()
+            else:
+                a = np.asarray(v, dt).reshape(-1)
+                a = np.ascontiguousarray(np.broadcast_to(a, (n,)) if a.size == 1 else a)
+                size = a.size
+            if size != n:
+                raise ValueError(f"{what}: one {k[2:]} entry per ray")
+            ends[k] = a
+        return ends
+
+    def query_hits(self, rays, raster_width: int = 0, want=HIT_PLANES, order=None, lo=None, after=None, hi=None):
         """The closest hit of every ray (rfx.h rfx_query_hits: one pass of Scene.cpp:82-107): a dict of the planes
         named in ``want`` -- object (n, int32, -1 = no hit), distance (n, FLT_MAX on a miss), point, normal, reflected,
         colour ((n, 3), zero on a miss).  ``rays`` as for trace_rays: a torch tensor on this renderer's device is
         queried where it lies, on torch's current stream, and tensors come back; anything else goes through numpy and
         the host form, which synchronises.  No random stream moves.  order: as for trace_rays (rfx.h
-        rfx_query_hits_ordered): an index array or "coherent"; not with raster_width."""
+        rfx_query_hits_ordered): an index array or "coherent"; not with raster_width.
+        lo, after, hi: a per-ray interval (rfx.h "Ray intervals", rfx_query_hits_span) -- the winner is the closest
+        candidate with distance <= hi and (distance, object) after (lo, after): after = -1 (the default) includes a
+        candidate at lo itself, INT32_MAX excludes it, the previous winner steps to the next object at that distance.
+        Arrays of n entries of the kind ``rays`` is, or one number for every ray."""
         if order is not None and raster_width:
             raise ValueError("query_hits: order goes with no raster_width")
         want = tuple(want)
@@ -543,7 +574,18 @@ class Renderer:
                    for k in want}
             for k in want:
                 setattr(hp, k, out[k].data_ptr())
-            if order is not None:
+            ends = self._span("query_hits", n, True, r.device, lo, after, hi)
+            if ends is not None:
+                sp = _lib.RaySpan(**{k: a.data_ptr() for k, a in ends.items()})
+                if order is not None:
+                    o = self._order_tensor(order, r, "query_hits")
+                    check(L.rfx_query_hits_span_ordered(self._h, C.c_void_p(r.data_ptr()), C.byref(sp),
+                                                        C.c_void_p(o.data_ptr()), n, C.byref(hp),
+                                                        C.c_void_p(stream or None)), "rfx_query_hits_span_ordered")
+                else:
+                    check(L.rfx_query_hits_span(self._h, C.c_void_p(r.data_ptr()), C.byref(sp), n, int(raster_width),
+                                                C.byref(hp), C.c_void_p(stream or None)), "rfx_query_hits_span")
+            elif order is not None:
                 o = self._order_tensor(order, r, "query_hits")
                 check(L.rfx_query_hits_ordered(self._h, C.c_void_p(r.data_ptr()), C.c_void_p(o.data_ptr()), n,
                                                C.byref(hp), C.c_void_p(stream or None)), "rfx_query_hits_ordered")
@@ -554,6 +596,7 @@ class Renderer:
                 self.synchronize()
             return out
         out = {k: np.empty(shape(k), np.int32 if k == "object" else np.float32) for k in want}
+        ends = self._span("query_hits", n, False, None, lo, after, hi)
         if order is not None:
             with self._DeviceArrays(self) as dev:
                 d_rays = dev.put(r)
@@ -561,21 +604,34 @@ class Renderer:
                 d_out = {k: dev.alloc(out[k].nbytes) for k in want}
                 for k in want:
                     setattr(hp, k, d_out[k].value)
-                check(L.rfx_query_hits_ordered(self._h, d_rays, d_order, n, C.byref(hp), None), "rfx_query_hits_ordered")
+                if ends is not None:
+                    sp = _lib.RaySpan(**{k: dev.put(a).value for k, a in ends.items()})
+                    check(L.rfx_query_hits_span_ordered(self._h, d_rays, C.byref(sp), d_order, n, C.byref(hp), None),
+                          "rfx_query_hits_span_ordered")
+                else:
+                    check(L.rfx_query_hits_ordered(self._h, d_rays, d_order, n, C.byref(hp), None),
+                          "rfx_query_hits_ordered")
                 for k in want:
                     dev.get(out[k], d_out[k])
             return out
         for k in want:
             setattr(hp, k, out[k].ctypes.data)
+        if ends is not None:
+            sp = _lib.RaySpan(**{k: a.ctypes.data for k, a in ends.items()})
+            check(L.rfx_query_hits_span_host(self._h, _lib.fptr(r), C.byref(sp), n, int(raster_width), C.byref(hp)),
+                  "rfx_query_hits_span_host")
+            return out
         check(L.rfx_query_hits_host(self._h, _lib.fptr(r), n, int(raster_width), C.byref(hp)), "rfx_query_hits_host")
         return out
 
-    def occluded(self, rays, skip=None, raster_width: int = 0, order=None):
+    def occluded(self, rays, skip=None, raster_width: int = 0, order=None, lo=None, hi=None):
         """Whether anything stands in each ray's way (rfx.h rfx_query_occluded, the shadow rays' any-hit of
-        Scene.cpp:133-143): (n,) uint8, 1 = some object other than ``skip[i]`` is hit.  The ray is unbounded.  skip:
-        (n,) int32 object indices (None, or a value outside [0, objects): nothing is left out), of the kind ``rays``
+        Scene.cpp:133-143): (n,) uint8, 1 = some object other than ``skip[i]`` is hit.  Without ``lo`` / ``hi`` (below)
+        the ray is unbounded.  skip: (n,) int32 object indices (None, or a value outside [0, objects): nothing is left out), of the kind ``rays``
         is -- a device tensor with a device tensor, else numpy.  order: as for trace_rays (rfx.h
-        rfx_query_occluded_ordered): an index array or "coherent"; not with raster_width."""
+        rfx_query_occluded_ordered): an index array or "coherent"; not with raster_width.
+        lo, hi: a per-ray interval (rfx.h rfx_query_occluded_span), both ends inclusive: only objects hit at a distance
+        in [lo, hi] count -- the ray becomes a segment.  Arrays of n entries of the kind ``rays`` is, or one number."""
         if order is not None and raster_width:
             raise ValueError("occluded: order goes with no raster_width")
         L = _lib.load()
@@ -590,7 +646,19 @@ class Renderer:
                     raise ValueError("occluded: one skip entry per ray")
             occ = torch.empty(n, dtype=torch.uint8, device=r.device)
             d_skip = C.c_void_p(sk.data_ptr() if sk is not None else None)
-            if order is not None:
+            ends = self._span("occluded", n, True, r.device, lo, None, hi)
+            if ends is not None:
+                sp = _lib.RaySpan(**{k: a.data_ptr() for k, a in ends.items()})
+                if order is not None:
+                    o = self._order_tensor(order, r, "occluded")
+                    check(L.rfx_query_occluded_span_ordered(self._h, C.c_void_p(r.data_ptr()), d_skip, C.byref(sp),
+                                                            C.c_void_p(o.data_ptr()), n, C.c_void_p(occ.data_ptr()),
+                                                            C.c_void_p(stream or None)), "rfx_query_occluded_span_ordered")
+                else:
+                    check(L.rfx_query_occluded_span(self._h, C.c_void_p(r.data_ptr()), d_skip, C.byref(sp), n,
+                                                    int(raster_width), C.c_void_p(occ.data_ptr()),
+                                                    C.c_void_p(stream or None)), "rfx_query_occluded_span")
+            elif order is not None:
                 o = self._order_tensor(order, r, "occluded")
                 check(L.rfx_query_occluded_ordered(self._h, C.c_void_p(r.data_ptr()), d_skip, C.c_void_p(o.data_ptr()), n,
                                                    C.c_void_p(occ.data_ptr()), C.c_void_p(stream or None)),
@@ -607,20 +675,76 @@ class Renderer:
             if sk.size != n:
                 raise ValueError("occluded: one skip entry per ray")
         occ = np.empty(n, np.uint8)
+        ends = self._span("occluded", n, False, None, lo, None, hi)
         if order is not None:
             with self._DeviceArrays(self) as dev:
                 d_rays = dev.put(r)
                 d_order = self._order_array(dev, order, d_rays, n, "occluded")
                 d_skip = dev.put(sk) if sk is not None else None
                 d_occ = dev.alloc(n)
-                check(L.rfx_query_occluded_ordered(self._h, d_rays, d_skip, d_order, n, d_occ, None),
-                      "rfx_query_occluded_ordered")
+                if ends is not None:
+                    sp = _lib.RaySpan(**{k: dev.put(a).value for k, a in ends.items()})
+                    check(L.rfx_query_occluded_span_ordered(self._h, d_rays, d_skip, C.byref(sp), d_order, n, d_occ, None),
+                          "rfx_query_occluded_span_ordered")
+                else:
+                    check(L.rfx_query_occluded_ordered(self._h, d_rays, d_skip, d_order, n, d_occ, None),
+                          "rfx_query_occluded_ordered")
                 dev.get(occ, d_occ)
+            return occ
+        if ends is not None:
+            sp = _lib.RaySpan(**{k: a.ctypes.data for k, a in ends.items()})
+            check(L.rfx_query_occluded_span_host(self._h, _lib.fptr(r), sk.ctypes.data_as(_lib._i32p) if sk is not None else None,
+                                                 C.byref(sp), n, int(raster_width), occ.ctypes.data_as(C.POINTER(C.c_uint8))),
+                  "rfx_query_occluded_span_host")
             return occ
         check(L.rfx_query_occluded_host(self._h, _lib.fptr(r), sk.ctypes.data_as(_lib._i32p) if sk is not None else None,
                                         n, int(raster_width), occ.ctypes.data_as(C.POINTER(C.c_uint8))),
               "rfx_query_occluded_host")
         return occ
+
+    def query_layers(self, rays, k: int, want=HIT_PLANES, raster_width: int = 0, order=None):
+        """The first k layers of every ray (rfx.h "Ray intervals"): a list of k dicts of the planes in ``want``, layer
+        0 the closest hit, layer l + 1 the closest candidate after layer l's (distance, object) -- a ray's candidates in
+        ascending (distance, index), each once, objects at exactly one distance lower index first.  A ray that has run
+        out of candidates is a miss in every later layer.  k calls of query_hits: the stepping planes (object,
+        distance) are computed whether wanted or not."""
+        if k < 1:
+            raise ValueError("query_layers: k >= 1 required")
+        want = tuple(want)
+        ask = want + tuple(p for p in ("object", "distance") if p not in want)
+        layers, lo, after = [], None, None
+        for _ in range(int(k)):
+            out = self.query_hits(rays, raster_width=raster_width, want=ask, order=order, lo=lo, after=after)
+            obj, dist = out["object"], out["distance"]
+            # a ray that missed stays out: its lower end becomes +inf, which no candidate lies after
+            if isinstance(dist, np.ndarray):
+                dist = np.where(obj < 0, np.float32(np.inf), dist)
+            else:
+                dist = dist.masked_fill(obj < 0, float("inf"))
+            layers.append({p: out[p] for p in want})
+            lo, after = dist, obj
+        return layers
+
+    def visible(self, a, b, skip=None):
+        """Whether point b[i] is visible from point a[i]: (n,) uint8, 1 = nothing (but ``skip[i]``) is hit on the
+        segment.  The ray is (a, b - a) and its upper end hi = |b - a| as float32 sqrt(dx^2 + dy^2 + dz^2); the far
+        end is inclusive -- an object hit at exactly that distance hides b -- and a caller who wants it open passes
+        occluded(..., hi=np.nextafter(hi, 0)) itself.  (n, 3) arrays of one kind: device tensors or numpy."""
+        try:
+            import torch
+            is_torch = isinstance(a, torch.Tensor) or isinstance(b, torch.Tensor)
+        except ImportError:
+            is_torch = False
+        if is_torch:
+            b = torch.as_tensor(b, dtype=torch.float32, device=a.device if isinstance(a, torch.Tensor) else b.device)
+            a = torch.as_tensor(a, dtype=torch.float32, device=b.device).reshape(-1, 3)
+            d = b.reshape(-1, 3) - a
+            hi = torch.sqrt(d[:, 0] * d[:, 0] + d[:, 1] * d[:, 1] + d[:, 2] * d[:, 2])
+            return 1 - self.occluded(torch.cat([a, d], dim=1), skip, hi=hi)
+        a = np.asarray(a, np.float32).reshape(-1, 3)
+        d = np.asarray(b, np.float32).reshape(-1, 3) - a
+        hi = np.sqrt(d[:, 0] * d[:, 0] + d[:, 1] * d[:, 1] + d[:, 2] * d[:, 2], dtype=np.float32)
+        return (1 - self.occluded(np.concatenate([a, d], axis=1), skip, hi=hi)).astype(np.uint8)
 
     def set_tile_order(self, mode: int):
         """Trace-launch schedule (rfx.h rfx_renderer_set_tile_order): 1 longest-tile-first (8x8 wave tiles)
@@ -934,16 +1058,22 @@ class Render:
         o = np.broadcast_to(np.asarray(origins, np.float32).reshape(-1, 3), d.shape)
         return self._r.trace_rays(np.concatenate([o, d], axis=1), reflNumber)
 
-    def pick(self, x: int, y: int):
+    def pick(self, x: int, y: int, layer: int = 0):
         """What lies under pixel (x, y) of the current camera and image size (row 0 = bottom): (object index as the add
-        call returned it, or -1 for the sky; its distance from the eye, |ray t| -- FLT_MAX for the sky).  The ray is cameras.pinhole_ray's, the pixel loop's own (Render.cpp:146-156)."""
+        call returned it, or -1 for the sky; its distance from the eye, |ray t| -- FLT_MAX for the sky).  The ray is cameras.pinhole_ray's, the pixel loop's own (Render.cpp:146-156).
+        layer: what lies behind that many hits (Renderer.query_layers); (-1, FLT_MAX) once the ray has run out."""
         from . import cameras
         W, H = self.imageWidth, self.imageHeight
         if not (0 <= x < W and 0 <= y < H):
             raise ValueError("pick: the pixel lies outside the image")
         self._r.set_scene(self.scene)
         ray = cameras.pinhole_ray(tuple(self.camera.eye), self.camera.view, self.camera.fov, W, H, x, y)
-        out = self._r.query_hits(ray[None, :], want=("object", "distance"))
+        if layer < 0:
+            raise ValueError("pick: layer >= 0 required")
+        if layer:
+            out = self._r.query_layers(ray[None, :], layer + 1, want=("object", "distance"))[layer]
+        else:
+            out = self._r.query_hits(ray[None, :], want=("object", "distance"))
         return int(out["object"][0]), float(out["distance"][0])
 
     def getRng(self):

@@ -2,11 +2,13 @@
 """Depth, object-id and normal images of a scene from its camera (GPU box): the pinhole frame's primary rays through
 one hit query (rfx.h rfx_query_hits) -- no shading, no random stream -- written as three TGA files.
 
-    python tools/aov.py default out/aov [--size 640x480]
+    python tools/aov.py default out/aov [--size 640x480] [--layer K]
 
 writes PREFIX_depth.tga (grey: near white, far black, scaled to the frame's own nearest and farthest hit; the sky
 black), PREFIX_object.tga (a fixed colour per object index, the sky black) and PREFIX_normal.tga (the unit normal
-mapped from [-1, 1] to [0, 255] per channel, the sky black).
+mapped from [-1, 1] to [0, 255] per channel, the sky black).  --layer K: the images of what lies behind K hits of every
+pixel's ray (Renderer.query_layers, rfx.h "Ray intervals"; 0, the default, is the first hit), a pixel whose ray has run out
+of hits black.
 """
 import argparse
 import os
@@ -31,6 +33,7 @@ def main():
     ap.add_argument("scene", help="a scene name (reflaxman_amd.scenes) or a .scene file")
     ap.add_argument("prefix", help="the files written are PREFIX_depth.tga, PREFIX_object.tga, PREFIX_normal.tga")
     ap.add_argument("--size", default="640x480", help="WxH")
+    ap.add_argument("--layer", type=int, default=0, help="the K-th hit behind the first (0: the first)")
     args = ap.parse_args()
     W, H = (int(v) for v in args.size.lower().split("x"))
     desc = scenes.parse_scene_file(args.scene) if os.path.isfile(args.scene) else scenes.get_scene(args.scene)
@@ -39,7 +42,11 @@ def main():
     r.set_scene(scene)
     # rows bottom-up, as the renderer's images and rfx_tga_save's rows are; an 8x8 tile of the raster per wave
     rays = cameras.pinhole_rays(tuple(cam.eye), cam.view, cam.fov, W, H)
-    out = r.query_hits(rays, raster_width=W, want=("object", "distance", "normal"))
+    if args.layer < 0:
+        ap.error("--layer: 0 or more")
+    want = ("object", "distance", "normal")
+    out = r.query_layers(rays, args.layer + 1, want=want, raster_width=W)[args.layer] if args.layer else \
+        r.query_hits(rays, raster_width=W, want=want)
     r.close()
     hit = out["object"] >= 0
     images = {}
@@ -59,7 +66,7 @@ def main():
         path = f"{args.prefix}_{what}.tga"
         _lib.check(_lib.load().rfx_tga_save(os.fsencode(path), W, H, _lib.u32ptr(pack(img.astype(np.uint8).reshape(H, W, 3)))),
                    "rfx_tga_save")
-    print(f"{args.prefix}_{{depth,object,normal}}.tga: {W}x{H} of {desc.name}, {int(hit.sum())} of {W * H} pixels hit")
+    print(f"{args.prefix}_{{depth,object,normal}}.tga: {W}x{H} of {desc.name}, layer {args.layer}, {int(hit.sum())} of {W * H} pixels hit")
 
 
 if __name__ == "__main__":

@@ -27,6 +27,17 @@ device events; medians over the rounds):
                                ordered call's scattered stores cost (it writes each ray's words where the ray lies in
                                the caller's arrays, not where its wave runs)
 One JSON line per arm goes to stdout and to DIR/hits_<config>.jsonl (default profiles/r13).
+
+--span: the span queries' arms instead (rfx.h "Ray intervals"), by the same method, to DIR/span_<config>.jsonl:
+    hits, hits_again           rfx_query_hits, all six planes, raster; twice: the pair is the run's noise band
+    hits_span_none             rfx_query_hits_span without ends, the same planes: what carrying the span costs
+    occluded, occluded_span_none   the same pair for the any-hit
+    seg<f>_span / seg<f>_workaround   segment visibility with hi = f x the depth-1 hit distance (f = 0.5: nothing in the
+                               way, f = 2: the first hit in the way): rfx_query_occluded_span with d_hi, against
+                               rfx_query_hits' distance plane alone followed by a device compare with hi; `occluded` is the
+                               unbounded any-hit beside them.  Before timing the two must agree on every ray
+    layers4 / hits_x4          Renderer.query_layers(rays, 4) (object and distance; its stepping included) against four
+                               plain rfx_query_hits calls for the same two planes
 """
 import argparse
 import ctypes as C
@@ -54,7 +65,10 @@ def main():
     ap.add_argument("--rounds", type=int, default=9)
     ap.add_argument("--calls", type=int, default=20, help="calls per timed window")
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "r13"))
+    ap.add_argument("--span", action="store_true", help="the span queries' arms (see above)")
     args = ap.parse_args()
+    if args.span:
+        return span_main(args)
     import torch
     name, W, H = CONFIGS[args.config]
     desc = scenes.get_scene(name)
@@ -186,6 +200,139 @@ def main():
                            "vs_hits_raster": round(med / statistics.median(ms["hits_raster"]), 4)})
         print(line)
         f.write(line + "\n")
+
+
+def span_main(args):
+    import torch
+    name, W, H = CONFIGS[args.config]
+    scene, cam = build_scene(scenes.get_scene(name))
+    n = W * H
+    stream = torch.cuda.Stream()
+    torch.cuda.set_stream(stream)
+    rays = torch.from_numpy(cameras.pinhole_rays(tuple(cam.eye), cam.view, cam.fov, W, H)).cuda()
+    planes = lambda: {k: torch.zeros((n,) if k in ("object", "distance") else (n, 3),
+                                     dtype=torch.int32 if k == "object" else torch.float32, device="cuda") for k in PLANES}
+    out, out2 = planes(), planes()
+    occ, occ2 = (torch.zeros(n, dtype=torch.uint8, device="cuda") for _ in range(2))
+    L = _lib.load()
+    sp = C.c_void_p(stream.cuda_stream)
+    p = lambda t: C.c_void_p(t.data_ptr())
+
+    def renderer():
+        r = Renderer(sphere_seed=SEED, jitter_seed=0)
+        r.set_stream(stream.cuda_stream)
+        r.set_scene(scene)
+        return r
+
+    def hits_arm(dst, want, span=False, times=1):
+        r = renderer()
+        hp = _lib.HitPlanes(**{k: dst[k].data_ptr() for k in want})
+
+        def call():
+            for _ in range(times):
+                if span:
+                    _lib.check(L.rfx_query_hits_span(r._h, p(rays), None, n, W, C.byref(hp), sp), "rfx_query_hits_span")
+                else:
+                    _lib.check(L.rfx_query_hits(r._h, p(rays), n, W, C.byref(hp), sp), "rfx_query_hits")
+        return r, call
+
+    def occ_arm(dst, hi=None, span=False):
+        r = renderer()
+        rs = _lib.RaySpan(d_hi=hi.data_ptr()) if hi is not None else None
+
+        def call():
+            if span:
+                _lib.check(L.rfx_query_occluded_span(r._h, p(rays), None, C.byref(rs) if rs else None, n, W, p(dst), sp),
+                           "rfx_query_occluded_span")
+            else:
+                _lib.check(L.rfx_query_occluded(r._h, p(rays), None, n, W, p(dst), sp), "rfx_query_occluded")
+        return r, call
+
+    def workaround_arm(dst, hi):
+        r, q = hits_arm(out2, ("distance",))
+
+        def call():
+            q()
+            torch.le(out2["distance"], hi, out=dst)
+        return r, call
+
+    def layers_arm():
+        r = renderer()
+        return r, lambda: r.query_layers(rays, 4, want=("object", "distance"), raster_width=W)
+
+    # the depth-1 distances the segments are cut from
+    r0, first = hits_arm(out, PLANES)
+    first()
+    stream.synchronize()
+    dist = out["distance"].clone()
+    ref = {k: out[k].clone() for k in PLANES}
+    # (a ray that hits nothing gets a segment of length 1: nothing lies on it, and the workaround's FLT_MAX says so too)
+    his = {f: torch.where(ref["object"] >= 0, dist * f, torch.ones_like(dist)) for f in (0.5, 2.0)}
+    seg_occ = {f: torch.zeros(n, dtype=torch.bool, device="cuda") for f in his}
+    arms = [("hits", (r0, first)), ("hits_span_none", hits_arm(out2, PLANES, span=True)), ("occluded", occ_arm(occ)),
+            ("occluded_span_none", occ_arm(occ2, span=True))]
+    for f, hi in his.items():
+        arms += [(f"seg{f}_span", occ_arm(occ2, hi, span=True)), (f"seg{f}_workaround", workaround_arm(seg_occ[f], hi))]
+    arms += [("layers4", layers_arm()), ("hits_x4", hits_arm(out2, ("object", "distance"), times=4)),
+             ("hits_again", hits_arm(out, PLANES))]
+    by = dict(arms)
+    bits = lambda t: t.view(torch.int32) if t.dtype == torch.float32 else t
+    # the checks before timing
+    by["hits_span_none"][1]()
+    by["occluded"][1]()
+    stream.synchronize()
+    check = {"span_none_equal": all(bool(torch.equal(bits(out2[k]), bits(ref[k]))) for k in PLANES)}
+    by["occluded_span_none"][1]()
+    stream.synchronize()
+    check["occluded_span_none_equal"] = bool(torch.equal(occ, occ2))
+    check["occluded"] = int(occ.sum())
+    for f in his:
+        by[f"seg{f}_span"][1]()
+        by[f"seg{f}_workaround"][1]()
+        stream.synchronize()
+        check[f"seg{f}_occluded"] = int(occ2.sum())
+        check[f"seg{f}_equal"] = bool(torch.equal(occ2.bool(), seg_occ[f]))
+    lay = by["layers4"][1]()
+    stream.synchronize()
+    check["layers_hit"] = [int((l["object"] >= 0).sum()) for l in lay]
+    check["layer0_equal"] = bool(torch.equal(lay[0]["object"], ref["object"]))
+    if not all(v for k, v in check.items() if k.endswith("equal")):
+        raise SystemExit(f"hits_bench --span: the check before timing failed: {check}")
+    for arm, (r, call) in arms:
+        for _ in range(3):
+            call()
+    stream.synchronize()
+    ms = {arm: [] for arm, _ in arms}
+    for _ in range(args.rounds):
+        for arm, (r, call) in arms:
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record(stream)
+            for _ in range(args.calls):
+                call()
+            e1.record(stream)
+            e1.synchronize()
+            ms[arm].append(e0.elapsed_time(e1) / args.calls)
+    med = {arm: statistics.median(v) for arm, v in ms.items()}
+    against = {"hits_span_none": "hits", "hits_again": "hits", "occluded_span_none": "occluded", "layers4": "hits_x4"}
+    for f in his:
+        against[f"seg{f}_span"] = f"seg{f}_workaround"
+    os.makedirs(args.out, exist_ok=True)
+    with open(os.path.join(args.out, f"span_{args.config}.jsonl"), "w") as fh:
+        for arm, (r, call) in arms:
+            rec = {"config": args.config, "scene": name, "W": W, "H": H, "arm": arm, "rounds": args.rounds,
+                   "calls_per_window": args.calls, "check": check, "ms_median": round(med[arm], 4),
+                   "ms_min": round(min(ms[arm]), 4), "ms_max": round(max(ms[arm]), 4),
+                   "mrays_s": round(n / med[arm] / 1e3, 1)}
+            if arm in against:
+                rec["vs"] = against[arm]
+                rec["ratio"] = round(med[arm] / med[against[arm]], 4)
+            if arm.endswith("_span") and arm.startswith("seg"):
+                rec["vs_occluded"] = round(med[arm] / med["occluded"], 4)
+            line = json.dumps(rec)
+            print(line)
+            fh.write(line + "\n")
+    for arm, (r, call) in arms:
+        r.close()
 
 
 def sky_pixels(r, desc, dirs, rgb) -> int:

@@ -7,7 +7,8 @@ lane and occupancy, from the compiler's kernel-resource-usage remarks, for every
 
 Kernel names are shortened to trace<STATS,MODE,CFG> / bounce<CFG> / bounce_lds<CFG> (the LDS-staged BVH form) /
 trace_rays<STATS,CFG> (rfx_trace_rays.hip) / query_hits<CFG>, query_occluded<CFG> (rfx_trace_hits.hip) /
-trace_rays_ordered<CFG>, query_hits_ordered<CFG>, query_occluded_ordered<CFG> (rfx_trace_ordered.hip) / order_keys,
+trace_rays_ordered<CFG>, query_hits_ordered<CFG>, query_occluded_ordered<CFG> (rfx_trace_ordered.hip) /
+query_hits_span<CFG>, query_occluded_span<CFG> and their _ordered forms (rfx_trace_span.hip) / order_keys,
 order_hist, order_scan, order_scatter (the coherent order's sort, rfx_order_sort.hip); CFG bits (rfx_types.h kCfg*):
 1 cull, 2 >32 lights, 4 small scene, 8 planes, 16 park, 32 one light, 64 triangle BVH.
 """
@@ -49,6 +50,9 @@ def short(name: str) -> str:
     m = re.match(r"_ZN3rfx\d+(trace_rays|query_hits|query_occluded)_ordered_kernelILi(\d+)EEEv", name)
     if m:
         return f"{m.group(1)}_ordered<{m.group(2)}>"
+    m = re.match(r"_ZN3rfx\d+(query_hits_span|query_occluded_span)_kernelILi(\d+)ELb(\d)EEEv", name)
+    if m:
+        return f"{m.group(1)}{'_ordered' if m.group(3) == '1' else ''}<{m.group(2)}>"
     m = re.match(r"_ZN3rfx\d+(order_\w+?)_kernelE", name)
     if m:
         return m.group(1)
@@ -76,7 +80,8 @@ def usage(tu: str):
             cur[FIELDS[key]] = int(val)
     return [k for k in out if k["kernel"].startswith(("trace<", "trace_rays<", "bounce<", "bounce_lds<", "query_hits<", "query_occluded<",
                                                       "trace_rays_ordered<", "query_hits_ordered<",
-                                                      "query_occluded_ordered<", "order_"))]
+                                                      "query_occluded_ordered<", "query_hits_span", "query_occluded_span",
+                                                      "order_"))]
 
 
 def main():
@@ -85,9 +90,9 @@ def main():
     ap.add_argument("--json", default=None)
     args = ap.parse_args()
     rows = [k for tu in args.tus for k in usage(tu)]
-    print(f"{'kernel':28s} {'vgpr':>5s} {'spill':>6s} {'sgpr_sp':>7s} {'scratch':>8s} {'occ':>4s} {'lds':>6s}")
+    print(f"{'kernel':34s} {'vgpr':>5s} {'spill':>6s} {'sgpr_sp':>7s} {'scratch':>8s} {'occ':>4s} {'lds':>6s}")
     for k in rows:
-        print(f"{k['kernel']:28s} {k.get('vgpr', 0):5d} {k.get('vgpr_spill', 0):6d} {k.get('sgpr_spill', 0):7d} "
+        print(f"{k['kernel']:34s} {k.get('vgpr', 0):5d} {k.get('vgpr_spill', 0):6d} {k.get('sgpr_spill', 0):7d} "
               f"{k.get('scratch', 0):8d} {k.get('occ', 0):4d} {k.get('lds', 0):6d}")
     if args.json:
         os.makedirs(os.path.dirname(os.path.abspath(args.json)), exist_ok=True)
