@@ -115,6 +115,20 @@ int rfx_scene_tri_bvh_dump(const rfx_scene *scene, int32_t counts[5], float *box
  * leader[0 .. triangles - 1], and the operands the rule compares into plane[6 t .. 6 t + 5] = v0 x y z, a31 a32 a33. */
 int rfx_scene_set_tri_mates(rfx_scene *scene, int on);
 int rfx_scene_tri_mates(const rfx_scene *scene, int32_t *leader, float *plane);
+/* Far lights (host only; DESIGN.md "Far lights").  A light L is far when the float32 difference L - d is L, bit for bit,
+ * for every point d with max |d_i| < near, where near = min_i (spacing of floats just below |L_i|) / 2 > 0, and when
+ * its fields are finite, sqlen(L) is finite and above VERY_SMALL_NUMBER, ang = 1 - radius^2 / sqlen(L) > 0, radius >
+ * VERY_SMALL_NUMBER and radius / |L| * 1.001 < 0.5.  Scene::trace's terms of such a light that do not read the hit are
+ * then constants, and the small-scene kernels of a scene with exactly one light read them from the light's record at
+ * every hit inside the bound (the same pixels; a hit outside it takes the general expressions).
+ * rfx_scene_set_far_lights (read by the next rfx_renderer_set_scene): 0 never; 1 (the default) when the scene has one
+ * light, it is far, and every sphere and triangle vertex lies inside the bound; 2 for any one-light scene whose light is
+ * far, whatever the scene's extent.
+ * rfx_scene_far_light writes, where given, terms[8] = {len(L), normalized(L) x y z, 1 - sqrt(ang), near, cos and sin of
+ * the shadow rays' cone about normalized(L)} of light `light` -- all 0 when it is not far -- and returns 1 when the
+ * scene's launches take the far-light kernels under its current setting, 0 when not, < 0 on error. */
+int rfx_scene_set_far_lights(rfx_scene *scene, int mode);
+int rfx_scene_far_light(const rfx_scene *scene, int light, float terms[8]);
 
 /* ---------------------------------------------------------------- Camera */
 /* Camera(eye, at, fov): view = [ox | oy | oz] columns, row-major _11.._33 -- Camera.cpp:24-38 */
@@ -573,7 +587,12 @@ int rfx_rand_dirs(rfx_renderer *r, uint32_t seed, uint64_t n, float *out3, uint3
  *       float class, both edges of the fast path's divisor and quotient bounds): counts[0] = quotients whose bits
  *       differ (0 expected), counts[1] = pairs that took div_rn's fast path, counts[2] = quotients checked (5 per
  *       pair).
+ *   rfx_kat_far_light: the bounce loop's far-light form against its general form for the scene's first light
+ *       (rfx_scene_far_light) at n points d (in n x 3 -> out n x 8): the general expressions' dirToLight x y z, its
+ *       length, its direction x y z and 1 - sqrt(ang) (0 unless ang > 0) at d; all eight NaN where d lies inside the
+ *       light's bound and the light's recorded terms differ from them in any bit.
  */
+int rfx_kat_far_light(rfx_renderer *r, const float *points, uint64_t n, float *out);
 int rfx_kat_objects(rfx_renderer *r, const float *rays, const int32_t *objects, uint64_t n, float *out);
 int rfx_kat_texels(rfx_renderer *r, int texture, const float *in, uint64_t n, float *out);
 int rfx_kat_powf(rfx_renderer *r, const float *xy, uint64_t n, float *out);

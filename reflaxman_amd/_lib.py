@@ -71,6 +71,8 @@ SIGNATURES = [
     ("rfx_scene_tri_bvh_dump", C.c_int, [C.c_void_p, _i32p, _fp, _i32p, _i32p, _i32p]),
     ("rfx_scene_set_tri_mates", C.c_int, [C.c_void_p, C.c_int]),
     ("rfx_scene_tri_mates", C.c_int, [C.c_void_p, _i32p, _fp]),
+    ("rfx_scene_set_far_lights", C.c_int, [C.c_void_p, C.c_int]),
+    ("rfx_scene_far_light", C.c_int, [C.c_void_p, C.c_int, _fp]),
     ("rfx_scene_add_plane", C.c_int, [C.c_void_p, _fp, _fp, C.c_int, _fp, C.c_float, C.c_float]),
     ("rfx_scene_plane_count", C.c_int, [C.c_void_p]),
     ("rfx_triangle_set_texture", C.c_int, [C.c_void_p, C.c_int, C.c_int, _fp]),
@@ -171,6 +173,7 @@ SIGNATURES = [
     ("rfx_kat_objects", C.c_int, [C.c_void_p, _fp, C.POINTER(C.c_int32), C.c_uint64, _fp]),
     ("rfx_kat_texels", C.c_int, [C.c_void_p, C.c_int, _fp, C.c_uint64, _fp]),
     ("rfx_kat_powf", C.c_int, [C.c_void_p, _fp, C.c_uint64, _fp]),
+    ("rfx_kat_far_light", C.c_int, [C.c_void_p, _fp, C.c_uint64, _fp]),
     ("rfx_kat_argb", C.c_int, [C.c_void_p, _fp, C.c_uint64, _u32p]),
     ("rfx_kat_powf_cube", C.c_int, [C.c_void_p, C.POINTER(C.c_uint64)]),
     ("rfx_kat_div", C.c_int, [C.c_void_p, C.c_uint64, C.c_uint64, C.POINTER(C.c_uint64)]),

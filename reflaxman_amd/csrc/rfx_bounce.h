@@ -110,8 +110,33 @@ __device__ __forceinline__ const FrameParams &kernarg_params()
   return *(const FrameParams *)(const __attribute__((address_space(4))) FrameParams *)(p + kParamsOff);
 }
 
+// A far light's bound (rfx_types.h LightRec::near): origin - d is origin, bit for bit, for this d.  A NaN coordinate
+// fails, and so does every d when near is 0.
+__device__ __forceinline__ bool near_light(const LightRec &L, v3 d)
+{
+  return fabsf(d.x) < L.near && fabsf(d.y) < L.near && fabsf(d.z) < L.near;
+}
+
+// A light's record read again where it is used: the far-light kernels' shading pass, so the 16 dwords are not held in
+// SGPRs across the shadow any-hit.  The pointer passes through an empty asm that also takes `when`, a wave-uniform value
+// of the current segment, so the read can neither merge with an earlier one nor leave the bounce loop.  The asm is not
+// volatile: a volatile one counts as a write to memory, after which no load of the loop is a scalar load any more.  The
+// pointer is a constant-space one, or the compiler no longer knows what it points into and reads with flat loads.
+__device__ __forceinline__ LightRec reread_light(const LightRec *l, uint64_t when)
+{
+  typedef const __attribute__((address_space(4))) LightRec *ConstLightPtr;
+  ConstLightPtr p = (ConstLightPtr)l;
+  asm("" : "+s"(p) : "s"(when));
+  return *(const LightRec *)p;
+}
+
+// FARL (with ONEL, SMALL and CULL, never STATS; RFX_FAR_LIGHT picks the halves): the scene's one light is far
+// (rfx_scene.cpp far_light_terms), so where a hit lies inside its bound the terms of the light that do not depend on the
+// hit -- dtl, its length and direction, ang > 0 and 1 - sqrt(ang) -- are read from the record, and a wave whose facing
+// hits all lie inside takes the shadow bundle's cone from it too (make_bundle_far).  Every other hit, and every other
+// instantiation, runs the expressions below as they stand.
 template <bool STATS, bool CULL, bool MANYL, bool SMALL, bool PLANES, bool PARK, class PK, bool ONEL = false,
-          bool TBVH = false>
+          bool TBVH = false, bool FARL = false>
 __device__ __forceinline__ col trace_from(const DevScene &RFX_SCENE_PARAM, v3 origin, v3 ray, col mulc, col pix, int refl,
                                           int depth, v3 rd, const float *lut, Cnt &cnt, bool valid, const PK &park,
                                           bool &parked, const uint64_t *pm_tile = nullptr, bool pm_shadow = true)
@@ -119,6 +144,9 @@ __device__ __forceinline__ col trace_from(const DevScene &RFX_SCENE_PARAM, v3 or
 #ifdef RFX_LAUNDER_SCENE
   const DevScene &S = S_in;
 #endif
+  static_assert(!FARL || (ONEL && SMALL && CULL && !MANYL && !STATS), "FARL: the small-scene one-light culling kernels");
+  constexpr bool FAR_SHADE = FARL && (RFX_FAR_LIGHT == 1 || RFX_FAR_LIGHT == 2);
+  constexpr bool FAR_CONE = FARL && (RFX_FAR_LIGHT == 1 || RFX_FAR_LIGHT == 3);
   // the first segment of a plain small-scene trace: this tile's per-view masks (prim_cull_kernel) -- the closest
   // hit's, then one per light for its shadow rays
   bool seg0 = pm_tile != nullptr;
@@ -232,7 +260,11 @@ __device__ __forceinline__ col trace_from(const DevScene &RFX_SCENE_PARAM, v3 or
                 om = pm_tile[1 + q];  // the primary hits' shadow mask for light q, precomputed for the view
               else
               {
-                const Bundle SB = make_bundle(drop, sray, facing);
+                Bundle SB;
+                bool far_cone = false;
+                if constexpr (FAR_CONE) far_cone = __ballot(facing && !near_light(L, drop)) == 0;  // wave-uniform
+                if (far_cone) SB = make_bundle_far(drop, L, facing);
+                else SB = make_bundle(drop, sray, facing);
                 if (SB.ok) om = cull_small(T.cull(), S.cull_valid, SB);
                 RFX_CULL_STAT(1, SB.ok, __ballot(facing), om, S.cull_valid);
               }
@@ -285,7 +317,45 @@ __device__ __forceinline__ col trace_from(const DevScene &RFX_SCENE_PARAM, v3 or
         {
           if (!((lit >> q) & 1u)) continue;
           RFX_CNT(C_L_LIT);
-          const LightRec L = S.lights[base + q];
+          const LightRec L = FAR_SHADE ? reread_light(S.lights + (base + q), __ballot(lit != 0)) : S.lights[base + q];
+          if constexpr (FAR_SHADE)
+          {
+            // the light's terms from its record where the hit lies inside its bound, by the expressions of the general
+            // form below where not; the rest of the shading is the general form's, operation for operation
+            v3 dtl = mk(L.ox, L.oy, L.oz), ndl = mk(L.ndx, L.ndy, L.ndz);
+            float dlen = L.dlen, spec_add = L.spec_add;
+            bool spec = true;
+            if (!near_light(L, drop))
+            {
+              dtl = sub(dtl, drop);
+              dlen = len(dtl);
+              const float a2 = sqlen(dtl);
+              const float ang = (a2 > kVerySmall) ? 1.0f - qdiv(L.radius * L.radius, a2) : 0.0f;
+              spec = ang > 0;
+              if (spec)
+              {
+                ndl = normalized(dtl);
+                spec_add = 1.0f - sqrt_rn(ang);
+              }
+            }
+            float aa = dlen * normLen;
+            const float cosl = (aa > kVerySmall) ? qdiv(dot(dtl, norm), aa) : 0.0f;
+            const col lc = mkc(L.r, L.g, L.b);
+            if (L.power > kVerySmall) sumL = cadd(sumL, cscale(cscale(lc, cosl), L.power));
+            if (spec)
+            {
+              const v3 dlr = add(ndl, mul(rd, 1.0f - m.refl));
+              aa = len(dlr) * reflectLen;
+              float sc = (aa > kVerySmall) ? qdiv(dot(dlr, reflv), aa) : 0.0f;
+              sc = clampf(sc + spec_add, 0.0f, 1.0f);
+              if (sc > kVerySmall && L.radius > kVerySmall)
+              {
+                const float sp = powf_dev(sc, 1 + qdiv(3 * m.refl * dlen, L.radius)) * m.refl;
+                sumS = cadd(sumS, cscale(lc, sp));
+              }
+            }
+            continue;
+          }
           const v3 dtl = sub(mk(L.ox, L.oy, L.oz), drop);
           const float dlen = len(dtl);
           float aa = dlen * normLen;
@@ -395,12 +465,13 @@ __device__ __forceinline__ col trace_from(const DevScene &RFX_SCENE_PARAM, v3 or
 #endif
 }
 
-template <bool STATS, bool CULL, bool MANYL, bool SMALL, bool PLANES, bool ONEL = false, bool TBVH = false>
+template <bool STATS, bool CULL, bool MANYL, bool SMALL, bool PLANES, bool ONEL = false, bool TBVH = false,
+          bool FARL = false>
 __device__ __forceinline__ col trace(const DevScene &S, v3 origin, v3 ray, int depth, v3 rd, const float *lut,
                                      Cnt &cnt, bool valid, const uint64_t *pm_tile = nullptr, bool pm_shadow = true)
 {
   bool parked;
-  return trace_from<STATS, CULL, MANYL, SMALL, PLANES, false, Park, ONEL, TBVH>(S, origin, ray, mkc(1.0f, 1.0f, 1.0f), mkc(0.0f, 0.0f, 0.0f), 0,
+  return trace_from<STATS, CULL, MANYL, SMALL, PLANES, false, Park, ONEL, TBVH, FARL>(S, origin, ray, mkc(1.0f, 1.0f, 1.0f), mkc(0.0f, 0.0f, 0.0f), 0,
                                                        depth, rd, lut, cnt, valid, Park{0, nullptr, nullptr, 0, 0},
                                                        parked, pm_tile, pm_shadow);
 }

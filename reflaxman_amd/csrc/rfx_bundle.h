@@ -118,6 +118,29 @@ __device__ __forceinline__ Bundle make_bundle_ball(v3 o, v3 d, float R, bool liv
   return B;
 }
 
+// Bundle of the shadow rays (o, L + rd R), |rd| <= 1, of the `live` lanes toward a far light (rfx_types.h LightRec,
+// near > 0; every live lane's o inside the light's bound, so its direction is L + rd R with the light's own origin L):
+// origin and rw as make_bundle finds them, the cone a constant of the light -- its axis normalized(L), its half-angle
+// the ball's angular radius asin(R / |L|), widened on the host as make_bundle_ball widens its own (which also covers
+// the rounding of L + rd R, a relative 2^-23 of |L|).  The cone make_bundle would find has the first live lane's ray as
+// its axis, so its half-angle reaches twice this one's.
+__device__ __forceinline__ Bundle make_bundle_far(v3 o, const LightRec &L, bool live)
+{
+  Bundle B;
+  const int ref = __ffsll((long long)__ballot(live)) - 1;
+  B.cx = lane_bcast(o.x, ref); B.cy = lane_bcast(o.y, ref); B.cz = lane_bcast(o.z, ref);
+  B.ax = L.ndx; B.ay = L.ndy; B.az = L.ndz;
+  const float ex = o.x - B.cx, ey = o.y - B.cy, ez = o.z - B.cz;
+  const float e2 = cdot(ex, ey, ez, ex, ey, ez);
+  const bool bad = live && !(e2 <= 1.0e30f);
+  const float e2m = wave_max_nonneg(live ? e2 : 0.0f);
+  B.rw = __builtin_amdgcn_sqrtf(e2m) * 1.0001f;
+  B.cosa = L.cone_cos;
+  B.sina = L.cone_sin;
+  B.ok = __ballot(bad) == 0 && B.rw <= 1.0e15f;
+  return B;
+}
+
 // Bundle of every ray from o with a direction in the quadrilateral d[0..3] of each `live` lane (the sample rays of an SSAA
 // pixel: the directions are a linear image of the pixel's sample rectangle, and the cone is convex, so a cone
 // holding the four corners holds every ray between them).  For the per-view masks of SSAA frames (prim_cull_kernel).

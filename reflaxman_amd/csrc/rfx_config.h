@@ -44,6 +44,9 @@
 #ifndef RFX_TRI_MATES
 #define RFX_TRI_MATES 2  // coplanar mates share the z stage: 0 never, 1 both small-scene loops, 3 shadow loop only (DESIGN.md "Exact work skipping", coplanar mates)
 #endif
+#ifndef RFX_FAR_LIGHT
+#define RFX_FAR_LIGHT 1  // a far light's constant terms from its record: 0 never, 2 the shading terms only, 3 the shadow cone only (DESIGN.md "Far lights")
+#endif
 #ifndef RFX_CULL_FMA
 #define RFX_CULL_FMA 1  // 0: the bundle and cull bounds without fused multiply-adds (DESIGN.md "Large scenes", fused cull bounds)
 #endif

@@ -64,6 +64,13 @@ extern "C" int rfx_kat_powf(rfx_renderer *r, const float *xy, uint64_t n, float 
   return kat_run(r, 2, 0, xy, (size_t)n * 2, nullptr, n, out, (size_t)n);
 }
 
+extern "C" int rfx_kat_far_light(rfx_renderer *r, const float *points, uint64_t n, float *out)
+{
+  if (!r || (n && (!points || !out))) return fail(RFX_ERR_ARG, "kat_far_light: bad args");
+  if (!r->has_scene || r->dev.n_light < 1) return fail(RFX_ERR_STATE, "kat_far_light: no scene with a light uploaded");
+  return kat_run(r, 4, 0, points, (size_t)n * 3, nullptr, n, out, (size_t)n * 8);
+}
+
 extern "C" int rfx_kat_argb(rfx_renderer *r, const float *rgb, uint64_t n, uint32_t *out)
 {
   if (!r || (n && (!rgb || !out))) return fail(RFX_ERR_ARG, "kat_argb: bad args");

@@ -1092,6 +1092,33 @@ __global__ __launch_bounds__(kKatThreads) void kat_powf(const float *xy, uint32_
   }
 }
 
+// The bounce loop's far-light form against its general form (rfx_bounce.h FARL), for the scene's first light and n
+// points d: out[8 i ..] = the general expressions' dtl, len(dtl), normalized(dtl) and 1 - sqrt_rn(ang) (0 unless ang >
+// 0) at d_i; where d_i lies inside the light's bound (near_light) and the record's terms differ from them in any bit, or
+// ang > 0 does not hold, the eight are NaN.
+__global__ __launch_bounds__(kKatThreads) void kat_far_light(DevScene S, const float *d, uint32_t n, float *out)
+{
+  const uint32_t i = blockIdx.x * kKatThreads + threadIdx.x;
+  if (i >= n) return;
+  const LightRec L = S.lights[0];
+  const v3 drop = mk(d[3 * (size_t)i], d[3 * (size_t)i + 1], d[3 * (size_t)i + 2]);
+  const v3 dtl = sub(mk(L.ox, L.oy, L.oz), drop);
+  const float dlen = len(dtl), aa = sqlen(dtl);
+  const float ang = (aa > kVerySmall) ? 1.0f - qdiv(L.radius * L.radius, aa) : 0.0f;
+  const v3 nd = normalized(dtl);
+  const float spec_add = ang > 0 ? 1.0f - sqrt_rn(ang) : 0.0f;
+  float v[8] = {dtl.x, dtl.y, dtl.z, dlen, nd.x, nd.y, nd.z, spec_add};
+  if (near_light(L, drop))
+  {
+    const float w[8] = {L.ox, L.oy, L.oz, L.dlen, L.ndx, L.ndy, L.ndz, L.spec_add};
+    bool same = ang > 0 && L.radius > kVerySmall;
+    for (int k = 0; k < 8; ++k) same = same && __float_as_uint(v[k]) == __float_as_uint(w[k]);
+    if (!same)
+      for (int k = 0; k < 8; ++k) v[k] = __builtin_nanf("");
+  }
+  for (int k = 0; k < 8; ++k) out[8 * (size_t)i + k] = v[k];
+}
+
 // powf3_dev(x) against powf_dev(x, 3) for the float bit patterns first .. first + n - 1 (every float in [0, 1] is
 // 0 .. 0x3f800000): counts[0] += mismatches, counts[1] += lanes that took glibc's algorithm
 __global__ __launch_bounds__(kKatThreads) void kat_powf_cube(uint32_t first, uint32_t n, unsigned long long *counts)
@@ -1445,6 +1472,7 @@ hipError_t launch_kat(int what, const DevScene &S, int tex, const void *in, cons
     case 0: hipLaunchKernelGGL(kat_objects, kat_grid(n), dim3(kKatThreads), 0, st, S, (const float *)in, objs, n, (float *)out); break;
     case 1: hipLaunchKernelGGL(kat_texels, kat_grid(n), dim3(kKatThreads), 0, st, S, tex, (const float *)in, n, (float *)out); break;
     case 2: hipLaunchKernelGGL(kat_powf, kat_grid(n), dim3(kKatThreads), 0, st, (const float *)in, n, (float *)out); break;
+    case 4: hipLaunchKernelGGL(kat_far_light, kat_grid(n), dim3(kKatThreads), 0, st, S, (const float *)in, n, (float *)out); break;
     default: hipLaunchKernelGGL(kat_argb, kat_grid(n), dim3(kKatThreads), 0, st, (const float *)in, n, (uint32_t *)out); break;
   }
   return hipGetLastError();
@@ -1538,10 +1566,14 @@ hipError_t launch_trace(const DevScene &S, const FrameParams &P, bool stats, hip
   // tile -- skip the bundle cull, trading tests for the cull's serial latency
   const bool cull = !stats && !(RFX_NOCULL_MAX_TILES > 0 && S.n_sph <= 32 && S.n_tri <= 32 &&
                                 trace_tiles(P) <= (uint32_t)RFX_NOCULL_MAX_TILES);
-  const int cfg = (S.n_light > 32 ? kCfgManyLights : 0) | (cull ? kCfgCull : 0) |
-                  (S.n_sph <= 32 && S.n_tri <= 32 ? kCfgSmall : 0) | (S.n_pln > 0 ? kCfgPlanes : 0) |
-                  (S.n_light == 1 && !stats && RFX_ONE_LIGHT ? kCfgOneLight : 0) |
-                  (RFX_TRI_BVH && S.tri_bvh != nullptr && !stats ? kCfgTriBvh : 0);
+  int cfg = (S.n_light > 32 ? kCfgManyLights : 0) | (cull ? kCfgCull : 0) |
+            (S.n_sph <= 32 && S.n_tri <= 32 ? kCfgSmall : 0) | (S.n_pln > 0 ? kCfgPlanes : 0) |
+            (S.n_light == 1 && !stats && RFX_ONE_LIGHT ? kCfgOneLight : 0) |
+            (RFX_TRI_BVH && S.tri_bvh != nullptr && !stats ? kCfgTriBvh : 0);
+  // a small scene whose one light is far (DevScene::far_light, the host's rule): the families that carry the kernels
+  const bool far_mode = mode == kModePlain || mode == kModeSsaaLanes || mode == kModeSsaaChunks;
+  if (RFX_FAR_LIGHT && S.far_light && far_mode && (cfg & ~kCfgPlanes) == (kCfgCull | kCfgSmall | kCfgOneLight))
+    cfg |= kCfgFarLight;
   launch_mode_cfg(stats, mode, cfg, grid, S, Pt, st);
   return hipGetLastError();
 }

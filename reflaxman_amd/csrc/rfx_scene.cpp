@@ -62,6 +62,7 @@ struct rfx_scene {
   float half_tile_w, half_tile_h;
   int skybox = -1;
   int tri_mates = 1;  // rfx_scene_set_tri_mates
+  int far_lights = 1;  // rfx_scene_set_far_lights
   std::vector<HostSphere> spheres;
   std::vector<HostTri> tris;
   std::vector<HostPlane> planes;
@@ -736,6 +737,88 @@ extern "C" int rfx_scene_tri_mates(const rfx_scene *s, int32_t *leader, float *p
   return (int)l.size();
 }
 
+// ============================================================== far lights
+// Scene::trace (Scene.cpp:117-181) forms dirToLight = light.origin - drop at every hit.  For a light L far from the
+// scene that difference is L itself in float32: with s_i the spacing of floats just below |L_i| (half the spacing above
+// it when |L_i| is a power of two), |d_i| < s_i / 2 puts L_i - d_i strictly nearer to L_i than to either neighbour, so
+// it rounds to L_i -- the compare must be strict, at |d_i| = s_i / 2 the tie may round away.  near = min_i s_i / 2.
+// With dtl == L every term of the light's shading that does not read the hit is a constant of the light: len(dtl),
+// sqlen(dtl), ang = 1 - r^2 / sqlen, normalized(dtl), 1 - sqrt(ang).  They are computed here by rfx_math.h's own
+// functions, whose host forms are the correctly rounded '/' and sqrtf the device forms reproduce bit for bit.
+// A light is far when every field is finite, near > 0 (so no coordinate is zero: admitting such a light per axis would
+// be sound, it is left out), sqlen(L) is finite and above kVerySmall, ang > 0, radius > kVerySmall -- the branches of
+// the general form the kernel then takes without testing -- and radius / |L| * 1.001 < 0.5 as rfx_bundle.h
+// make_bundle_ball asks of its direction ball.  The shadow rays' directions L + rd radius, |rd| <= 1, then lie in the
+// cone of half-angle asin(radius / |L|) about normalized(L); cone_cos / cone_sin are that cone widened exactly as
+// make_bundle_ball widens its own (ca = 1, sa = 0: the axis is the ball's centre).
+// Returns the record with near > 0 for a far light, with the eight new fields 0 otherwise.
+static LightRec far_light_terms(const HostLight &l)
+{
+  LightRec rec{l.origin.x, l.origin.y, l.origin.z, l.radius, l.r, l.g, l.b, l.power, 0, 0, 0, 0, 0, 0, 0, 0};
+  const float c[3] = {l.origin.x, l.origin.y, l.origin.z};
+  float near = INFINITY;
+  for (int a = 0; a < 3; ++a)
+  {
+    if (!std::isfinite(c[a])) return rec;
+    const float m = fabsf(c[a]);
+    near = fminf(near, (m - nextafterf(m, 0.0f)) / 2);
+  }
+  if (!std::isfinite(l.radius) || !(near > 0.0f)) return rec;
+  const v3 dtl = l.origin;
+  const float aa = sqlen(dtl);
+  if (!std::isfinite(aa) || !(aa > kVerySmall)) return rec;
+  const float ang = 1.0f - qdiv(l.radius * l.radius, aa);
+  if (!(ang > 0) || !(l.radius > kVerySmall)) return rec;
+  const float dlen = len(dtl);
+  const float sb = fminf(l.radius / dlen * 1.001f, 1.0f);
+  if (!(sb < 0.5f)) return rec;
+  const v3 nd = normalized(dtl);
+  const float cb = sqrtf(fmaxf(1.0f - sb * sb, 0.0f));
+  const float dev = fmaxf(1.0f - cb, 0.0f);
+  rec.dlen = dlen;
+  rec.ndx = nd.x; rec.ndy = nd.y; rec.ndz = nd.z;
+  rec.spec_add = 1.0f - sqrt_rn(ang);
+  rec.near = near;
+  rec.cone_cos = 1.0f - dev - 4e-6f;
+  rec.cone_sin = sqrtf(fmaxf(1.0f - rec.cone_cos * rec.cone_cos, 0.0f) + 1e-7f) * 1.001f;
+  return rec;
+}
+
+// Whether the launches of this scene may take the far-light kernels (rfx_scene_set_far_lights): exactly one light, far,
+// and under mode 1 every sphere (its box) and every triangle vertex inside |coordinate| < near.  The kernels guard every
+// hit by the same bound, so the extent decides only whether they pay: a plane, a far eye or a rounding may still put a
+// hit outside, and it then takes the general expressions.
+static bool far_light_scene(const rfx_scene &s, const LightRec &rec)
+{
+  if (s.far_lights == 0 || s.lights.size() != 1 || !(rec.near > 0.0f)) return false;
+  if (s.far_lights == 2) return true;
+  const auto inside = [&](float v) { return fabsf(v) < rec.near; };  // false for a NaN
+  for (const HostSphere &h : s.spheres)
+    for (float v : {h.center.x - h.radius, h.center.x + h.radius, h.center.y - h.radius, h.center.y + h.radius,
+                    h.center.z - h.radius, h.center.z + h.radius})
+      if (!inside(v)) return false;
+  for (const HostTri &t : s.tris)
+    for (const v3 *v : {&t.v0, &t.v1, &t.v2})
+      if (!inside(v->x) || !inside(v->y) || !inside(v->z)) return false;
+  return true;
+}
+
+extern "C" int rfx_scene_set_far_lights(rfx_scene *s, int mode)
+{
+  if (!s || mode < 0 || mode > 2) return fail(RFX_ERR_ARG, "scene_set_far_lights: 0 (off), 1 (auto) or 2 (any extent)");
+  s->far_lights = mode;
+  return RFX_OK;
+}
+
+extern "C" int rfx_scene_far_light(const rfx_scene *s, int light, float terms[8])
+{
+  if (!s || light < 0 || light >= (int)s->lights.size()) return fail(RFX_ERR_ARG, "scene_far_light: no light %d", light);
+  const LightRec rec = far_light_terms(s->lights[light]);
+  if (terms)
+    for (float f : {rec.dlen, rec.ndx, rec.ndy, rec.ndz, rec.spec_add, rec.near, rec.cone_cos, rec.cone_sin}) *terms++ = f;
+  return far_light_scene(*s, rec) ? 1 : 0;
+}
+
 // ============================================================== the device form of a scene
 // The coherent order's key box (rfx.h "Coherent order"): float32 throughout, objects in insertion order, a NaN never
 // taken; planes are unbounded and do not count
@@ -1004,7 +1087,8 @@ SceneBuild::SceneBuild(const rfx_scene &scene, int tri_accel)
       loc[o] = kind << 28 | (kind == 0 ? sph_dev[idx] : idx);
     }
   }
-  for (const HostLight &l : s->lights) lr.push_back({l.origin.x, l.origin.y, l.origin.z, l.radius, l.r, l.g, l.b, l.power});
+  for (const HostLight &l : s->lights) lr.push_back(far_light_terms(l));
+  d.far_light = !lr.empty() && far_light_scene(*s, lr[0]);
   for (const HostTexture &t : s->textures)
   {
     const bool empty = t.texels.empty();  // the reference's empty colorBuf: checker (Texture.cpp:242-243)

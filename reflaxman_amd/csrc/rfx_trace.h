@@ -183,6 +183,8 @@ __host__ __device__ constexpr uint32_t ss_lane_block(int ss)
 // for the bounce kernel (ray regrouping; rfx_trace_plain_park.hip).  The values: rfx_types.h.
 // kCfgTriBvh -- a non-small scene with a triangle BVH (rfx_types.h RFX_TRI_BVH): its culling configurations carry the
 // triangle walkers; every other scene runs kernels without them (with them C5 traced 3.0% slower)
+// kCfgFarLight -- a small scene whose one light is far (rfx_scene.cpp far_light_terms, rfx_bounce.h FARL): plain,
+// lanes and chunks frames of the culling configurations 5 and 13 with kCfgOneLight, and the parking form of the first
 
 // one workgroup = kTileW x kTileH output pixels (block mode: block corners), one wave = an 8x8 tile (ray coherence).
 // Every lane of a wave reaches trace() -- lanes outside the frame or the cursor span as invalid -- so the
@@ -199,6 +201,8 @@ __global__ __launch_bounds__(kWgThreads) __attribute__((amdgpu_waves_per_eu(
   constexpr bool PLANES = (CFG & kCfgPlanes) != 0, PARK = MODE == kModePlain && !STATS && (CFG & kCfgPark) != 0;
   constexpr bool ONEL = (CFG & kCfgOneLight) != 0;  // exactly one light: the light loops unrolled
   constexpr bool TBVH = (CFG & kCfgTriBvh) != 0;    // the scene has a triangle BVH
+  constexpr bool FARL = (CFG & kCfgFarLight) != 0;  // the one light is far: its constant terms come from its record
+  static_assert(!FARL || (MODE == kModePlain || MODE == kModeSsaaLanes || MODE == kModeSsaaChunks), "far-light modes");
   RFX_WAVE_T0();
   __shared__ float lut[256];
   for (uint32_t i = threadIdx.x; i < 256; i += kWgThreads) lut[i] = (float)i / 255.0f;  // Color.cpp:11-13
@@ -279,8 +283,8 @@ __global__ __launch_bounds__(kWgThreads) __attribute__((amdgpu_waves_per_eu(
       // the tile's per-view masks (prim_cull_kernel<., true>; chunks: the pixel's closest-hit mask, every chunk)
       const uint64_t *pm = RFX_PRIM_LANES && SMALL && CULL && !STATS && P.prim_mask
                                ? P.prim_mask + (size_t)kPrimStride * t8 : nullptr;
-      const col c = trace<STATS, CULL, MANYL, SMALL, PLANES, ONEL, TBVH>(S, eye, ray, P.depth, rd, lut, cnt, valid, pm,
-                                                                  P.prim_shadow != 0);
+      const col c = trace<STATS, CULL, MANYL, SMALL, PLANES, ONEL, TBVH, FARL>(S, eye, ray, P.depth, rd, lut, cnt, valid, pm,
+                                                                        P.prim_shadow != 0);
       {
 #ifdef RFX_LAUNDER_PARAMS
         const FrameParams &P = kernarg_params();  // shadows the by-value parameter: re-read after the bounce loop
@@ -412,9 +416,8 @@ __global__ __launch_bounds__(kWgThreads) __attribute__((amdgpu_waves_per_eu(
       if (valid) rd = load_rd(P, pr);
       const ParkTile park{P.park_after, P.queue, P.queue_count, P, wv, w8};
       const uint64_t *pm_tile = SMALL && CULL && !STATS && P.prim_mask ? P.prim_mask + (size_t)kPrimStride * t8 : nullptr;
-      const col c = trace_from<STATS, CULL, MANYL, SMALL, PLANES, PARK, ParkTile, ONEL, TBVH>(S, eye, ray, mkc(1.0f, 1.0f, 1.0f),
-                                                                  mkc(0.0f, 0.0f, 0.0f), 0, P.depth, rd, lut, cnt,
-                                                                  valid, park, parked, pm_tile);
+      const col c = trace_from<STATS, CULL, MANYL, SMALL, PLANES, PARK, ParkTile, ONEL, TBVH, FARL>(
+          S, eye, ray, mkc(1.0f, 1.0f, 1.0f), mkc(0.0f, 0.0f, 0.0f), 0, P.depth, rd, lut, cnt, valid, park, parked, pm_tile);
       out = cadd(mkc(0.0f, 0.0f, 0.0f), c);                                      // Render.cpp:185 (/ 1.0f exact)
     }
     else
@@ -513,6 +516,16 @@ inline void launch_cfg(int cfg, dim3 grid, const DevScene &S, const FrameParams 
     cfg &= ~kCfgTriBvh;
   }
 #endif
+  if (cfg & kCfgFarLight)  // a far light (rfx_kernels.hip launch_trace sets the bit for these modes and configurations only)
+  {
+    if constexpr (!STATS && RFX_FAR_LIGHT && (MODE == kModePlain || MODE == kModeSsaaLanes || MODE == kModeSsaaChunks))
+      switch (cfg & ~kCfgFarLight)
+      {
+        case 5 | kCfgOneLight: launch_one<STATS, MODE, 5 | kCfgOneLight | kCfgFarLight>(grid, S, P, st); return;
+        case 13 | kCfgOneLight: launch_one<STATS, MODE, 13 | kCfgOneLight | kCfgFarLight>(grid, S, P, st); return;
+      }
+    cfg &= ~kCfgFarLight;
+  }
   if (cfg & kCfgOneLight)  // scenes with exactly one light: the culling configurations have unrolled light loops
   {
     switch (cfg & ~kCfgOneLight)

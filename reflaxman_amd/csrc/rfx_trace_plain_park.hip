@@ -18,7 +18,11 @@ static void launch_park_one(dim3 grid, const DevScene &S, const FrameParams &P, 
 
 void launch_trace_plain_park(int cfg, dim3 grid, const DevScene &S, const FrameParams &P, hipStream_t st)
 {
-  switch (cfg & ~kCfgPark)
+#if RFX_FAR_LIGHT
+  if ((cfg & ~kCfgPark) == (5 | kCfgOneLight | kCfgFarLight))  // a small scene whose one light is far
+    return launch_park_one<5 | kCfgOneLight | kCfgFarLight>(grid, S, P, st);
+#endif
+  switch (cfg & ~(kCfgPark | kCfgFarLight))  // every other far-light configuration: the kernels without the bit
   {
 #if RFX_TRI_BVH
     case 1 | kCfgTriBvh: launch_park_one<1 | kCfgTriBvh>(grid, S, P, st); break;
@@ -39,7 +43,7 @@ void launch_trace_plain_park(int cfg, dim3 grid, const DevScene &S, const FrameP
     case 13: launch_park_one<13>(grid, S, P, st); break;
     case 15: launch_park_one<15>(grid, S, P, st); break;
     default:  // one light, other configurations: the general kernels
-      if (cfg & kCfgOneLight) launch_trace_plain_park(cfg & ~kCfgOneLight, grid, S, P, st);
+      if (cfg & kCfgOneLight) launch_trace_plain_park(cfg & ~(kCfgOneLight | kCfgFarLight), grid, S, P, st);
       break;
   }
 }

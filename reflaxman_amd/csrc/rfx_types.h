@@ -77,7 +77,15 @@ struct alignas(16) BvhNode { float lx[2], ly[2], lz[2], hx[2], hy[2], hz[2]; int
 // removes the walkers from the kernels.
 // Plane(pos, norm, material) (Plane.h:6-14): the normal as given (the reference never normalises it)
 struct alignas(16) PlaneGeo { float px, py, pz, nx, ny, nz; int32_t obj, dielectric; };
-struct alignas(16) LightRec { float ox, oy, oz, radius, r, g, b, power; }; // OmniLight.h
+// OmniLight.h, and the terms of Scene::trace that are constants of a far light (rfx_scene.cpp far_light_terms): near > 0
+// says that for every point d with max |d_i| < near the float difference origin - d is origin, bit for bit; then
+// len(origin - d) is dlen, normalized(origin - d) is (ndx, ndy, ndz), 1 - sqrt_rn(ang) is spec_add with ang > 0, and
+// every direction origin + rd radius, |rd| <= 1, lies in the cone of half-angle acos(cone_cos) about (ndx, ndy, ndz).
+// near == 0: not a far light, the other seven are 0.
+struct alignas(16) LightRec {
+  float ox, oy, oz, radius, r, g, b, power;
+  float dlen, ndx, ndy, ndz, spec_add, near, cone_cos, cone_sin;
+};
 struct alignas(16) TexRec { uint32_t offset, w, h, pad; };
 
 struct DevScene {
@@ -120,6 +128,7 @@ struct DevScene {
   int32_t n_tri_bvh;          // nodes of the triangle BVH
   int32_t tri_bvh_depth;      // its internal levels (<= kBvhStack)
   int32_t tri_bvh_narrow;     // narrow bundles (a tile's primary rays) walk the tree too (else: the bundle-culled chunks)
+  int32_t far_light;          // host only: the launches may take the far-light kernels (rfx_scene_set_far_lights)
 };
 
 // The bounce kernel with the BVH staged in LDS (rfx_parked.h bounce_kernel_lds): one workgroup of kLdsBvhWaves waves
@@ -201,5 +210,6 @@ constexpr int kPrimLights = 4, kPrimStride = 1 + kPrimLights;
 // the trace and bounce kernels' CFG template bits (rfx_trace.h trace_kernel), chosen per launch by the host
 constexpr int kCfgCull = 1, kCfgManyLights = 2, kCfgSmall = 4, kCfgPlanes = 8, kCfgPark = 16, kCfgOneLight = 32;
 constexpr int kCfgTriBvh = 64;
+constexpr int kCfgFarLight = 128;  // with kCfgOneLight | kCfgSmall | kCfgCull only: the one light's constant terms from its record
 
 }  // namespace rfx

@@ -204,6 +204,19 @@ class Scene:
         check(L.rfx_scene_tri_mates(self._h, leader.ctypes.data_as(_lib._i32p), _lib.fptr(rows)), "Scene.tri_mates")
         return (leader, rows) if plane else leader
 
+    def set_far_lights(self, mode: int):
+        """Far-light kernels (rfx.h rfx_scene_set_far_lights): 0 never, 1 automatic (the default), 2 for any one-light
+        scene whose light is far.  No pixel changes; read by the next upload of the scene."""
+        check(_lib.load().rfx_scene_set_far_lights(self._h, int(mode)), "Scene.set_far_lights")
+        self._version += 1
+
+    def far_light(self, light: int = 0):
+        """(chosen, terms): whether this scene's launches take the far-light kernels, and light `light`'s record terms
+        as float32 [dlen, ndx, ndy, ndz, spec_add, near, cone_cos, cone_sin] (rfx.h rfx_scene_far_light; host only)."""
+        terms = np.zeros(8, np.float32)
+        chosen = check(_lib.load().rfx_scene_far_light(self._h, int(light), _lib.fptr(terms)), "Scene.far_light")
+        return bool(chosen), terms
+
     def addPlane(self, pos: Vector3, norm: Vector3, material: Material) -> Plane:
         """Plane(pos, norm, material) (Plane.cpp:9-14) as a scene object, traced by Plane::trace (Plane.cpp:36-73)."""
         obj = check(_lib.load().rfx_scene_add_plane(self._h, farr(Vector3(*pos)), farr(Vector3(*norm)), material.type,
@@ -859,6 +872,14 @@ class Renderer:
         xy = np.ascontiguousarray(xy, np.float32)
         out = np.zeros(xy.shape[0], np.float32)
         check(_lib.load().rfx_kat_powf(self._h, _lib.fptr(xy), xy.shape[0], _lib.fptr(out)), "rfx_kat_powf")
+        return out
+
+    def kat_far_light(self, points: np.ndarray) -> np.ndarray:
+        """(n, 8) float32: the general form's light terms at each point, NaN rows where the far form differs
+        (rfx.h rfx_kat_far_light)."""
+        pts = np.ascontiguousarray(points, np.float32).reshape(-1, 3)
+        out = np.zeros((pts.shape[0], 8), np.float32)
+        check(_lib.load().rfx_kat_far_light(self._h, _lib.fptr(pts), pts.shape[0], _lib.fptr(out)), "rfx_kat_far_light")
         return out
 
     def kat_powf_cube(self):

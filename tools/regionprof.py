@@ -35,11 +35,13 @@ def main():
                     help="rfx_renderer_set_prim_exact setting (0: the conservative per-view masks)")
     ap.add_argument("--mates", type=int, default=None,
                     help="rfx_scene_set_tri_mates setting (0: every triangle its own mate group)")
+    ap.add_argument("--far", type=int, default=None,
+                    help="rfx_scene_set_far_lights setting (0: the general kernels)")
     a = ap.parse_args()
     path = os.path.join(_build.LIBDIR, "diag", a.lib)
     scene = a.scene
     r = ab.Runner("prof", path, scenes.get_scene(scene), a.width, a.height, a.depth, 1350490027, regroup=a.regroup,
-                  prim=a.prim, exact=a.exact, mates=a.mates)
+                  prim=a.prim, exact=a.exact, mates=a.mates, far=a.far)
     r.render(2)
     assert r.L.rfx_synchronize(r.r) == 0
     buf = (C.c_ulonglong * 16)()

@@ -10,7 +10,7 @@ trace_rays<STATS,CFG> (rfx_trace_rays.hip) / query_hits<CFG>, query_occluded<CFG
 trace_rays_ordered<CFG>, query_hits_ordered<CFG>, query_occluded_ordered<CFG> (rfx_trace_ordered.hip) /
 query_hits_span<CFG>, query_occluded_span<CFG> and their _ordered forms (rfx_trace_span.hip) / order_keys,
 order_hist, order_scan, order_scatter (the coherent order's sort, rfx_order_sort.hip); CFG bits (rfx_types.h kCfg*):
-1 cull, 2 >32 lights, 4 small scene, 8 planes, 16 park, 32 one light, 64 triangle BVH.
+1 cull, 2 >32 lights, 4 small scene, 8 planes, 16 park, 32 one light, 64 triangle BVH, 128 far light.
 """
 from __future__ import annotations
 
