@@ -515,6 +515,69 @@ int rfx_query_hits_ordered(rfx_renderer *r, const float *d_rays, const uint32_t 
 int rfx_query_occluded_ordered(rfx_renderer *r, const float *d_rays, const int32_t *d_skip, const uint32_t *d_order,
                                uint64_t n, uint8_t *d_occluded, void *stream);
 
+/*
+ * Paths: Scene::trace (Scene.cpp:73-236) as a state per ray that the caller holds on the device and steps by segment.
+ * rfx_trace_rays fixes the depth at the call and keeps everything between the first ray and the final colour to
+ * itself; here the variables Scene::trace carries from one loop iteration to the next lie in planes of the caller's,
+ * and a step runs the loop's body on them -- bit for bit the operations of the one-shot call, so after k segments a
+ * path's colour is Scene::trace(origin, ray, k).  A caller renders to one depth and continues to another without
+ * tracing again, drops ended paths and regroups the live ones between segments (rfx_paths_order), brings its own
+ * randDir per path, or edits rays and mulColor between segments.  Added under RFX_ABI_VERSION 5 without raising it:
+ * detect by symbol (dlsym).  There are no host forms (rfx_device_alloc and rfx_memcpy_* serve C callers) and no
+ * counters form.
+ */
+typedef struct {            /* device planes of n paths; every plane indexed by the path index i */
+  float       *d_rays;      /* 6 n : the next segment's origin and ray -- rfx_trace_rays' record, used as given */
+  float       *d_mul;       /* 3 n : mulColor   (Scene.cpp:76) */
+  float       *d_colour;    /* 3 n : pixelColor (Scene.cpp:77): after k segments it is Scene::trace(.., k) */
+  float       *d_rand;      /* 3 n : randDir    (Scene.cpp:75); only rfx_paths_begin writes it */
+  int32_t     *d_state;     /* n   : s >= 0: live, s segments run; s < 0: ended, ~s segments run (>= 1) */
+  uint32_t    *d_argb;      /* n, or NULL : Color::argb of d_colour, written wherever d_colour is */
+} rfx_paths;
+/*
+ * The start state of the n paths whose d_rays the caller has filled: mul = 1, colour = 0, state = 0, argb where given.
+ * draw != 0: d_rand[i] becomes the i-th randomInsideSphere draw from the renderer's current sphere-stream state -- the
+ * three floats the batch kernels take for ray i -- and the stream then stands n accepted triples on, exactly as after
+ * rfx_trace_rays of n rays (the same pre-pass, the same splitting above the launch limit).  draw == 0: d_rand and both
+ * streams are left alone (the caller's own sampler; zero vectors give the noise-free image).
+ * Errors: those of rfx_trace_rays (NULL renderer or p, a NULL required plane, n == 0: RFX_ERR_ARG; no scene:
+ * RFX_ERR_STATE); an emitted frame pending is RFX_ERR_STATE only when draw != 0.
+ */
+int rfx_paths_begin(rfx_renderer *r, const rfx_paths *p, uint64_t n, int draw, void *stream);
+/*
+ * One step.  Wave w takes slots 64 w .. 64 w + 63, and slot s works on path i = d_index ? d_index[s] : s; a slot with
+ * i >= n is a dead lane that reads and writes nothing (the ordered calls' rule).  For a named path with
+ * st = d_state[i]:
+ *   st < 0 or st >= upto : no word of the path is written.
+ *   otherwise            : the body of Scene::trace's loop (Scene.cpp:80-234) runs on the path's variables, refl = st,
+ *                          until refl == upto or the loop is left by one of its breaks (the sky, 228-233; the mulColor
+ *                          cut-off, 220-222).  d_colour[i] (and d_argb[i]) are written either way.  Left by a break:
+ *                          d_state[i] = ~(segments run), and the path's d_rays and d_mul words are unspecified from then
+ *                          on (the library never reads them again).  Else d_state[i] = upto, d_rays[i] = the (origin,
+ *                          ray) of Scene.cpp:225-226 and d_mul[i] = mulColor.
+ * d_live (capacity `slots`, must not alias d_index) receives the index of every named path that is live (state >= 0)
+ * after the call, whether or not it ran, and d_live_count[0] is set by the call to their number (d_live NULL: the count
+ * alone).  Their order in d_live is a schedule, not a value: it may differ from run to run.  An index named twice in
+ * one call is the caller's error: that path's words are unspecified, and nothing out of bounds is touched.  `slots`
+ * above the launch limit run as consecutive slot ranges over the whole arrays, the count running on.  Stream-ordered,
+ * no host sync.  The call touches no random stream, mask, tile cost, timing sum or rewind state (the queries' rule).
+ * Errors: NULL renderer or p, any of the five required planes NULL, slots == 0, n == 0 or n >= 2^32, upto < 1 or
+ * upto == INT32_MAX, d_live without d_live_count: RFX_ERR_ARG; no scene uploaded: RFX_ERR_STATE.
+ */
+int rfx_paths_step(rfx_renderer *r, const rfx_paths *p, uint64_t n, const uint32_t *d_index /* or NULL */,
+                   uint64_t slots, int32_t upto, uint32_t *d_live /* or NULL */, uint32_t *d_live_count /* or NULL */,
+                   void *stream);
+/*
+ * d_order[0 .. slots) becomes the entries of d_index (NULL: 0 .. slots - 1), stably sorted by the "Coherent order" key
+ * of each path's current d_rays record; an entry >= n takes key 0xFFFFFFFF, so it sorts last and is kept.  With
+ * d_index NULL and slots == n the result is rfx_rays_order(p->d_rays, n) word for word.  d_order may be d_index.  The
+ * renderer's sort scratch and rfx_rays_order's rules for it apply; like it, the call touches nothing else.
+ * Errors: NULL renderer, p, d_rays or d_order, n == 0 or n >= 2^32, slots == 0 or slots >= 2^31: RFX_ERR_ARG; no scene:
+ * RFX_ERR_STATE.
+ */
+int rfx_paths_order(rfx_renderer *r, const rfx_paths *p, uint64_t n, const uint32_t *d_index /* or NULL */,
+                    uint64_t slots, uint32_t *d_order, void *stream);
+
 /* ---------------------------------------------------------------- Device groups (multi-GPU, one process)
  * A group renders the frame of Render::renderNext (Render.cpp:136-215) on several devices of this process: row bands,
  * one per member, each member counting its slice of the frame's random stream and pushing it to the others (the one

@@ -56,6 +56,25 @@ class RaySpan(C.Structure):
     _fields_ = [(n, C.c_void_p) for n in ("d_lo", "d_after", "d_hi")]
 
 
+class PathPlanes(C.Structure):
+    """rfx_paths (include/rfx.h "Paths"): the device planes of n paths, one pointer each; d_argb may be 0."""
+    _fields_ = [(n, C.c_void_p) for n in ("d_rays", "d_mul", "d_colour", "d_rand", "d_state", "d_argb")]
+
+
+def path_segments(state):
+    """Segments run by a path (or an array of them) of rfx_paths' state word s: s itself while live (s >= 0), ~s once
+    ended (s < 0)."""
+    import numpy as np
+    s = np.asarray(state)
+    return np.where(s < 0, ~s, s)
+
+
+def path_ended_state(segments):
+    """The state word of a path that ended after `segments` segments (>= 1): ~segments."""
+    import numpy as np
+    return ~np.asarray(segments)
+
+
 _i32p = C.POINTER(C.c_int32)
 
 # (name, restype, argtypes) for every symbol of include/rfx.h
@@ -139,6 +158,11 @@ SIGNATURES = [
                                          C.c_void_p]),
     ("rfx_query_occluded_ordered", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p,
                                              C.c_void_p]),
+    ("rfx_paths_begin", C.c_int, [C.c_void_p, C.POINTER(PathPlanes), C.c_uint64, C.c_int, C.c_void_p]),
+    ("rfx_paths_step", C.c_int, [C.c_void_p, C.POINTER(PathPlanes), C.c_uint64, C.c_void_p, C.c_uint64, C.c_int32,
+                                 C.c_void_p, C.c_void_p, C.c_void_p]),
+    ("rfx_paths_order", C.c_int, [C.c_void_p, C.POINTER(PathPlanes), C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p,
+                                  C.c_void_p]),
     ("rfx_group_create", C.c_int, [C.POINTER(C.c_void_p), C.POINTER(C.c_int), C.c_int]),
     ("rfx_group_destroy", None, [C.c_void_p]),
     ("rfx_group_size", C.c_int, [C.c_void_p]),

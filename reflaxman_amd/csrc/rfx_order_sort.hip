@@ -3,6 +3,7 @@
 //
 //   order_keys_kernel    : a lane per ray, the 24-B record read non-temporally (rfx_ray_slot.h load_ray's read), the
 //                          key of rfx.h "Coherent order" written in ray order.
+//   paths_order_keys_kernel : the same key gathered through an index array (rfx.h rfx_paths_order): a lane per slot.
 //   order_hist_kernel    : a digit pass's per-workgroup histograms, table[digit][workgroup].
 //   order_scan_kernel    : workgroup d scans row d of the table in place (exclusive) and leaves the row's total.
 //   order_scatter_kernel : the stable scatter.  A pair's place is (the digits below its own, from the scanned totals) +
@@ -14,6 +15,7 @@
 
 #include "../../include/rfx.h"
 #include "rfx_launch.h"
+#include "rfx_paths.h"
 
 #pragma clang fp contract(off)
 
@@ -68,6 +70,27 @@ __global__ __launch_bounds__(kOrderThreads) void order_keys_kernel(OrderBox B, c
   const uint32_t k = order_key(B, ox, oy, oz, dx, dy, dz);
   keys[i] = k;
   if (keys2) keys2[i] = k;
+}
+
+// The paths' form (rfx.h rfx_paths_order): slot s keys the record of path index[s] (null: s); an entry that is no path
+// of the n reads nothing and takes the last key, so the sort keeps it behind every path
+__global__ __launch_bounds__(kOrderThreads) void paths_order_keys_kernel(OrderBox B, const float *rays, uint32_t n,
+                                                                         const uint32_t *index, uint32_t slots,
+                                                                         uint32_t *keys)
+{
+  const uint32_t s = blockIdx.x * kOrderThreads + threadIdx.x;
+  if (s >= slots) return;
+  const uint32_t i = index ? index[s] : s;
+  uint32_t k = 0xFFFFFFFFu;
+  if (i < n)
+  {
+    const float *f = rays + 6ull * i;
+    const float ox = __builtin_nontemporal_load(f), oy = __builtin_nontemporal_load(f + 1),
+                oz = __builtin_nontemporal_load(f + 2), dx = __builtin_nontemporal_load(f + 3),
+                dy = __builtin_nontemporal_load(f + 4), dz = __builtin_nontemporal_load(f + 5);
+    k = order_key(B, ox, oy, oz, dx, dy, dz);
+  }
+  keys[s] = k;
 }
 
 // ------------------------------------------------------------- the digit pass
@@ -210,6 +233,15 @@ hipError_t launch_order_keys(const OrderBox &B, const float *d_rays, uint32_t n,
   if (!n) return hipSuccess;
   hipLaunchKernelGGL(order_keys_kernel, dim3((n + kOrderThreads - 1) / kOrderThreads), dim3(kOrderThreads), 0, st, B,
                      d_rays, n, keys, keys2);
+  return hipGetLastError();
+}
+
+hipError_t launch_paths_order_keys(const OrderBox &B, const float *d_rays, uint32_t n, const uint32_t *d_index,
+                                   uint32_t slots, uint32_t *keys, hipStream_t st)
+{
+  if (!slots) return hipSuccess;
+  hipLaunchKernelGGL(paths_order_keys_kernel, dim3((slots + kOrderThreads - 1) / kOrderThreads), dim3(kOrderThreads), 0,
+                     st, B, d_rays, n, d_index, slots, keys);
   return hipGetLastError();
 }
 

@@ -759,6 +759,36 @@ class Renderer:
         hi = np.sqrt(d[:, 0] * d[:, 0] + d[:, 1] * d[:, 1] + d[:, 2] * d[:, 2], dtype=np.float32)
         return (1 - self.occluded(np.concatenate([a, d], axis=1), skip, hi=hi)).astype(np.uint8)
 
+    def paths(self, rays, draw=True) -> "Paths":
+        """The rays as resumable paths (rfx.h "Paths", rfx_paths_begin): a Paths whose step() runs Scene::trace's loop
+        segment by segment on state held on the device.  ``rays`` as for trace_rays: a torch tensor on this renderer's
+        device starts a torch-backed state with no host copy (the records are copied on the device: a step overwrites
+        them), anything else goes through numpy into device arrays of the library's own.  draw: True takes path i's
+        randDir from the i-th draw of the sphere stream, as trace_rays does; False leaves the streams alone and gives
+        every path the zero vector (the noise-free image); an (n, 3) array gives the caller's own directions."""
+        return Paths(self, rays, draw)
+
+    def trace_wavefront(self, rays, depth: int, order=None, argb: bool = False):
+        """trace_rays(rays, depth) as a wavefront loop over paths: begin, then a step per segment over the paths still
+        live, with order="coherent" the live list sorted by the paths' current rays (Paths.order) before every step but
+        the first.  The colours (and words, argb=True) are those of trace_rays, bit for bit, and so is the sphere
+        stream's end state; only the schedule differs."""
+        if order not in (None, "coherent"):
+            raise ValueError("trace_wavefront: order is None or \"coherent\"")
+        p = self.paths(rays)
+        try:
+            live = None
+            for k in range(1, int(depth) + 1):
+                if live is not None:
+                    if len(live) == 0:
+                        break
+                    if order == "coherent":
+                        live = p.order(live)
+                live = p.step(k, index=live, live=True)
+            return (p.colour, p.argb) if argb else p.colour
+        finally:
+            p.close()
+
     def set_tile_order(self, mode: int):
         """Trace-launch schedule (rfx.h rfx_renderer_set_tile_order): 1 longest-tile-first (8x8 wave tiles)
         from earlier launches' tile costs on large launches (default), 3 on every launch, 0 raster order,
@@ -899,6 +929,170 @@ class Renderer:
         after = C.c_uint32()
         check(_lib.load().rfx_rand_dirs(self._h, seed, n, _lib.fptr(out), C.byref(after)), "rfx_rand_dirs")
         return out, after.value
+
+
+class Paths:
+    """Scene::trace as resumable per-ray states on the device (rfx.h "Paths"), made by Renderer.paths.
+
+    The planes are torch tensors when the rays were one (every call then runs on torch's current stream and gives
+    tensors back: int32 for index lists, state and ARGB words), else device arrays of the library's own, read back as
+    numpy (uint32 index lists and words).  colour / state / rays / mul / rand / argb read the planes; segments decodes
+    the state words.  close() frees a numpy-backed state."""
+
+    PLANES = (("rays", 6, np.float32), ("mul", 3, np.float32), ("colour", 3, np.float32), ("rand", 3, np.float32),
+              ("state", 1, np.int32), ("argb", 1, np.uint32))
+
+    def __init__(self, renderer: "Renderer", rays, draw=True):
+        self._r, L = renderer, _lib.load()
+        is_torch, r, _ = renderer._ray_batch(rays, "paths")
+        n = int(r.shape[0])
+        if n == 0:
+            raise ValueError("paths: at least one ray")
+        own = None if isinstance(draw, (bool, int)) else np.ascontiguousarray(draw, np.float32).reshape(-1, 3)
+        if own is not None and own.shape[0] != n:
+            raise ValueError("paths: one randDir per ray")
+        self.n, self._torch, self._dev, self._t = n, is_torch, None, {}
+        if is_torch:
+            import torch
+            self._t["rays"] = r.clone()
+            for name, w, dt in self.PLANES[1:]:
+                shape = (n, w) if w > 1 else (n,)
+                tdt = torch.float32 if dt == np.float32 else torch.int32
+                self._t[name] = torch.zeros(shape, dtype=tdt, device=r.device)
+            if own is not None:
+                self._t["rand"].copy_(torch.from_numpy(own))
+            ptr = {k: v.data_ptr() for k, v in self._t.items()}
+        else:
+            self._dev = Renderer._DeviceArrays(renderer)
+            ptr = {"rays": self._dev.put(r).value}
+            for name, w, dt in self.PLANES[1:]:
+                a = own if name == "rand" and own is not None else np.zeros(n * w, dt)
+                ptr[name] = self._dev.put(a).value
+        self._planes = _lib.PathPlanes(**{"d_" + k: v for k, v in ptr.items()})
+        stream = self._enter()
+        check(L.rfx_paths_begin(renderer._h, C.byref(self._planes), n, 1 if own is None and draw else 0,
+                                C.c_void_p(stream or None)), "rfx_paths_begin")
+        self._leave(stream)
+
+    # torch: the current stream's handle; the legacy default stream has none to pass on, so there a call is fenced on
+    # both sides (Renderer.trace_rays).  numpy: the renderer's own stream.
+    def _enter(self):
+        if not self._torch:
+            return None
+        import torch
+        s = torch.cuda.current_stream(self._t["rays"].device)
+        if not s.cuda_stream:
+            s.synchronize()
+        return s.cuda_stream
+
+    def _leave(self, stream):
+        if self._torch and not stream:
+            self._r.synchronize()
+
+    def close(self):
+        if self._dev is not None:
+            self._dev.__exit__()
+            self._dev = None
+        self._t = {}
+
+    def _plane(self, name):
+        if self._torch:
+            return self._t[name]
+        w, dt = next((w, dt) for k, w, dt in self.PLANES if k == name)
+        a = np.empty((self.n, w) if w > 1 else (self.n,), dt)
+        return self._dev.get(a, C.c_void_p(getattr(self._planes, "d_" + name)))
+
+    colour = property(lambda self: self._plane("colour"))
+    state = property(lambda self: self._plane("state"))
+    rays = property(lambda self: self._plane("rays"))
+    mul = property(lambda self: self._plane("mul"))
+    rand = property(lambda self: self._plane("rand"))
+    argb = property(lambda self: self._plane("argb"))
+
+    @property
+    def segments(self):
+        """Segments run by every path so far (numpy): the state word while live, its complement once ended."""
+        s = self.state
+        return _lib.path_segments(s.cpu().numpy() if self._torch else s)
+
+    def _index(self, index, what):
+        """An index list as (device pointer or None, slots, what keeps it alive)."""
+        if index is None:
+            return None, self.n, None
+        if self._torch:
+            import torch
+            if isinstance(index, torch.Tensor):
+                t = index.to(device=self._t["rays"].device, dtype=torch.int32).reshape(-1).contiguous()
+            else:
+                a = np.ascontiguousarray(index).astype(np.uint32).view(np.int32).reshape(-1)
+                t = torch.from_numpy(a).to(self._t["rays"].device)
+            if t.numel() == 0:
+                raise ValueError(f"{what}: an empty index list")
+            return t.data_ptr(), int(t.numel()), t
+        a = np.ascontiguousarray(index).astype(np.uint32).reshape(-1)
+        if a.size == 0:
+            raise ValueError(f"{what}: an empty index list")
+        return self._dev.put(a).value, int(a.size), None
+
+    def _words(self, count):
+        """(device pointer, holder) of `count` uint32 of scratch."""
+        if self._torch:
+            import torch
+            t = torch.empty(count, dtype=torch.int32, device=self._t["rays"].device)
+            return t.data_ptr(), t
+        return self._dev.alloc(4 * count).value, None
+
+    def _free(self, *ptrs):
+        """numpy: a call's scratch goes once its results are read (the reads synchronise)."""
+        if self._torch:
+            return
+        gone = {p for p in ptrs if p}
+        for p in gone:
+            self._dev.L.rfx_device_free(self._r._h, C.c_void_p(p))
+        self._dev.ptrs = [q for q in self._dev.ptrs if q.value not in gone]
+
+    def step(self, upto: int, index=None, live: bool = False):
+        """rfx_paths_step: run every named live path that has run fewer than ``upto`` segments on to ``upto`` segments
+        or to its end.  index: the paths to work on, wave w of the launch taking index[64 w .. 64 w + 63] (None: all,
+        in order); an entry >= n is a dead lane.  live=True: return the indices of the named paths that are live after
+        the step (in no particular order) -- the next step's index; the count is read back, so this waits for the step."""
+        L = _lib.load()
+        stream = self._enter()
+        d_index, slots, keep = self._index(index, "step")
+        d_live = d_count = None
+        if live:
+            d_live, hold = self._words(slots + 1)  # the list, then its count
+            d_count = d_live + 4 * slots
+        check(L.rfx_paths_step(self._r._h, C.byref(self._planes), self.n, C.c_void_p(d_index), slots, int(upto),
+                               C.c_void_p(d_live), C.c_void_p(d_count), C.c_void_p(stream or None)), "rfx_paths_step")
+        self._leave(stream)
+        if not live:
+            if not self._torch and d_index:
+                self._r.synchronize()
+                self._free(d_index)
+            return None
+        if self._torch:
+            return hold[:int(hold[slots].item())]
+        count = int(self._dev.get(np.empty(1, np.uint32), C.c_void_p(d_count))[0])
+        out = self._dev.get(np.empty(count, np.uint32), C.c_void_p(d_live)) if count else np.empty(0, np.uint32)
+        self._free(d_index, d_live)
+        return out
+
+    def order(self, index=None):
+        """rfx_paths_order: the entries of ``index`` (None: every path) stably sorted by the coherent-order key of the
+        paths' current rays, entries >= n last -- the index of a step whose waves should hold like rays."""
+        L = _lib.load()
+        stream = self._enter()
+        d_index, slots, keep = self._index(index, "order")
+        d_order, hold = self._words(slots)
+        check(L.rfx_paths_order(self._r._h, C.byref(self._planes), self.n, C.c_void_p(d_index), slots,
+                                C.c_void_p(d_order), C.c_void_p(stream or None)), "rfx_paths_order")
+        self._leave(stream)
+        if self._torch:
+            return hold
+        out = self._dev.get(np.empty(slots, np.uint32), C.c_void_p(d_order))
+        self._free(d_index, d_order)
+        return out
 
 
 def make_frame(camera: Camera, W: int, H: int, reflect_num: int, sample_num: int = 1, additive: bool = False,

@@ -9,7 +9,8 @@ Kernel names are shortened to trace<STATS,MODE,CFG> / bounce<CFG> / bounce_lds<C
 trace_rays<STATS,CFG> (rfx_trace_rays.hip) / query_hits<CFG>, query_occluded<CFG> (rfx_trace_hits.hip) /
 trace_rays_ordered<CFG>, query_hits_ordered<CFG>, query_occluded_ordered<CFG> (rfx_trace_ordered.hip) /
 query_hits_span<CFG>, query_occluded_span<CFG> and their _ordered forms (rfx_trace_span.hip) / order_keys,
-order_hist, order_scan, order_scatter (the coherent order's sort, rfx_order_sort.hip); CFG bits (rfx_types.h kCfg*):
+order_hist, order_scan, order_scatter, paths_order_keys (the coherent order's sort, rfx_order_sort.hip) /
+paths_step<CFG>, paths_begin (rfx_trace_paths.hip); CFG bits (rfx_types.h kCfg*):
 1 cull, 2 >32 lights, 4 small scene, 8 planes, 16 park, 32 one light, 64 triangle BVH, 128 far light.
 """
 from __future__ import annotations
@@ -56,6 +57,12 @@ def short(name: str) -> str:
     m = re.match(r"_ZN3rfx\d+(order_\w+?)_kernelE", name)
     if m:
         return m.group(1)
+    m = re.match(r"_ZN3rfx17paths_step_kernelILi(\d+)EEEv", name)
+    if m:
+        return f"paths_step<{m.group(1)}>"
+    m = re.match(r"_ZN3rfx\d+(paths_\w+?)_kernelE", name)
+    if m:
+        return m.group(1)
     return name
 
 
@@ -81,7 +88,7 @@ def usage(tu: str):
     return [k for k in out if k["kernel"].startswith(("trace<", "trace_rays<", "bounce<", "bounce_lds<", "query_hits<", "query_occluded<",
                                                       "trace_rays_ordered<", "query_hits_ordered<",
                                                       "query_occluded_ordered<", "query_hits_span", "query_occluded_span",
-                                                      "order_"))]
+                                                      "order_", "paths_"))]
 
 
 def main():
