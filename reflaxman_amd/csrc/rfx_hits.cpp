@@ -4,31 +4,19 @@
 //
 // A query reads the uploaded scene and nothing else of the renderer: no pre-pass (the random streams stay where they
 // are), no tile schedule, no per-view masks, no regroup queue, no timing sums, and nothing rfx_frame_rng_rewind undoes.
-#include "rfx_internal.h"
+#include "rfx_query_host.h"
 
 using namespace rfx;
 
-// Launches of a ray batch's size (rays_per_launch).  P holds the whole batch's pointers; each launch takes them at its
+// Launches of a ray batch's size (launch_ranges).  P holds the whole batch's pointers; each launch takes them at its
 // first ray.
 static int run_query(rfx_renderer *r, const HitParams &P, bool any, hipStream_t st)
 {
-  const uint64_t per = rays_per_launch(r, P.W);
-  for (uint64_t a = 0; a < P.n; a += per)
-  {
-    HitParams Q = P;
-    Q.n = std::min(per, P.n - a);
-    Q.rays = P.rays + 6 * a;
-    if (P.skip) Q.skip = P.skip + a;
-    if (P.object) Q.object = P.object + a;
-    if (P.distance) Q.distance = P.distance + a;
-    if (P.point) Q.point = P.point + 3 * a;
-    if (P.normal) Q.normal = P.normal + 3 * a;
-    if (P.reflected) Q.reflected = P.reflected + 3 * a;
-    if (P.colour) Q.colour = P.colour + 3 * a;
-    if (P.occluded) Q.occluded = P.occluded + a;
+  return launch_ranges(r, P.n, P.W, [&](uint64_t a, uint64_t b) -> int {
+    const HitParams Q = hit_params_at(P, a, b - a);
     HIP_CHECK(launch_query_hits(r->dev, Q, any, st));
-  }
-  return RFX_OK;
+    return RFX_OK;
+  });
 }
 
 extern "C" int rfx_query_hits(rfx_renderer *r, const float *d_rays, uint64_t n, uint32_t raster_width,
@@ -62,13 +50,38 @@ extern "C" int rfx_query_occluded(rfx_renderer *r, const float *d_rays, const in
   return run_query(r, P, true, stream_or_own(r, stream));
 }
 
-extern "C" int rfx_query_hits_host(rfx_renderer *r, const float *rays, uint64_t n, uint32_t raster_width,
-                                   const rfx_hit_planes *out)
+// The host forms' interval on the device: one staging array of n words per given end (every end is a 4-B word)
+struct HostSpan {
+  DevBuf<float> d;
+  rfx_ray_span dev{};
+  int put(rfx_renderer *r, const rfx_ray_span *span, uint64_t n, bool with_after)
+  {
+    if (!span) return RFX_OK;
+    const void *host[3] = {span->d_lo, span->d_lo && with_after ? span->d_after : nullptr, span->d_hi};
+    size_t words = 0;
+    for (const void *h : host) words += h ? (size_t)n : 0;
+    if (!words) return RFX_OK;
+    int rc;
+    if ((rc = d.reserve(words)) < 0) return rc;
+    float *p = d.p;
+    const void *at[3] = {nullptr, nullptr, nullptr};
+    for (int k = 0; k < 3; ++k)
+      if (host[k])
+      {
+        RCHECK(copy_in(r, p, host[k], (size_t)n * sizeof(float)));
+        at[k] = p;
+        p += n;
+      }
+    dev.d_lo = static_cast<const float *>(at[0]);
+    dev.d_after = static_cast<const int32_t *>(at[1]);
+    dev.d_hi = static_cast<const float *>(at[2]);
+    return RFX_OK;
+  }
+};
+
+int rfx::query_hits_host(rfx_renderer *r, const float *rays, const rfx_ray_span *span, bool spanned, uint64_t n,
+                         uint32_t raster_width, const rfx_hit_planes *out)
 {
-  int rc;
-  if ((rc = enter_call(r, rays && n && out && any_plane(out), "query_hits_host",
-                       "renderer, rays, n > 0 and at least one output plane required")) != RFX_OK)
-    return rc;
   // one staging array: the rays, then the requested planes one after the other (every plane is made of 4-B words)
   float *const host[6] = {reinterpret_cast<float *>(out->object), out->distance, out->point, out->normal,
                           out->reflected, out->colour};
@@ -80,8 +93,10 @@ extern "C" int rfx_query_hits_host(rfx_renderer *r, const float *rays, uint64_t 
     if (host[k]) total += words[k];
   }
   DevBuf<float> d;
-  if ((rc = d.reserve(total)) < 0) return rc;
-  HIP_CHECK(hipMemcpyAsync(d, rays, (size_t)n * 6 * sizeof(float), hipMemcpyHostToDevice, r->stream));
+  HostSpan hs;
+  int rc;
+  if ((rc = d.reserve(total)) < 0 || (rc = hs.put(r, span, n, true)) < 0) return rc;
+  RCHECK(copy_in(r, d, rays, (size_t)n * 6 * sizeof(float)));
   rfx_hit_planes dp{};
   if (host[0]) dp.object = reinterpret_cast<int32_t *>(d.p + off[0]);
   if (host[1]) dp.distance = d.p + off[1];
@@ -89,18 +104,40 @@ extern "C" int rfx_query_hits_host(rfx_renderer *r, const float *rays, uint64_t 
   if (host[3]) dp.normal = d.p + off[3];
   if (host[4]) dp.reflected = d.p + off[4];
   if (host[5]) dp.colour = d.p + off[5];
-  rc = rfx_query_hits(r, d, n, raster_width, &dp, nullptr);
-  // d is freed on return: whatever was enqueued reads and writes it before that
-  if (rc != RFX_OK)
-  {
-    (void)hipStreamSynchronize(r->stream);
+  rc = spanned ? rfx_query_hits_span(r, d, &hs.dev, n, raster_width, &dp, nullptr)
+               : rfx_query_hits(r, d, n, raster_width, &dp, nullptr);
+  for (int k = 0; k < 6 && rc == RFX_OK; ++k)
+    if (host[k]) rc = copy_out(r, host[k], d.p + off[k], words[k] * sizeof(float));
+  return host_done(r, rc);
+}
+
+int rfx::query_occluded_host(rfx_renderer *r, const float *rays, const int32_t *skip, const rfx_ray_span *span,
+                             bool spanned, uint64_t n, uint32_t raster_width, uint8_t *occluded)
+{
+  DevBuf<float> d_rays;
+  DevBuf<int32_t> d_skip;
+  DevBuf<uint8_t> d_occ;
+  HostSpan hs;
+  int rc;
+  if ((rc = d_rays.reserve((size_t)n * 6)) < 0 || (rc = d_occ.reserve((size_t)n)) < 0 ||
+      (skip && (rc = d_skip.reserve((size_t)n)) < 0) || (rc = hs.put(r, span, n, false)) < 0)
     return rc;
-  }
-  for (int k = 0; k < 6; ++k)
-    if (host[k])
-      HIP_CHECK(hipMemcpyAsync(host[k], d.p + off[k], words[k] * sizeof(float), hipMemcpyDeviceToHost, r->stream));
-  HIP_CHECK(hipStreamSynchronize(r->stream));
-  return RFX_OK;
+  RCHECK(copy_in(r, d_rays, rays, (size_t)n * 6 * sizeof(float)));
+  if (skip) RCHECK(copy_in(r, d_skip, skip, (size_t)n * sizeof(int32_t)));
+  rc = spanned ? rfx_query_occluded_span(r, d_rays, skip ? d_skip.p : nullptr, &hs.dev, n, raster_width, d_occ, nullptr)
+               : rfx_query_occluded(r, d_rays, skip ? d_skip.p : nullptr, n, raster_width, d_occ, nullptr);
+  if (rc == RFX_OK) rc = copy_out(r, occluded, d_occ, (size_t)n);
+  return host_done(r, rc);
+}
+
+extern "C" int rfx_query_hits_host(rfx_renderer *r, const float *rays, uint64_t n, uint32_t raster_width,
+                                   const rfx_hit_planes *out)
+{
+  int rc;
+  if ((rc = enter_call(r, rays && n && out && any_plane(out), "query_hits_host",
+                       "renderer, rays, n > 0 and at least one output plane required")) != RFX_OK)
+    return rc;
+  return query_hits_host(r, rays, nullptr, false, n, raster_width, out);
 }
 
 extern "C" int rfx_query_occluded_host(rfx_renderer *r, const float *rays, const int32_t *skip, uint64_t n,
@@ -110,21 +147,5 @@ extern "C" int rfx_query_occluded_host(rfx_renderer *r, const float *rays, const
   if ((rc = enter_call(r, rays && n && occluded, "query_occluded_host",
                        "renderer, rays, n > 0 and the result array required")) != RFX_OK)
     return rc;
-  DevBuf<float> d_rays;
-  DevBuf<int32_t> d_skip;
-  DevBuf<uint8_t> d_occ;
-  if ((rc = d_rays.reserve((size_t)n * 6)) < 0 || (rc = d_occ.reserve((size_t)n)) < 0 ||
-      (skip && (rc = d_skip.reserve((size_t)n)) < 0))
-    return rc;
-  HIP_CHECK(hipMemcpyAsync(d_rays, rays, (size_t)n * 6 * sizeof(float), hipMemcpyHostToDevice, r->stream));
-  if (skip) HIP_CHECK(hipMemcpyAsync(d_skip, skip, (size_t)n * sizeof(int32_t), hipMemcpyHostToDevice, r->stream));
-  rc = rfx_query_occluded(r, d_rays, skip ? d_skip.p : nullptr, n, raster_width, d_occ, nullptr);
-  if (rc != RFX_OK)
-  {
-    (void)hipStreamSynchronize(r->stream);
-    return rc;
-  }
-  HIP_CHECK(hipMemcpyAsync(occluded, d_occ, (size_t)n, hipMemcpyDeviceToHost, r->stream));
-  HIP_CHECK(hipStreamSynchronize(r->stream));
-  return RFX_OK;
+  return query_occluded_host(r, rays, skip, nullptr, false, n, raster_width, occluded);
 }

@@ -8,6 +8,8 @@
 //   query_hits_body, query_occluded_body : the two kernels' text, written once: the lane's ray and whether it is live
 //       come from the caller (these kernels here, the ordered ones in rfx_ordered.h).  The launch tables are
 //       rfx_batch_launch.h's.
+//   lane_ray, hit_none, hit_planes_store : a lane's ray, the empty hit record, and the closest hit's output planes --
+//       written once for these bodies and the span queries' (rfx_span.h).
 //
 // One lane per ray, a wave's unit and a lane's ray by ray_slot's rule (rfx_ray_slot.h): 64 consecutive rays, or an 8x8 tile
 // of the batch read as a row-major raster.  Every lane of a wave reaches the query -- lanes past the batch's end or
@@ -45,42 +47,32 @@ __device__ __forceinline__ RaySlot hit_slot(const HitParams &P)
   return ray_slot(P, ray_unit(P, wv, w8), w8, lane);
 }
 
-// sl: the lane's ray among P's arrays, and whether the lane is live.  lut: the calling kernel's own 256-entry LDS table
-// (declared there, so that each kernel's LDS layout is its own).
-template <int CFG>
-__device__ __forceinline__ void query_hits_body(const DevScene &S, const HitParams &P, const RaySlot &sl, float *lut)
+// The lane's ray: ray i of `rays` in a live lane, zero in every other
+__device__ __forceinline__ RayRecord lane_ray(const float *rays, uint64_t i, bool live)
 {
-  static_assert((CFG & ~kHitCfgMask) == 0 && !((CFG & kCfgSmall) && (CFG & kCfgTriBvh)), "a query's CFG bits");
-  constexpr bool SMALL = (CFG & kCfgSmall) != 0, PLANES = (CFG & kCfgPlanes) != 0, TBVH = (CFG & kCfgTriBvh) != 0;
-  const bool live = sl.valid;
-  v3 o = mk(0.0f, 0.0f, 0.0f), d = mk(0.0f, 0.0f, 0.0f);
-  if (live)
-  {
-    const RayRecord r = load_ray(P.rays, sl.i);
-    o = r.o;
-    d = r.d;
-  }
-  // the colour plane's texels go through Color(ARGB)'s table; nothing here raises a power
-  for (uint32_t i = threadIdx.x; i < 256; i += kWgThreads) lut[i] = (float)i / 255.0f;  // Color.cpp:11-13
-  if constexpr (SMALL) stage_small_scene(S);
-  __syncthreads();
-  Cnt cnt;
-  const Tabs<SMALL> T{S};
+  RayRecord r;
+  r.o = r.d = mk(0.0f, 0.0f, 0.0f);
+  if (live) r = load_ray(rays, i);
+  return r;
+}
+
+// The closest-hit record before any candidate is taken
+__device__ __forceinline__ Hit hit_none()
+{
   Hit h;
   h.obj = -1; h.kind = 0; h.i = 0; h.t = 0.0f; h.u = 0.0f; h.v = 0.0f; h.sq = kNoHitKey;
-  if (__ballot(live))  // (a bundle needs a live lane; a raster's edge tiles may hold none)
-  {
-    const Bundle B = make_bundle(o, d, live);
-    if constexpr (SMALL)
-    {
-      uint64_t om = S.cull_valid;
-      if (B.ok) om = cull_small(T.cull(), S.cull_valid, B);
-      if (live) closest_hit_small<false, PLANES>(S, o, d, om, h, cnt);
-    }
-    else
-      closest_hit<false, PLANES, TBVH>(S, o, d, live, &B, h, cnt);
-  }
-  if (!live) return;
+  return h;
+}
+
+// A live lane's planes of P from its closest-hit record h (h.obj < 0: the miss values) for the ray (o, d): the one place
+// a plane is computed and stored, for the plain queries' body below and the span queries' (rfx_span.h).  lut: the
+// kernel's Color(ARGB) table.
+template <int CFG>
+__device__ __forceinline__ void hit_planes_store(const DevScene &S, const HitParams &P, const RaySlot &sl, v3 o, v3 d,
+                                                 const Hit &h, const float *lut, Cnt &cnt)
+{
+  constexpr bool SMALL = (CFG & kCfgSmall) != 0, PLANES = (CFG & kCfgPlanes) != 0;
+  const Tabs<SMALL> T{S};
   // Scene.cpp:82: curDist starts at FLT_MAX, the hit object at none
   const bool hit = h.obj >= 0;
   if (P.object) P.object[sl.i] = hit ? h.obj : -1;
@@ -125,19 +117,46 @@ __device__ __forceinline__ void query_hits_body(const DevScene &S, const HitPara
   if (P.colour) store3(P.colour, sl.i, mk(c.r, c.g, c.b));
 }
 
+// sl: the lane's ray among P's arrays, and whether the lane is live.  lut: the calling kernel's own 256-entry LDS table
+// (declared there, so that each kernel's LDS layout is its own).
+template <int CFG>
+__device__ __forceinline__ void query_hits_body(const DevScene &S, const HitParams &P, const RaySlot &sl, float *lut)
+{
+  static_assert((CFG & ~kHitCfgMask) == 0 && !((CFG & kCfgSmall) && (CFG & kCfgTriBvh)), "a query's CFG bits");
+  constexpr bool SMALL = (CFG & kCfgSmall) != 0, PLANES = (CFG & kCfgPlanes) != 0, TBVH = (CFG & kCfgTriBvh) != 0;
+  const bool live = sl.valid;
+  const RayRecord r = lane_ray(P.rays, sl.i, live);
+  const v3 o = r.o, d = r.d;
+  // the colour plane's texels go through Color(ARGB)'s table; nothing here raises a power
+  for (uint32_t i = threadIdx.x; i < 256; i += kWgThreads) lut[i] = (float)i / 255.0f;  // Color.cpp:11-13
+  if constexpr (SMALL) stage_small_scene(S);
+  __syncthreads();
+  Cnt cnt;
+  Hit h = hit_none();
+  if (__ballot(live))  // (a bundle needs a live lane; a raster's edge tiles may hold none)
+  {
+    const Bundle B = make_bundle(o, d, live);
+    if constexpr (SMALL)
+    {
+      const Tabs<SMALL> T{S};
+      uint64_t om = S.cull_valid;
+      if (B.ok) om = cull_small(T.cull(), S.cull_valid, B);
+      if (live) closest_hit_small<false, PLANES>(S, o, d, om, h, cnt);
+    }
+    else
+      closest_hit<false, PLANES, TBVH>(S, o, d, live, &B, h, cnt);
+  }
+  if (live) hit_planes_store<CFG>(S, P, sl, o, d, h, lut, cnt);
+}
+
 template <int CFG>
 __device__ __forceinline__ void query_occluded_body(const DevScene &S, const HitParams &P, const RaySlot &sl)
 {
   static_assert((CFG & ~kHitCfgMask) == 0 && !((CFG & kCfgSmall) && (CFG & kCfgTriBvh)), "a query's CFG bits");
   constexpr bool SMALL = (CFG & kCfgSmall) != 0, PLANES = (CFG & kCfgPlanes) != 0, TBVH = (CFG & kCfgTriBvh) != 0;
   const bool live = sl.valid;
-  v3 o = mk(0.0f, 0.0f, 0.0f), d = mk(0.0f, 0.0f, 0.0f);
-  if (live)
-  {
-    const RayRecord r = load_ray(P.rays, sl.i);
-    o = r.o;
-    d = r.d;
-  }
+  const RayRecord r = lane_ray(P.rays, sl.i, live);
+  const v3 o = r.o, d = r.d;
   // the object left out, as (kind, index within its kind's device arrays): kat_objects' decode of obj_loc
   int skip_sph = -1, skip_tri = -1, skip_pln = -1;
   if (live && P.skip)

@@ -5,12 +5,40 @@
 // The order call reads the uploaded scene's key box and its own scratch and nothing else of the renderer.  The ordered
 // trace is a ray batch (rfx_rays.cpp) in one launch; the ordered queries are hit queries (rfx_hits.cpp) and, like
 // them, leave every stream, mask and timing sum alone.
-#include "rfx_internal.h"
+#include "rfx_query_host.h"
 
 using namespace rfx;
 
+// The sort's passes: one per digit of the key.  At least two, so that d_order may be d_index: the pass that reads the one
+// is not the pass that writes the other.
 constexpr uint32_t kKeyBits = 3 * RFX_ORDER_CELL_BITS + 2 * RFX_ORDER_DIR_BITS;
 constexpr uint32_t kPasses = (kKeyBits + kOrderDigitBits - 1) / kOrderDigitBits;
+static_assert(kPasses >= 2, "d_order may be d_index: the pass that reads the one is not the pass that writes the other");
+
+int rfx::order_scratch(rfx_renderer *r, uint32_t m)
+{
+  int rc;
+  if ((rc = r->order_keys.reserve(2 * (size_t)m)) < 0 || (rc = r->order_idx.reserve(2 * (size_t)m)) < 0 ||
+      (rc = r->order_table.reserve((size_t)kOrderDigits * order_groups(m) + kOrderDigits)) < 0)
+    return rc;
+  return RFX_OK;
+}
+
+int rfx::order_sort(rfx_renderer *r, uint32_t m, const uint32_t *d_index, uint32_t *d_order, hipStream_t st)
+{
+  uint32_t *const key[2] = {r->order_keys.p, r->order_keys.p + m}, *const idx[2] = {r->order_idx.p, r->order_idx.p + m};
+  uint32_t *const table = r->order_table.p, *const totals = table + (size_t)kOrderDigits * order_groups(m);
+  // pass p sorts by digit p, least significant first, from half p & 1 to the other; the first takes d_index (or the
+  // index itself), the last leaves the indices alone, in the caller's array
+  for (uint32_t p = 0; p < kPasses; ++p)
+  {
+    const uint32_t a = p & 1u, b = a ^ 1u;
+    const bool last = p + 1 == kPasses;
+    HIP_CHECK(launch_order_pass(key[a], p ? idx[a] : d_index, last ? nullptr : key[b], last ? d_order : idx[b], m,
+                                p * kOrderDigitBits, table, totals, st));
+  }
+  return RFX_OK;
+}
 
 extern "C" int rfx_renderer_order_box(const rfx_renderer *r, float lo[3], float scale[3])
 {
@@ -33,22 +61,9 @@ extern "C" int rfx_rays_order(rfx_renderer *r, const float *d_rays, uint64_t n, 
     return rc;
   const hipStream_t st = stream_or_own(r, stream);
   const uint32_t m = (uint32_t)n;
-  if ((rc = r->order_keys.reserve(2 * (size_t)m)) < 0 || (rc = r->order_idx.reserve(2 * (size_t)m)) < 0 ||
-      (rc = r->order_table.reserve((size_t)kOrderDigits * order_groups(m) + kOrderDigits)) < 0)
-    return rc;
-  uint32_t *const key[2] = {r->order_keys.p, r->order_keys.p + m}, *const idx[2] = {r->order_idx.p, r->order_idx.p + m};
-  uint32_t *const table = r->order_table.p, *const totals = table + (size_t)kOrderDigits * order_groups(m);
-  HIP_CHECK(launch_order_keys(r->order_box, d_rays, m, key[0], d_keys, st));
-  // pass p sorts by digit p, least significant first, from half p & 1 to the other; the first takes the index itself,
-  // the last leaves the indices alone, in the caller's array
-  for (uint32_t p = 0; p < kPasses; ++p)
-  {
-    const uint32_t a = p & 1u, b = a ^ 1u;
-    const bool last = p + 1 == kPasses;
-    HIP_CHECK(launch_order_pass(key[a], p ? idx[a] : nullptr, last ? nullptr : key[b], last ? d_order : idx[b], m,
-                                p * kOrderDigitBits, table, totals, st));
-  }
-  return RFX_OK;
+  if ((rc = order_scratch(r, m)) < 0) return rc;
+  HIP_CHECK(launch_order_keys(r->order_box, d_rays, m, r->order_keys.p, d_keys, st));
+  return order_sort(r, m, nullptr, d_order, st);
 }
 
 extern "C" int rfx_rays_order_host(rfx_renderer *r, const float *rays, uint64_t n, uint32_t *order, uint32_t *keys)
@@ -60,18 +75,11 @@ extern "C" int rfx_rays_order_host(rfx_renderer *r, const float *rays, uint64_t 
   DevBuf<float> d_rays;
   DevBuf<uint32_t> d_out;  // the order, then the keys
   if ((rc = d_rays.reserve((size_t)n * 6)) < 0 || (rc = d_out.reserve((size_t)n * (keys ? 2 : 1))) < 0) return rc;
-  HIP_CHECK(hipMemcpyAsync(d_rays, rays, (size_t)n * 6 * sizeof(float), hipMemcpyHostToDevice, r->stream));
+  RCHECK(copy_in(r, d_rays, rays, (size_t)n * 6 * sizeof(float)));
   rc = rfx_rays_order(r, d_rays, n, d_out, keys ? d_out.p + n : nullptr, nullptr);
-  // the arrays are freed on return: whatever was enqueued reads and writes them before that
-  if (rc != RFX_OK)
-  {
-    (void)hipStreamSynchronize(r->stream);
-    return rc;
-  }
-  HIP_CHECK(hipMemcpyAsync(order, d_out, (size_t)n * sizeof(uint32_t), hipMemcpyDeviceToHost, r->stream));
-  if (keys) HIP_CHECK(hipMemcpyAsync(keys, d_out.p + n, (size_t)n * sizeof(uint32_t), hipMemcpyDeviceToHost, r->stream));
-  HIP_CHECK(hipStreamSynchronize(r->stream));
-  return RFX_OK;
+  if (rc == RFX_OK) rc = copy_out(r, order, d_out, (size_t)n * sizeof(uint32_t));
+  if (rc == RFX_OK && keys) rc = copy_out(r, keys, d_out.p + n, (size_t)n * sizeof(uint32_t));
+  return host_done(r, rc);
 }
 
 extern "C" int rfx_trace_rays_ordered(rfx_renderer *r, const float *d_rays, const uint32_t *d_order, uint64_t n,
@@ -100,21 +108,15 @@ extern "C" int rfx_trace_rays_ordered(rfx_renderer *r, const float *d_rays, cons
   return RFX_OK;
 }
 
-// The slots in launches of a linear batch's size (rays_per_launch, as rfx_hits.cpp run_query); every launch sees the
+// The slots in launches of a linear batch's size (launch_ranges, as rfx_hits.cpp run_query); every launch sees the
 // whole arrays.
 static int run_query_ordered(rfx_renderer *r, const HitParams &H, const uint32_t *d_order, bool any, hipStream_t st)
 {
-  const uint64_t per = rays_per_launch(r, 0);
-  for (uint64_t a = 0; a < H.n; a += per)
-  {
-    HitOrderParams Q{};
-    Q.H = H;
-    Q.order = d_order;
-    Q.slot0 = a;
-    Q.slot1 = std::min(H.n, a + per);
+  return launch_ranges(r, H.n, 0, [&](uint64_t a, uint64_t b) -> int {
+    const HitOrderParams Q{H, d_order, a, b};
     HIP_CHECK(launch_query_hits_ordered(r->dev, Q, any, st));
-  }
-  return RFX_OK;
+    return RFX_OK;
+  });
 }
 
 extern "C" int rfx_query_hits_ordered(rfx_renderer *r, const float *d_rays, const uint32_t *d_order, uint64_t n,

@@ -9,7 +9,7 @@
 // not a ray of the batch, is a dead lane: it reads and writes nothing, and reaches the wave-wide code as an invalid
 // lane does.  Outputs leave per lane (12-B and 4-B stores): a wave's rays are nowhere near each other, so the staged
 // 16-B forms of the unordered kernels do not apply.  There is no stats form.  rfx_trace_ordered.hip holds these kernels;
-// rfx_span.h includes this for ordered_slot alone.
+// rfx_span.h includes this for ordered_query_slot alone.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -64,11 +64,16 @@ __global__ __launch_bounds__(kWgThreads) __attribute__((amdgpu_waves_per_eu(
 #include "rfx_rays_body.inc"  // the kernel's text, on S, P, STATS, CFG, Rays and lut
 }
 
-// A lane's slot of an ordered query: wave w of the launch takes the slots slot0 + 64 w .. of [slot0, slot1)
-__device__ __forceinline__ RaySlot ordered_hit_slot(const HitOrderParams &P)
+// A lane's slot of an ordered query, plain or span: wave w of the launch takes the slots slot0 + 64 w .. of
+// [slot0, slot1), each naming one of the batch's n rays
+__device__ __forceinline__ RaySlot ordered_query_slot(const uint32_t *order, uint64_t slot0, uint64_t slot1, uint64_t n)
 {
   const uint32_t lane = threadIdx.x & 63u, wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  return ordered_slot(P.order, P.slot0 + 64ull * (kWgWaves * blockIdx.x + wv) + lane, P.slot1, P.H.n);
+  return ordered_slot(order, slot0 + 64ull * (kWgWaves * blockIdx.x + wv) + lane, slot1, n);
+}
+__device__ __forceinline__ RaySlot ordered_hit_slot(const HitOrderParams &P)
+{
+  return ordered_query_slot(P.order, P.slot0, P.slot1, P.H.n);
 }
 
 template <int CFG>

@@ -18,8 +18,8 @@
 //     exactly dist == hi is still taken.  The any-hit walk prunes by the seed alone.
 //   * The small-scene triangle loop runs every triangle's own z stage (no TriMates group state), so a mate the span
 //     filters out leaves nothing behind for the next one.
-// The kernels' outputs are rfx_hits.h's (span_planes_store), their CFG bits a query's three, their slots ray_slot's rule
-// or the ordered one (rfx_ordered.h ordered_slot).  rfx_trace_span.hip is the one unit that includes this.
+// The kernels' outputs are rfx_hits.h's (hit_planes_store), their CFG bits a query's three, their slots ray_slot's rule
+// or the ordered one (rfx_ordered.h ordered_query_slot). rfx_trace_span.hip is the one unit that includes this.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -272,60 +272,6 @@ __device__ __forceinline__ void span_walk(const DevScene &S, v3 o, v3 ray, bool 
   if constexpr (PLANES) span_planes(S, o, ray, k, vis, cnt);
 }
 
-// A live lane's planes of P from its closest-hit record h (h.obj < 0: the miss values) for the ray (o, d): the words
-// query_hits_body (rfx_hits.h) writes after its walk, expression for expression.  It is restated here and not shared:
-// moving it out of query_hits_body changed the code of the two existing units that hold that body.  To do once those
-// units may change: one store function in rfx_hits.h for both bodies (and one staging helper for the host forms of
-// rfx_hits.cpp and rfx_span.cpp), so that a plane is defined in one place.
-template <int CFG>
-__device__ __forceinline__ void span_planes_store(const DevScene &S, const HitParams &P, const RaySlot &sl, v3 o, v3 d,
-                                                  const Hit &h, const float *lut, Cnt &cnt)
-{
-  constexpr bool SMALL = (CFG & kCfgSmall) != 0, PLANES = (CFG & kCfgPlanes) != 0;
-  const Tabs<SMALL> T{S};
-  // Scene.cpp:82: curDist starts at FLT_MAX, the hit object at none
-  const bool hit = h.obj >= 0;
-  if (P.object) P.object[sl.i] = hit ? h.obj : -1;
-  if (P.distance) P.distance[sl.i] = hit ? sqrt_rn(h.sq) : __FLT_MAX__;
-  if (!(P.point || P.normal || P.reflected || P.colour)) return;
-  v3 drop = mk(0.0f, 0.0f, 0.0f), norm = drop, refl = drop;
-  col c = mkc(0.0f, 0.0f, 0.0f);
-  if (hit)
-  {
-    drop = add(o, mul(d, h.t));
-    MatRec m;
-    if (h.kind == 0)
-    {
-      const SphereGeo g = T.sph_geo(h.i);
-      norm = sub(drop, mk(g.cx, g.cy, g.cz));                                  // Sphere.cpp:67
-      m = T.sph_mat(h.i);
-    }
-    else if (!PLANES || h.kind == 1)
-    {
-      const TriShade sh = T.tri_shade(h.i);
-      norm = mk(sh.nx, sh.ny, sh.nz);
-      m = T.tri_mat(h.i);
-      if (P.colour && sh.tex >= 0)                                             // Triangle.cpp:89-96
-      {
-        const col tc = tri_texel<false>(S, sh, h.u, h.v, lut, cnt);
-        m.r = tc.r; m.g = tc.g; m.b = tc.b;
-      }
-    }
-    else
-    {
-      const PlaneGeo g = S.pln_geo[h.i];
-      norm = mk(g.nx, g.ny, g.nz);                                             // Plane.cpp:58-59
-      m = S.pln_mat[h.i];                                                      // untextured (Plane.cpp:67-68)
-    }
-    c = mkc(m.r, m.g, m.b);
-    refl = reflect(mul(d, h.t), norm);                                         // trace_math.cpp:14-23
-  }
-  if (P.point) store3(P.point, sl.i, drop);
-  if (P.normal) store3(P.normal, sl.i, norm);
-  if (P.reflected) store3(P.reflected, sl.i, refl);
-  if (P.colour) store3(P.colour, sl.i, mk(c.r, c.g, c.b));
-}
-
 // ------------------------------------------------------------- the two bodies
 // sl: the lane's ray among P's arrays and whether the lane is live (query_hits_body's rule); lut: the kernel's own table
 template <int CFG>
@@ -333,22 +279,17 @@ __device__ __forceinline__ void query_hits_span_body(const DevScene &S, const Sp
 {
   static_assert((CFG & ~kHitCfgMask) == 0 && !((CFG & kCfgSmall) && (CFG & kCfgTriBvh)), "a query's CFG bits");
   const bool live = sl.valid;
-  v3 o = mk(0.0f, 0.0f, 0.0f), d = mk(0.0f, 0.0f, 0.0f);
-  if (live)
-  {
-    const RayRecord r = load_ray(P.H.rays, sl.i);
-    o = r.o;
-    d = r.d;
-  }
+  const RayRecord r = lane_ray(P.H.rays, sl.i, live);
+  const v3 o = r.o, d = r.d;
   SpanClosest vis;
   vis.sp = span_lane(P, sl.i, live);
-  vis.h.obj = -1; vis.h.kind = 0; vis.h.i = 0; vis.h.t = 0.0f; vis.h.u = 0.0f; vis.h.v = 0.0f; vis.h.sq = kNoHitKey;
+  vis.h = hit_none();
   for (uint32_t i = threadIdx.x; i < 256; i += kWgThreads) lut[i] = (float)i / 255.0f;  // Color.cpp:11-13
   if constexpr ((CFG & kCfgSmall) != 0) stage_small_scene(S);
   __syncthreads();
   Cnt cnt;
   if (__ballot(live)) span_walk<CFG>(S, o, d, live, vis, cnt);  // (a raster's edge tiles may hold no live lane)
-  if (live) span_planes_store<CFG>(S, P.H, sl, o, d, vis.h, lut, cnt);
+  if (live) hit_planes_store<CFG>(S, P.H, sl, o, d, vis.h, lut, cnt);
 }
 
 template <int CFG>
@@ -356,13 +297,8 @@ __device__ __forceinline__ void query_occluded_span_body(const DevScene &S, cons
 {
   static_assert((CFG & ~kHitCfgMask) == 0 && !((CFG & kCfgSmall) && (CFG & kCfgTriBvh)), "a query's CFG bits");
   const bool live = sl.valid;
-  v3 o = mk(0.0f, 0.0f, 0.0f), d = mk(0.0f, 0.0f, 0.0f);
-  if (live)
-  {
-    const RayRecord r = load_ray(P.H.rays, sl.i);
-    o = r.o;
-    d = r.d;
-  }
+  const RayRecord r = lane_ray(P.H.rays, sl.i, live);
+  const v3 o = r.o, d = r.d;
   SpanAny vis;
   vis.sp = span_lane(P, sl.i, live);
   vis.sp.after = -1;  // (the any-hit has no `after`: its lower end is inclusive)
@@ -384,10 +320,7 @@ template <bool ORDERED>
 __device__ __forceinline__ RaySlot span_slot(const SpanParams &P)
 {
   if constexpr (ORDERED)
-  {
-    const uint32_t lane = threadIdx.x & 63u, wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    return ordered_slot(P.order, P.slot0 + 64ull * (kWgWaves * blockIdx.x + wv) + lane, P.slot1, P.H.n);
-  }
+    return ordered_query_slot(P.order, P.slot0, P.slot1, P.H.n);
   else
     return hit_slot(P.H);
 }

@@ -21,6 +21,7 @@ Drop-in semantics (Render.cpp:57-226):
 """
 from __future__ import annotations
 
+import contextlib
 import ctypes as C
 import os
 from typing import List, Optional, Sequence
@@ -560,6 +561,50 @@ class Renderer:
             ends[k] = a
         return ends
 
+    def _query(self, kind, what, is_torch, r, stream, raster_width, order, ends, skip, out):
+        """One call of a hit query (query_hits: kind "hits"; occluded: kind "occluded").  The C entry is
+        rfx_query_<kind>[_span][_ordered | _host]: _span with an interval (ends, from _span), _ordered with ``order``,
+        else _host for numpy arrays.  Tensors are passed where they lie, on ``stream`` (_ray_batch; the legacy stream is
+        fenced here); numpy arrays with ``order``, which has no host form, go through _DeviceArrays.  skip: the any-hit's
+        array or None; out: the result arrays by name, filled in place -- the planes of "hits" (an rfx_hit_planes), the
+        one array of "occluded"."""
+        n, host = r.shape[0], not is_torch and order is None
+        name = f"rfx_query_{kind}" + ("_span" if ends is not None else "") + (
+            "_ordered" if order is not None else "_host" if host else "")
+        address = lambda p: C.cast(p, C.c_void_p).value
+        with (contextlib.nullcontext() if is_torch or host else self._DeviceArrays(self)) as dev:
+            if is_torch:
+                src = dst = lambda a: C.c_void_p(a.data_ptr())
+            elif host:
+                src = dst = lambda a: a.ctypes.data_as(C.POINTER(np.ctypeslib.as_ctypes_type(a.dtype)))
+            else:
+                src, dst = dev.put, lambda a: dev.alloc(a.nbytes)
+            d_rays = src(r)
+            args = [self._h, d_rays]
+            if kind == "occluded":
+                args.append(src(skip) if skip is not None else None)
+            if ends is not None:
+                args.append(C.byref(_lib.RaySpan(**{k: address(src(a)) for k, a in ends.items()})))
+            if order is not None:
+                o = self._order_tensor(order, r, what) if is_torch else None
+                args.append(src(o) if is_torch else self._order_array(dev, order, d_rays, n, what))
+            args.append(n)
+            if order is None:
+                args.append(int(raster_width))
+            d_out = {k: dst(a) for k, a in out.items()}
+            if kind == "hits":
+                args.append(C.byref(_lib.HitPlanes(**{k: address(p) for k, p in d_out.items()})))
+            else:
+                args.extend(d_out.values())
+            if not host:
+                args.append(C.c_void_p(stream or None))
+            check(getattr(_lib.load(), name)(*args), name)
+            if dev is not None:
+                for k, a in out.items():
+                    dev.get(a, d_out[k])
+        if is_torch and not stream:
+            self.synchronize()
+
     def query_hits(self, rays, raster_width: int = 0, want=HIT_PLANES, order=None, lo=None, after=None, hi=None):
         """The closest hit of every ray (rfx.h rfx_query_hits: one pass of Scene.cpp:82-107): a dict of the planes
         named in ``want`` -- object (n, int32, -1 = no hit), distance (n, FLT_MAX on a miss), point, normal, reflected,
@@ -576,65 +621,17 @@ class Renderer:
         want = tuple(want)
         if not want or any(k not in self.HIT_PLANES for k in want):
             raise ValueError(f"query_hits: want names at least one of {self.HIT_PLANES}")
-        L = _lib.load()
         is_torch, r, stream = self._ray_batch(rays, "query_hits")
         n = r.shape[0]
         shape = lambda k: (n,) if k in ("object", "distance") else (n, 3)
-        hp = _lib.HitPlanes()
         if is_torch:
             import torch
             out = {k: torch.empty(shape(k), dtype=torch.int32 if k == "object" else torch.float32, device=r.device)
                    for k in want}
-            for k in want:
-                setattr(hp, k, out[k].data_ptr())
-            ends = self._span("query_hits", n, True, r.device, lo, after, hi)
-            if ends is not None:
-                sp = _lib.RaySpan(**{k: a.data_ptr() for k, a in ends.items()})
-                if order is not None:
-                    o = self._order_tensor(order, r, "query_hits")
-                    check(L.rfx_query_hits_span_ordered(self._h, C.c_void_p(r.data_ptr()), C.byref(sp),
-                                                        C.c_void_p(o.data_ptr()), n, C.byref(hp),
-                                                        C.c_void_p(stream or None)), "rfx_query_hits_span_ordered")
-                else:
-                    check(L.rfx_query_hits_span(self._h, C.c_void_p(r.data_ptr()), C.byref(sp), n, int(raster_width),
-                                                C.byref(hp), C.c_void_p(stream or None)), "rfx_query_hits_span")
-            elif order is not None:
-                o = self._order_tensor(order, r, "query_hits")
-                check(L.rfx_query_hits_ordered(self._h, C.c_void_p(r.data_ptr()), C.c_void_p(o.data_ptr()), n,
-                                               C.byref(hp), C.c_void_p(stream or None)), "rfx_query_hits_ordered")
-            else:
-                check(L.rfx_query_hits(self._h, C.c_void_p(r.data_ptr()), n, int(raster_width), C.byref(hp),
-                                       C.c_void_p(stream or None)), "rfx_query_hits")
-            if not stream:
-                self.synchronize()
-            return out
-        out = {k: np.empty(shape(k), np.int32 if k == "object" else np.float32) for k in want}
-        ends = self._span("query_hits", n, False, None, lo, after, hi)
-        if order is not None:
-            with self._DeviceArrays(self) as dev:
-                d_rays = dev.put(r)
-                d_order = self._order_array(dev, order, d_rays, n, "query_hits")
-                d_out = {k: dev.alloc(out[k].nbytes) for k in want}
-                for k in want:
-                    setattr(hp, k, d_out[k].value)
-                if ends is not None:
-                    sp = _lib.RaySpan(**{k: dev.put(a).value for k, a in ends.items()})
-                    check(L.rfx_query_hits_span_ordered(self._h, d_rays, C.byref(sp), d_order, n, C.byref(hp), None),
-                          "rfx_query_hits_span_ordered")
-                else:
-                    check(L.rfx_query_hits_ordered(self._h, d_rays, d_order, n, C.byref(hp), None),
-                          "rfx_query_hits_ordered")
-                for k in want:
-                    dev.get(out[k], d_out[k])
-            return out
-        for k in want:
-            setattr(hp, k, out[k].ctypes.data)
-        if ends is not None:
-            sp = _lib.RaySpan(**{k: a.ctypes.data for k, a in ends.items()})
-            check(L.rfx_query_hits_span_host(self._h, _lib.fptr(r), C.byref(sp), n, int(raster_width), C.byref(hp)),
-                  "rfx_query_hits_span_host")
-            return out
-        check(L.rfx_query_hits_host(self._h, _lib.fptr(r), n, int(raster_width), C.byref(hp)), "rfx_query_hits_host")
+        else:
+            out = {k: np.empty(shape(k), np.int32 if k == "object" else np.float32) for k in want}
+        ends = self._span("query_hits", n, is_torch, r.device if is_torch else None, lo, after, hi)
+        self._query("hits", "query_hits", is_torch, r, stream, raster_width, order, ends, None, out)
         return out
 
     def occluded(self, rays, skip=None, raster_width: int = 0, order=None, lo=None, hi=None):
@@ -647,72 +644,21 @@ class Renderer:
         in [lo, hi] count -- the ray becomes a segment.  Arrays of n entries of the kind ``rays`` is, or one number."""
         if order is not None and raster_width:
             raise ValueError("occluded: order goes with no raster_width")
-        L = _lib.load()
         is_torch, r, stream = self._ray_batch(rays, "occluded")
         n = r.shape[0]
         if is_torch:
             import torch
-            sk = None
-            if skip is not None:
-                sk = torch.as_tensor(skip, device=r.device).to(torch.int32).reshape(-1).contiguous()
-                if sk.numel() != n:
-                    raise ValueError("occluded: one skip entry per ray")
-            occ = torch.empty(n, dtype=torch.uint8, device=r.device)
-            d_skip = C.c_void_p(sk.data_ptr() if sk is not None else None)
-            ends = self._span("occluded", n, True, r.device, lo, None, hi)
-            if ends is not None:
-                sp = _lib.RaySpan(**{k: a.data_ptr() for k, a in ends.items()})
-                if order is not None:
-                    o = self._order_tensor(order, r, "occluded")
-                    check(L.rfx_query_occluded_span_ordered(self._h, C.c_void_p(r.data_ptr()), d_skip, C.byref(sp),
-                                                            C.c_void_p(o.data_ptr()), n, C.c_void_p(occ.data_ptr()),
-                                                            C.c_void_p(stream or None)), "rfx_query_occluded_span_ordered")
-                else:
-                    check(L.rfx_query_occluded_span(self._h, C.c_void_p(r.data_ptr()), d_skip, C.byref(sp), n,
-                                                    int(raster_width), C.c_void_p(occ.data_ptr()),
-                                                    C.c_void_p(stream or None)), "rfx_query_occluded_span")
-            elif order is not None:
-                o = self._order_tensor(order, r, "occluded")
-                check(L.rfx_query_occluded_ordered(self._h, C.c_void_p(r.data_ptr()), d_skip, C.c_void_p(o.data_ptr()), n,
-                                                   C.c_void_p(occ.data_ptr()), C.c_void_p(stream or None)),
-                      "rfx_query_occluded_ordered")
-            else:
-                check(L.rfx_query_occluded(self._h, C.c_void_p(r.data_ptr()), d_skip, n, int(raster_width),
-                                           C.c_void_p(occ.data_ptr()), C.c_void_p(stream or None)), "rfx_query_occluded")
-            if not stream:
-                self.synchronize()
-            return occ
         sk = None
         if skip is not None:
-            sk = np.ascontiguousarray(skip, np.int32).reshape(-1)
-            if sk.size != n:
+            if is_torch:
+                sk = torch.as_tensor(skip, device=r.device).to(torch.int32).reshape(-1).contiguous()
+            else:
+                sk = np.ascontiguousarray(skip, np.int32).reshape(-1)
+            if (sk.numel() if is_torch else sk.size) != n:
                 raise ValueError("occluded: one skip entry per ray")
-        occ = np.empty(n, np.uint8)
-        ends = self._span("occluded", n, False, None, lo, None, hi)
-        if order is not None:
-            with self._DeviceArrays(self) as dev:
-                d_rays = dev.put(r)
-                d_order = self._order_array(dev, order, d_rays, n, "occluded")
-                d_skip = dev.put(sk) if sk is not None else None
-                d_occ = dev.alloc(n)
-                if ends is not None:
-                    sp = _lib.RaySpan(**{k: dev.put(a).value for k, a in ends.items()})
-                    check(L.rfx_query_occluded_span_ordered(self._h, d_rays, d_skip, C.byref(sp), d_order, n, d_occ, None),
-                          "rfx_query_occluded_span_ordered")
-                else:
-                    check(L.rfx_query_occluded_ordered(self._h, d_rays, d_skip, d_order, n, d_occ, None),
-                          "rfx_query_occluded_ordered")
-                dev.get(occ, d_occ)
-            return occ
-        if ends is not None:
-            sp = _lib.RaySpan(**{k: a.ctypes.data for k, a in ends.items()})
-            check(L.rfx_query_occluded_span_host(self._h, _lib.fptr(r), sk.ctypes.data_as(_lib._i32p) if sk is not None else None,
-                                                 C.byref(sp), n, int(raster_width), occ.ctypes.data_as(C.POINTER(C.c_uint8))),
-                  "rfx_query_occluded_span_host")
-            return occ
-        check(L.rfx_query_occluded_host(self._h, _lib.fptr(r), sk.ctypes.data_as(_lib._i32p) if sk is not None else None,
-                                        n, int(raster_width), occ.ctypes.data_as(C.POINTER(C.c_uint8))),
-              "rfx_query_occluded_host")
+        occ = torch.empty(n, dtype=torch.uint8, device=r.device) if is_torch else np.empty(n, np.uint8)
+        ends = self._span("occluded", n, is_torch, r.device if is_torch else None, lo, None, hi)
+        self._query("occluded", "occluded", is_torch, r, stream, raster_width, order, ends, sk, {"occluded": occ})
         return occ
 
     def query_layers(self, rays, k: int, want=HIT_PLANES, raster_width: int = 0, order=None):

@@ -460,6 +460,38 @@ def test_sizes_splitting_and_orders(name):
     r.close()
 
 
+@pytest.mark.parametrize("name", ["default", "planes300"])
+def test_host_forms_equal_the_device_forms_across_a_launch_split(name):
+    """Through numpy (the host forms) and through a tensor (the device forms) every word is the same, for each plane
+    asked alone and all six, without ends and with hi alone, and for the any-hit with and without skip -- on the
+    smallest batches that take two launches: 65 rays at a limit of 64 (the second launch one ray), and a 21-wide raster
+    of 189 rays at a limit of 168 (one tile row of 8 x 21, then one row)."""
+    r, s, cam = renderer(name)
+    for n, limit, rw in ((65, 64, 0), (189, 168, 21)):
+        rays = pierce_rays(name)[:n]
+        r.set_launch_traces(limit)
+        full = hits(r, rays, raster_width=rw)
+        assert (full["object"] >= 0).sum() >= n // 2 and full["object"][-1] >= 0  # (the planes are not all misses)
+        with np.errstate(over="ignore"):  # (a miss's FLT_MAX doubled is +inf)
+            hi = (full["distance"] * np.where(np.arange(n) % 2 == 0, 2.0, 0.5).astype(np.float32)).astype(np.float32)
+        for ends in ({}, {"hi": hi}):
+            tag = (name, n, rw, tuple(ends))
+            for want in [(k,) for k in PLANES] + [PLANES]:
+                dev_out = hits(r, rays, raster_width=rw, want=want, **ends)
+                host_out = r.query_hits(rays, raster_width=rw, want=want, **ends)
+                assert tuple(host_out) == want and tuple(dev_out) == want, tag
+                assert all(isinstance(v, np.ndarray) for v in host_out.values()), tag
+                assert_planes(host_out, dev_out, tag + (want,))
+                if not ends:
+                    assert_planes(dev_out, {k: full[k] for k in want}, tag + (want, "alone = among six"))
+            for skip in (None, full["object"]):
+                assert_occ(r.occluded(rays, skip, raster_width=rw, **ends), shadow(r, rays, skip, raster_width=rw, **ends),
+                           tag + ("any-hit", skip is not None))
+        cut = hits(r, rays, raster_width=rw, hi=hi)["object"]
+        assert (cut != full["object"]).sum() >= n // 8  # (hi does cut winners off)
+    r.close()
+
+
 def test_sentinels_and_unrequested_planes():
     """16 sentinel words either side of every output and span buffer stay as they were; an unrequested plane stays
     wholly as it was."""
