@@ -106,6 +106,12 @@ int rfx_scene_counts(const rfx_scene *scene, int *spheres, int *triangles, int *
  * for the leaf size), < 0 on error. */
 int rfx_scene_tri_bvh_dump(const rfx_scene *scene, int32_t counts[5], float *boxes, int32_t *children,
                            int32_t *leaf_ids, int32_t *residual);
+/* The bundle-cull records a renderer would upload for a small scene (at most 32 spheres and 32 triangles), as built
+ * (host only; for tests of the culls, DESIGN.md "Exact work skipping"): recs -- 64 lane records of 8 floats (centre x y z,
+ * radius, plane normal x y z, plane offset; sphere i in lane (i & 1) 16 + (i >> 1), triangle i in lane 32 + i), tris --
+ * 32 footprint records of 12 floats (v0, |gu|, gu, |gv|, gv, |gu + gv|), valid -- the lanes that hold an object.  Any
+ * pointer may be null.  RFX_ERR_STATE for a scene that is not small. */
+int rfx_scene_cull_dump(const rfx_scene *scene, float recs[64 * 8], float tris[32 * 12], uint64_t *valid);
 /* Mate groups of the scene's triangles (host only; DESIGN.md "Coplanar mates"): triangles whose plane-crossing half of
  * Triangle::trace gives one value for every ray -- the third row of axTrans finite and bitwise equal, v0 finite and
  * bitwise equal on every axis whose row-3 coefficient is not zero.  The small-scene kernels compute that half once per

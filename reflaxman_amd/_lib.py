@@ -88,6 +88,7 @@ SIGNATURES = [
     ("rfx_scene_add_triangle", C.c_int, [C.c_void_p, _fp, _fp, _fp, C.c_int, _fp, C.c_float, C.c_float]),
     ("rfx_scene_add_mesh", C.c_int, [C.c_void_p, _fp, C.c_uint32, _u32p, C.c_uint32, C.c_int, _fp, C.c_float, C.c_float]),
     ("rfx_scene_tri_bvh_dump", C.c_int, [C.c_void_p, _i32p, _fp, _i32p, _i32p, _i32p]),
+    ("rfx_scene_cull_dump", C.c_int, [C.c_void_p, _fp, _fp, _u64p]),
     ("rfx_scene_set_tri_mates", C.c_int, [C.c_void_p, C.c_int]),
     ("rfx_scene_tri_mates", C.c_int, [C.c_void_p, _i32p, _fp]),
     ("rfx_scene_set_far_lights", C.c_int, [C.c_void_p, C.c_int]),

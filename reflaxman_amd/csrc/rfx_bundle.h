@@ -212,8 +212,8 @@ __device__ __forceinline__ uint64_t cull_chunk(const Bound *bound, int first, in
 // a crossing by at most |d| (1 + 1 / n.dir)).  If that disk lies outside the triangle in (u, v) -- u or v below
 // 0, or u + v above 1, by more than R |gu|, R |gv|, R |gu + gv| -- no ray of the bundle can hit it.  Margins
 // cover the reference's float (u, v): its inverse basis and its t differ from the exact ones by a relative
-// ~150 eps for cond < 100, amplified at most 10x by 1 / ndmin; the margins are 1e-2 of |g| times the
-// distances involved (|o - v0| plus the travel to the plane).
+// ~150 eps for cond < 100 (the host's gate, rfx_scene.cpp), amplified at most 10x by 1 / ndmin; the margins are 1e-2 of |g|
+// times the distances involved (|o - v0| plus the travel to the plane).  Measured: tests/test_bundle_cull_bound.py (footprint).
 __device__ __forceinline__ bool tri_footprint_misses(const CullTri &q, float side, float an, const Bundle &B)
 {
   const float h = fabsf(side), anp = side > 0.0f ? -an : an;  // height, cosine of the axis into the plane
@@ -237,9 +237,9 @@ __device__ __forceinline__ bool tri_footprint_misses(const CullTri &q, float sid
 // Small scenes: lane l tests cull record l (rfx_types.h CullRec) -- the cone test of cull_chunk, and
 // for a triangle also its plane: when every origin lies more than rw (plus a margin) on one side and
 // every direction leaves that side (axis . n beyond sin of the cone's half-angle, plus a margin), every
-// ray has t <= 0 for the plane.  The reference's float test then sees -ao.z and ar.z of opposite signs
-// too: for a basis with cond <= 1000 their rounding error stays below 2e-4 of |o - v0| and |ray|, inside
-// the 1e-3 margins.  FOOT (the precomputed primary masks only): triangles also take the footprint test above.
+// ray has t <= 0 for the plane.  The reference's float test then sees -ao.z and ar.z of opposite signs too: for a
+// basis with cond <= 1000 their rounding error stays below 2e-4 of |o - v0| and |ray|, inside the 1e-3 margins (measured
+// with the record's own rounding: tests/test_bundle_cull_bound.py).  FOOT (the primary masks only): the footprint test above.
 // Bits of lanes without an object are cleared.
 template <bool FOOT = false>
 __device__ __forceinline__ uint64_t cull_small(const CullRec *tab, uint64_t valid, const Bundle &B,

@@ -1152,3 +1152,18 @@ SceneBuild::SceneBuild(const rfx_scene &scene, int tri_accel)
   d.half_tile_w = s->half_tile_w;
   d.half_tile_h = s->half_tile_h;
 }
+
+// The small-scene cull records as SceneBuild makes them (host only, for the tests of the bundle culls): the 64 lane
+// records (rfx_types.h CullRec, 8 floats each), the 32 footprint records (CullTri, 12 floats each), the valid lanes.
+extern "C" int rfx_scene_cull_dump(const rfx_scene *s, float recs[64 * 8], float tris[32 * 12], uint64_t *valid)
+{
+  if (!s) return fail(RFX_ERR_ARG, "scene_cull_dump: no scene");
+  if (!(s->spheres.size() <= 32 && s->tris.size() <= 32))
+    return fail(RFX_ERR_STATE, "scene_cull_dump: not a small scene (more than 32 spheres or triangles)");
+  const SceneBuild B(*s, 0);
+  static_assert(sizeof(CullRec) == 8 * sizeof(float) && sizeof(CullTri) == 12 * sizeof(float), "dump layout");
+  if (recs) memcpy(recs, B.cs.data(), 64 * sizeof(CullRec));
+  if (tris) memcpy(tris, B.ct.data(), 32 * sizeof(CullTri));
+  if (valid) *valid = B.d.cull_valid;
+  return RFX_OK;
+}

@@ -190,6 +190,14 @@ class Scene:
         return {"nodes": nodes, "leaves": leaves, "leaf_size": leaf, "depth": depth, "boxes": boxes,
                 "children": children, "leaf_ids": ids, "residual": res}
 
+    def cull_dump(self):
+        """The bundle-cull records of a small scene as a renderer would upload them (rfx.h rfx_scene_cull_dump; host
+        only): (recs (64, 8), tris (32, 12), valid lanes as an int)."""
+        recs, tris = np.zeros((64, 8), np.float32), np.zeros((32, 12), np.float32)
+        valid = C.c_uint64(0)
+        check(_lib.load().rfx_scene_cull_dump(self._h, _lib.fptr(recs), _lib.fptr(tris), C.byref(valid)), "Scene.cull_dump")
+        return recs, tris, int(valid.value)
+
     def set_tri_mates(self, on: bool):
         """Group coplanar triangles whose plane crossing is one value per ray (rfx.h rfx_scene_set_tri_mates): on by
         default; off makes every triangle its own group.  No pixel changes; read by the next upload of the scene."""
