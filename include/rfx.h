@@ -584,6 +584,77 @@ int rfx_paths_step(rfx_renderer *r, const rfx_paths *p, uint64_t n, const uint32
 int rfx_paths_order(rfx_renderer *r, const rfx_paths *p, uint64_t n, const uint32_t *d_index /* or NULL */,
                     uint64_t slots, uint32_t *d_order, void *stream);
 
+/* ---------------------------------------------------------------- Moving meshes
+ * A deforming mesh keeps its topology: its triangles' records and boxes change, its tree does not.  These calls give
+ * triangles of the uploaded scene new vertices on the device, stream-ordered, without the host rebuild and re-upload of
+ * rfx_renderer_set_scene.  (Added under RFX_ABI_VERSION 5; detect them by symbol.)
+ *
+ * Contract: after the call every launch on the renderer returns, word for word, what a renderer returns whose
+ * rfx_renderer_set_scene got the same scene built at the new vertices -- frames of every mode, rfx_trace_rays, the hit
+ * queries and spans, the ordered forms, rfx_paths_step -- settings, random streams and inputs being the same.  The update
+ * touches neither random stream (rfx_renderer_get_rng reads the same before and after), nor the tile costs, the timing
+ * sums, the regroup queue or the rewind state; it drops the per-view masks, as rfx_renderer_set_scene does.  The
+ * coherent order's key box (rfx_renderer_order_box) stays as rfx_renderer_set_scene computed it: it is a schedule
+ * input, and no value of an ordered call depends on it.
+ *
+ * What follows a vertex (DESIGN.md "Moving meshes"): the triangle's v0 and axTrans (Triangle.cpp:11-21, the
+ * reference's float operations in its operand order), its normal, its bounding sphere, its copy in the triangle BVH's
+ * leaves, and the BVH's boxes -- every node refitted on every update from the current vertices alone, by the builder's
+ * own widening formula, so repeated updates do not drift.  The tree's topology, the residual list and the margin
+ * reference point stay as built: only speed follows a mesh that has moved far from where its tree was cut, and
+ * rfx_renderer_set_scene restores it.  A triangle of the tree whose new basis is ill-conditioned (cond >= 300, singular,
+ * a non-finite vertex) may report hits far from its vertices: its leaf and every box above it become all of space (NaN
+ * bounds, which the kernels' box test keeps for every ray; rfx_renderer_tri_bvh_nodes reports them as 0x7FC00000), so
+ * every ray still tests it.  A residual triangle that becomes well-conditioned stays residual.
+ *
+ * Works on non-small scenes (more than 32 spheres or more than 32 triangles), with or without a triangle BVH.  A small
+ * scene is RFX_ERR_STATE: its 64 lane records, footprints and mate groups are uploaded again by
+ * rfx_renderer_set_scene in microseconds.  Materials, textures, uv and object indices stay; spheres and lights do not
+ * move.
+ *
+ * Triangles [first, first + count) take new vertices; `first` counts triangles in insertion order (0 = the scene's
+ * first triangle, rfx_scene_tri_mates' numbering; rfx_scene_object_triangle maps an object index to it).
+ *   d_indices == NULL : d_positions holds 9 floats per triangle, (v1, v2, v3) as rfx_scene_add_triangle takes them;
+ *                       n_positions == 3 * count.
+ *   d_indices != NULL : 3 uint32 per triangle into d_positions (n_positions x 3 floats), rfx_scene_add_mesh's form.  A
+ *                       triangle naming an index >= n_positions keeps its old vertices (a dead lane: it cannot be an
+ *                       error without a sync).
+ * Stream-ordered (NULL = the renderer's stream), no host sync.
+ * Errors: NULL renderer or positions, count == 0, first + count > the scene's triangles, d_indices == NULL with
+ * n_positions != 3 * count: RFX_ERR_ARG; no scene uploaded, or a small scene: RFX_ERR_STATE. */
+int rfx_renderer_update_triangles(rfx_renderer *r, uint32_t first, uint32_t count, const float *d_positions,
+                                  uint32_t n_positions, const uint32_t *d_indices, void *stream);
+/* The same on host arrays: copies them in on the renderer's stream and synchronises. */
+int rfx_renderer_update_triangles_host(rfx_renderer *r, uint32_t first, uint32_t count, const float *positions,
+                                       uint32_t n_positions, const uint32_t *indices);
+/* The host scene kept in step: Triangle.cpp:11-21 run again in place on triangles [first, first + count) (v0, v1, v2,
+ * norm, axTrans and the builder's condition number) from 9 floats each.  Material, texture, uv and object index stay.
+ * Read by the next rfx_renderer_set_scene. */
+int rfx_scene_set_triangle_vertices(rfx_scene *scene, uint32_t first, uint32_t count, const float *vertices9);
+/* The triangle index (insertion order among triangles) of an object, or RFX_ERR_ARG for a non-triangle. */
+int rfx_scene_object_triangle(const rfx_scene *scene, int object_index);
+/* The words that follow a triangle's vertices, RFX_TRI_RECORD_WORDS uint32 per triangle of [first, first + count), from
+ * the host scene and -- a device read-back, synchronises; not for a small scene -- from the uploaded one:
+ *   [0, 12)  the geometry record: v0 x y z, axTrans row 3, then (a11, a21), (a12, a22), (a13, a23);
+ *   [12, 15) the normal;   [15, 19) the bounding sphere: centre x y z, radius (+inf: never culled);
+ *   [19, 28) the vertices as given;   [28] 1 = well-conditioned, 0 = not;
+ *   [29, 41) the triangle BVH's copy of the geometry record (a triangle outside the tree, and the host scene: words
+ *            [0, 12) again).
+ * Every NaN is reported as 0x7FC00000 (its sign and payload carry nothing and differ between processors), so equal
+ * scenes give equal words. */
+#define RFX_TRI_RECORD_WORDS 41
+int rfx_scene_tri_records(const rfx_scene *scene, uint32_t first, uint32_t count, uint32_t *out);
+int rfx_renderer_tri_records(rfx_renderer *r, uint32_t first, uint32_t count, uint32_t *out);
+/* The tree rfx_scene_tri_bvh_dump reports for `built` -- its topology, leaf membership and residual list -- refitted on
+ * the host to the vertices given (9 floats for every triangle of the scene), as the device update refits it: boxes --
+ * nodes x 12 floats in the dump's layout, mt -- nodes x 2 margin terms; either may be NULL.  widen = 0: the boxes as
+ * built (at the scene's own vertices: the dump's, bit for bit); widen = 1: the device copy, grown by the cull margin
+ * from the tree's reference point.  Returns 1 with a tree, 0 without. */
+int rfx_scene_tri_bvh_refit(const rfx_scene *built, const float *vertices9_all, int widen, float *boxes, float *mt);
+/* The uploaded triangle BVH's nodes read back (synchronises): 16 words per node -- 12 box floats in the dump's layout,
+ * the 2 children as int32, the 2 margin terms.  Returns the node count (0: no tree); out may be NULL to ask for it. */
+int rfx_renderer_tri_bvh_nodes(rfx_renderer *r, float *out);
+
 /* ---------------------------------------------------------------- Device groups (multi-GPU, one process)
  * A group renders the frame of Render::renderNext (Render.cpp:136-215) on several devices of this process: row bands,
  * one per member, each member counting its slice of the frame's random stream and pushing it to the others (the one

@@ -16,6 +16,7 @@ RFX_NCOUNTERS = 40
 RFX_ABI_VERSION = 5
 # the coherent order's key widths and the sort's rays per workgroup (rfx.h "Coherent order")
 RFX_ORDER_CELL_BITS, RFX_ORDER_DIR_BITS, RFX_ORDER_TILE = 4, 10, 4096
+RFX_TRI_RECORD_WORDS = 41  # rfx.h "Moving meshes": words per triangle of rfx_scene_tri_records / rfx_renderer_tri_records
 METAL, DIELECTRIC = 0, 1
 
 _fp = C.POINTER(C.c_float)
@@ -164,6 +165,15 @@ SIGNATURES = [
                                  C.c_void_p, C.c_void_p, C.c_void_p]),
     ("rfx_paths_order", C.c_int, [C.c_void_p, C.POINTER(PathPlanes), C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p,
                                   C.c_void_p]),
+    ("rfx_renderer_update_triangles", C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p,
+                                                C.c_void_p]),
+    ("rfx_renderer_update_triangles_host", C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, _fp, C.c_uint32, _u32p]),
+    ("rfx_scene_set_triangle_vertices", C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, _fp]),
+    ("rfx_scene_object_triangle", C.c_int, [C.c_void_p, C.c_int]),
+    ("rfx_scene_tri_records", C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, _u32p]),
+    ("rfx_renderer_tri_records", C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, _u32p]),
+    ("rfx_scene_tri_bvh_refit", C.c_int, [C.c_void_p, _fp, C.c_int, _fp, _fp]),
+    ("rfx_renderer_tri_bvh_nodes", C.c_int, [C.c_void_p, _fp]),
     ("rfx_group_create", C.c_int, [C.POINTER(C.c_void_p), C.POINTER(C.c_int), C.c_int]),
     ("rfx_group_destroy", None, [C.c_void_p]),
     ("rfx_group_size", C.c_int, [C.c_void_p]),

@@ -299,6 +299,8 @@ extern "C" int rfx_renderer_set_scene(rfx_renderer *r, const rfx_scene *s)
       (rc = upload(r, B.tt.nodes, &d.tri_bvh)) || (rc = upload(r, B.tleaf, &d.tri_leaf)) ||
       (rc = upload(r, B.tt.resid, &d.tri_resid)) || (rc = upload(r, B.aux, &d.bvh_aux)))
     return rc;
+  r->dev = d;
+  if ((rc = upload_update_tables(r, B)) != RFX_OK) return rc;
   r->accel = B.accel;
   r->order_box = B.order_box;
   r->dev = d;

@@ -8,6 +8,7 @@
 #include <vector>
 
 #include "rfx_launch.h"
+#include "rfx_refit.h"
 #include "rfx_scene.h"
 
 #define HIP_CHECK(expr)                                                                          \
@@ -202,6 +203,15 @@ struct rfx_renderer {
   // keys and indices (two halves each) and the digit pass's histogram table with its totals
   rfx::OrderBox order_box{};
   rfx::DevBuf<uint32_t> order_keys, order_idx, order_table;
+  // moving meshes (rfx_update.cpp; filled by set_scene for a non-small scene with triangles, upd_tris its count, else
+  // 0): per triangle its current vertices, its record in tri_leaf and its class flag; the tree's leaf membership, its
+  // nodes by height (upd_hoff: the heights' ends in upd_hlist) and the refit's unwidened boxes; the host form's staging
+  rfx::DevBuf<float> upd_verts, upd_pos;
+  rfx::DevBuf<int32_t> upd_slot, upd_order, upd_hlist;
+  rfx::DevBuf<uint32_t> upd_ill, upd_idx;
+  rfx::DevBuf<rfx::RefitBox> upd_lbox, upd_nbox;
+  std::vector<uint32_t> upd_hoff;
+  uint32_t upd_tris = 0, upd_leaves = 0;
   // per-phase event timing: triples {start, after pre-pass, after trace} on every timing_every-th frame (the events'
   // own cost stays off the other frames: ~10 us per frame for three records at C1's 640x480)
   bool timing = false, timing_this = false;
@@ -221,6 +231,8 @@ int save_rewind_state(rfx_renderer *r, hipStream_t st);
 // takes: their randDir states into r->rd on `st`, the sphere stream n accepted triples on, the jitter stream untouched.
 // Fails while an emitted frame is pending; the call cannot be undone by rfx_frame_rng_rewind.
 int prepass_traces(rfx_renderer *r, uint64_t n, hipStream_t st);
+// rfx_update.cpp: the moving-mesh tables of the scene set_scene has just uploaded (r's device current, its stream idle)
+int upload_update_tables(rfx_renderer *r, const SceneBuild &B);
 
 // ---- what the batch entry points share (rfx_rays.cpp, rfx_hits.cpp, rfx_order.cpp)
 // A call's opening tests: its arguments (args_ok false, or no renderer: "<call>: <required>") and an uploaded scene

@@ -137,8 +137,10 @@ extern "C" int rfx_kat_rng_seq_legacy(rfx_renderer *r, uint32_t *counts)
   int rc;
   if ((rc = d_jump.reserve(jump.size())) < 0 || (rc = d_cnt.reserve(nb)) < 0 || (rc = d_origin.reserve(1)) < 0)
     return named("kat_rng_seq_legacy", rc);
-  hipError_t e = hipMemcpy(d_jump, jump.data(), jump.size() * sizeof(uint32_t), hipMemcpyHostToDevice);
-  if (e == hipSuccess) e = hipMemset(d_origin, 0, sizeof(uint32_t));  // the cycle's origin state
+  // both on the kernel's stream: it is a non-blocking one, which the null stream's copies and memsets are not ordered
+  // with (and a memset may return before it has run)
+  hipError_t e = hipMemcpyAsync(d_jump, jump.data(), jump.size() * sizeof(uint32_t), hipMemcpyHostToDevice, r->stream);
+  if (e == hipSuccess) e = hipMemsetAsync(d_origin, 0, sizeof(uint32_t), r->stream);  // the cycle's origin state
   if (e == hipSuccess) e = launch_rng_count(d_origin, d_jump, d_cnt, 0, nb, nullptr, r->stream);
   if (e == hipSuccess) e = hipStreamSynchronize(r->stream);
   if (e == hipSuccess) e = hipMemcpy(counts, d_cnt, nb * sizeof(uint32_t), hipMemcpyDeviceToHost);

@@ -85,4 +85,11 @@ hipError_t launch_order_pass(const uint32_t *kin, const uint32_t *iin, uint32_t 
 hipError_t launch_trace_rays_ordered(const DevScene &S, const FrameParams &P, const float *d_rays,
                                      const uint32_t *d_order, hipStream_t st);
 hipError_t launch_query_hits_ordered(const DevScene &S, const HitOrderParams &P, bool any, hipStream_t st);
+// ---- rfx_update_kernels.hip: moving meshes (rfx_refit.h) -- the updated triangles' records, the leaves' boxes, and the nodes
+// of one height from the boxes below them
+struct UpdateParams;
+struct RefitParams;
+hipError_t launch_update_tris(const UpdateParams &P, hipStream_t st);
+hipError_t launch_refit_leaves(const RefitParams &P, hipStream_t st);
+hipError_t launch_refit_nodes(const RefitParams &P, hipStream_t st);
 }  // namespace rfx

@@ -1,0 +1,184 @@
+// What follows a triangle's vertices, written once for the three places that compute it: the host scene builder
+// (rfx_scene.cpp: rfx_scene_add_triangle, SceneBuild, build_pair_bvh), the host refit (rfx_scene_tri_bvh_refit) and the
+// device update (rfx_update_kernels.hip).  Float steps are rfx_math.h's (the reference's Triangle constructor, operation for
+// operation); double steps are IEEE add, multiply, divide and sqrt, so with FP contraction off the device gives the
+// host's words.  No HIP needed: a plain C++ compiler builds rfx_scene.cpp with this.
+#pragma once
+#include <math.h>
+
+#include "rfx_math.h"
+#include "rfx_types.h"
+
+#pragma clang fp contract(off)
+
+namespace rfx {
+
+// A triangle is well-conditioned -- its reported hits lie within the cull margin of its vertices, so it may be culled by
+// a bound and live in the tree -- when det is usable and cond = sqrt(|M|_F^2 |M^-1|_F^2) < 300.  kTriCondSq is the
+// smallest double whose correctly rounded root is >= 300, so p < kTriCondSq <=> sqrt(p) < 300.0 for every double p (the
+// root is monotone; NaN fails both): the device decides the class without a double root (tests/test_mesh_update_host.py
+// checks the constant's two neighbours).
+constexpr double kTriCondSq = 0x1.5f8ffffffffffp+16;
+
+// Triangle.cpp:11-21 from the three vertices as rfx_scene_add_triangle takes them, and the builder's condition terms:
+// p = |basis|_F^2 |axTrans|_F^2 in double, det_ok = the basis' float determinant is above kVerySmall
+struct TriSetup {
+  v3 v0, v1, v2, norm;
+  m33 ax;
+  double p;
+  bool det_ok;
+};
+RFX_HD TriSetup tri_setup(v3 v0, v3 v1, v3 v2)
+{
+  TriSetup t;
+  t.v0 = v0; t.v1 = v1; t.v2 = v2;
+  t.norm = normalized(cross(sub(v1, v0), sub(v2, v0)));
+  const m33 basis = from_cols(sub(v2, v0), sub(v1, v0), neg(t.norm));
+  t.ax = inverted(basis);
+  const float a[9] = {basis.m11, basis.m12, basis.m13, basis.m21, basis.m22, basis.m23, basis.m31, basis.m32, basis.m33};
+  const float b[9] = {t.ax.m11, t.ax.m12, t.ax.m13, t.ax.m21, t.ax.m22, t.ax.m23, t.ax.m31, t.ax.m32, t.ax.m33};
+  double na = 0.0, nb = 0.0;
+  for (int k = 0; k < 9; ++k) { na += (double)a[k] * a[k]; nb += (double)b[k] * b[k]; }
+  const float det = basis.m11 * (basis.m22 * basis.m33 - basis.m32 * basis.m23) +
+                    basis.m21 * (basis.m32 * basis.m13 - basis.m12 * basis.m33) +
+                    basis.m31 * (basis.m12 * basis.m23 - basis.m13 * basis.m22);
+  t.p = na * nb;
+  t.det_ok = fabsf(det) > kVerySmall;
+  return t;
+}
+RFX_HD bool tri_well(const TriSetup &t) { return t.det_ok && t.p < kTriCondSq; }
+
+// the geometry words of a tri_geo / tri_leaf record (its padding is the caller's)
+RFX_HD void tri_geo_set(TriGeo &g, const TriSetup &t)
+{
+  g.v0x = t.v0.x; g.v0y = t.v0.y; g.v0z = t.v0.z;
+  g.a11 = t.ax.m11; g.a12 = t.ax.m12; g.a13 = t.ax.m13;
+  g.a21 = t.ax.m21; g.a22 = t.ax.m22; g.a23 = t.ax.m23;
+  g.a31 = t.ax.m31; g.a32 = t.ax.m32; g.a33 = t.ax.m33;
+}
+
+// Bounding sphere of a triangle for the wave-bundle cull: the centroid and the farthest vertex in double; r = +inf for a
+// triangle that is not well-conditioned (never culled)
+RFX_HD Bound tri_bound(v3 v0, v3 v1, v3 v2, bool well)
+{
+  const double cx = ((double)v0.x + v1.x + v2.x) / 3.0, cy = ((double)v0.y + v1.y + v2.y) / 3.0,
+               cz = ((double)v0.z + v1.z + v2.z) / 3.0;
+  const v3 q[3] = {v0, v1, v2};
+  double r2 = 0.0;
+  for (int k = 0; k < 3; ++k)
+    r2 = fmax(r2, (q[k].x - cx) * (q[k].x - cx) + (q[k].y - cy) * (q[k].y - cy) + (q[k].z - cz) * (q[k].z - cz));
+  float r = (float)(sqrt(r2) * 1.0001 + 1e-6);
+  if (!well) r = INFINITY;
+  Bound b;
+  b.x = (float)cx; b.y = (float)cy; b.z = (float)cz; b.r = r;
+  return b;
+}
+
+// Child c of a hierarchy node from the union [l, h] of the unwidened boxes below it (build_pair_bvh).  widen: the box
+// grown by the node part of the kernel's margin, kCullRel mt[c] (rfx_bundle.h kCullRel = 2e-3), from the float mt the
+// kernel would have used, with a relative 1e-6 on top (false: rfx_scene_tri_bvh_dump, the boxes as built).  Then rounded
+// outwards to float; mt[c]: the margin term of the child against the reference point ref (the root box centre), Euclidean
+// |ref - centre|_2 + the half-diagonal (round 3; the L1 form made C5 2.2% slower), rounded up.
+RFX_HD void bvh_child_set(BvhNode &n, int c, const double lo[3], const double hi[3], const double ref[3], bool widen)
+{
+  double l[3] = {lo[0], lo[1], lo[2]}, h[3] = {hi[0], hi[1], hi[2]};
+  if (widen)
+  {
+    double cd = 0.0, hd = 0.0;
+    for (int k = 0; k < 3; ++k)
+    {
+      const double dc = ref[k] - 0.5 * (l[k] + h[k]), dh = 0.5 * (h[k] - l[k]);
+      cd += dc * dc;
+      hd += dh * dh;
+    }
+    const double w = 2e-3 * (double)nextafterf((float)((sqrt(cd) + sqrt(hd)) * 1.0001), INFINITY) * (1.0 + 1e-6);
+    for (int k = 0; k < 3; ++k) { l[k] -= w; h[k] += w; }
+  }
+  n.lx[c] = nextafterf((float)l[0], -INFINITY); n.ly[c] = nextafterf((float)l[1], -INFINITY);
+  n.lz[c] = nextafterf((float)l[2], -INFINITY);
+  n.hx[c] = nextafterf((float)h[0], INFINITY); n.hy[c] = nextafterf((float)h[1], INFINITY);
+  n.hz[c] = nextafterf((float)h[2], INFINITY);
+  double cd = 0.0, hd = 0.0;
+  for (int k = 0; k < 3; ++k)
+  {
+    const double dc = ref[k] - 0.5 * (l[k] + h[k]), dh = 0.5 * (h[k] - l[k]);
+    cd += dc * dc;
+    hd += dh * dh;
+  }
+  const double mt = sqrt(cd) + sqrt(hd);
+  n.mt[c] = nextafterf((float)(mt * 1.0001), INFINITY);
+}
+
+// The all-space child: a refitted child that holds a triangle which is no longer well-conditioned (its hits may lie
+// anywhere, so every ray must reach it).  Its six bounds are NaN (one fixed quiet pattern, set directly, not through the
+// formula), its margin term +inf.  rfx_bvh.h bvh_box then has six NaN slab ends whatever the ray: its fminf / fmaxf leave
+// t0 = 0 (the 0 of the entry clamp) and t1 = NaN, and `t0 > t1 ...` fails in the keeping direction; the walkers'
+// distance prune sees t0 = 0.  Infinite bounds would not do: for an origin and a reciprocal direction whose product
+// overflows (an axis-parallel ray from beyond 3.4e8: the reciprocal is clamped to 1e30) the slab constant is infinite,
+// inf - inf leaves one end of the slab NaN and fminf / fmaxf take the other, -inf, for both -- t1 = -inf culls the box
+// (tests/test_mesh_update_host.py replays both in float32).
+RFX_HD void bvh_child_all_space(BvhNode &n, int c)
+{
+  const float q = u2f(0x7FC00000u);
+  n.lx[c] = n.ly[c] = n.lz[c] = q;
+  n.hx[c] = n.hy[c] = n.hz[c] = q;
+  n.mt[c] = INFINITY;
+}
+
+// An unwidened box of the refit: the exact float min / max of the vertices below it, and whether a triangle below it is
+// not well-conditioned.  fminf / fmaxf drop a NaN vertex (such a triangle raises `ill`, and the box then does not count).
+struct alignas(16) RefitBox { float lo[3], hi[3]; uint32_t ill, pad; };
+RFX_HD void refit_box_empty(RefitBox &b)
+{
+  for (int k = 0; k < 3; ++k) { b.lo[k] = INFINITY; b.hi[k] = -INFINITY; }
+  b.ill = 0; b.pad = 0;
+}
+RFX_HD void refit_box_vertex(RefitBox &b, const float *q)
+{
+  for (int k = 0; k < 3; ++k) { b.lo[k] = fminf(b.lo[k], q[k]); b.hi[k] = fmaxf(b.hi[k], q[k]); }
+}
+RFX_HD void refit_box_join(RefitBox &b, const RefitBox &o)
+{
+  for (int k = 0; k < 3; ++k) { b.lo[k] = fminf(b.lo[k], o.lo[k]); b.hi[k] = fmaxf(b.hi[k], o.hi[k]); }
+  b.ill |= o.ill;
+}
+// child c of node n from the box below it
+RFX_HD void refit_child(BvhNode &n, int c, const RefitBox &b, const double ref[3], bool widen)
+{
+  if (b.ill) { bvh_child_all_space(n, c); return; }
+  const double l[3] = {b.lo[0], b.lo[1], b.lo[2]}, h[3] = {b.hi[0], b.hi[1], b.hi[2]};
+  bvh_child_set(n, c, l, h, ref, widen);
+}
+
+// the per-triangle words rfx_scene_tri_records / rfx_renderer_tri_records report (rfx.h "Moving meshes")
+constexpr int kTriRecordWords = 41;
+
+// One launch of the device update (rfx_update_kernels.hip update_tris_kernel): triangles [first, first + count) take the
+// vertices at pos (idx null: 9 floats per triangle; else 3 indices per triangle into n_pos vertices, a triangle naming
+// an index >= n_pos keeps what it has).  The scene arrays are the uploaded DevScene's, the rest the renderer's own.
+struct UpdateParams {
+  TriGeo *tri_geo;
+  TriShade *tri_shade;
+  Bound *tri_bound;      // DevScene::bound + n_sph
+  TriGeo *tri_leaf;      // null without a tree
+  float *verts;          // 9 floats per triangle: the current vertices
+  uint32_t *ill;         // per triangle: 1 = not well-conditioned
+  const int32_t *slot;   // per triangle: its record in tri_leaf, -1 outside the tree
+  const float *pos;
+  const uint32_t *idx;
+  uint32_t n_pos, first, count;
+};
+// The refit's launches (rfx_update_kernels.hip refit_leaves_kernel, refit_nodes_kernel): the leaves' boxes from the current
+// vertices, then the nodes of one height from the boxes below them -- list[0 .. n) are that height's nodes
+struct RefitParams {
+  BvhNode *nodes;
+  const int32_t *order;  // leaves x RFX_TRI_BVH_LEAF triangle indices, -1 padding
+  const float *verts;
+  const uint32_t *ill;
+  RefitBox *leaf_box, *node_box;
+  const int32_t *list;
+  uint32_t n;            // leaves (refit_leaves_kernel) or nodes of this height (refit_nodes_kernel)
+  double ref[3];         // DevScene::bvh_rx, bvh_ry, bvh_rz
+};
+
+}  // namespace rfx

@@ -17,6 +17,7 @@
 #include <vector>
 
 #include "rfx_math.h"
+#include "rfx_refit.h"
 #include "rfx_scene.h"
 
 #pragma clang fp contract(off)
@@ -116,29 +117,24 @@ extern "C" int rfx_scene_add_sphere(rfx_scene *s, const float c[3], float radius
   return sp.obj;
 }
 
+// Triangle.cpp:11-21 (v0, v1, v2, norm, axTrans) and the builder's condition number of the basis, from the vertices
+static void set_tri_vertices(HostTri &t, const float a[3], const float b[3], const float c[3])
+{
+  const TriSetup u = tri_setup(mk(a[0], a[1], a[2]), mk(b[0], b[1], b[2]), mk(c[0], c[1], c[2]));
+  t.v0 = u.v0; t.v1 = u.v1; t.v2 = u.v2;
+  t.norm = u.norm;
+  t.ax = u.ax;
+  t.cond = u.det_ok ? sqrt(u.p) : INFINITY;
+}
+
 extern "C" int rfx_scene_add_triangle(rfx_scene *s, const float a[3], const float b[3], const float c[3], int type,
                                       const float rgb[3], float refl, float transp)    // Triangle.cpp:11-21
 {
   if (!s || !a || !b || !c || !rgb || (type != RFX_METAL && type != RFX_DIELECTRIC))
     return fail(RFX_ERR_ARG, "add_triangle: bad args");
   HostTri t;
-  const v3 v0 = mk(a[0], a[1], a[2]), v1 = mk(b[0], b[1], b[2]), v2 = mk(c[0], c[1], c[2]);
-  t.v0 = v0;
+  set_tri_vertices(t, a, b, c);
   t.mat = make_mat(type, rgb, refl, transp);
-  t.norm = normalized(cross(sub(v1, v0), sub(v2, v0)));
-  const m33 basis = from_cols(sub(v2, v0), sub(v1, v0), neg(t.norm));
-  t.ax = inverted(basis);
-  t.v1 = v1;
-  t.v2 = v2;
-  {
-    const float *a = &basis.m11, *b = &t.ax.m11;
-    double na = 0.0, nb = 0.0;
-    for (int k = 0; k < 9; ++k) { na += (double)a[k] * a[k]; nb += (double)b[k] * b[k]; }
-    const float det = basis.m11 * (basis.m22 * basis.m33 - basis.m32 * basis.m23) +
-                      basis.m21 * (basis.m32 * basis.m13 - basis.m12 * basis.m33) +
-                      basis.m31 * (basis.m12 * basis.m23 - basis.m13 * basis.m22);
-    t.cond = fabsf(det) > kVerySmall ? sqrt(na * nb) : INFINITY;
-  }
   memset(&t.tuv, 0, sizeof(t.tuv));
   t.obj = (int)s->obj_kind.size();
   s->obj_kind.push_back(1);
@@ -525,40 +521,10 @@ int build_pair_bvh(std::vector<BvhNode> &nodes, std::vector<uint32_t> &pairs, si
     double l[3] = {INFINITY, INFINITY, INFINITY}, h[3] = {-INFINITY, -INFINITY, -INFINITY};
     for (size_t i = range[c][0]; i < range[c][1]; ++i)
       for (int k = 0; k < 3; ++k) { l[k] = fmin(l[k], box[pairs[i]].lo[k]); h[k] = fmax(h[k], box[pairs[i]].hi[k]); }
-    if (widen)  // (false: rfx_scene_tri_bvh_dump, the boxes as built)
-    {
-      // the box grown by the node part of the kernel's margin, kCullRel mt[c] (rfx_bundle.h kCullRel = 2e-3), from the
-      // float mt the kernel would have used, with a relative 1e-6 on top
-      double cd = 0.0, hd = 0.0;
-      for (int k = 0; k < 3; ++k)
-      {
-        const double dc = ref[k] - 0.5 * (l[k] + h[k]), dh = 0.5 * (h[k] - l[k]);
-        cd += dc * dc;
-        hd += dh * dh;
-      }
-      const double w = 2e-3 * (double)nextafterf((float)((sqrt(cd) + sqrt(hd)) * 1.0001), INFINITY) * (1.0 + 1e-6);
-      for (int k = 0; k < 3; ++k) { l[k] -= w; h[k] += w; }
-    }
-    // round outwards to float
-    n.lx[c] = nextafterf((float)l[0], -INFINITY); n.ly[c] = nextafterf((float)l[1], -INFINITY);
-    n.lz[c] = nextafterf((float)l[2], -INFINITY);
-    n.hx[c] = nextafterf((float)h[0], INFINITY); n.hy[c] = nextafterf((float)h[1], INFINITY);
-    n.hz[c] = nextafterf((float)h[2], INFINITY);
+    // widened by the cull margin's node part (widen false: rfx_scene_tri_bvh_dump, the boxes as built), rounded
+    // outwards to float, with the child's margin term: rfx_refit.h, shared with the refits
+    bvh_child_set(n, c, l, h, ref, widen);
     n.child[c] = kids[c];
-    // margin term of the child against the reference point ref (the root box centre), rounded up
-    double mt = 0.0;
-    {
-      // Euclidean: |ref - centre|_2 + the half-diagonal (round 3; the L1 form made C5 2.2% slower)
-      double cd = 0.0, hd = 0.0;
-      for (int k = 0; k < 3; ++k)
-      {
-        const double dc = ref[k] - 0.5 * (l[k] + h[k]), dh = 0.5 * (h[k] - l[k]);
-        cd += dc * dc;
-        hd += dh * dh;
-      }
-      mt = sqrt(cd) + sqrt(hd);
-    }
-    n.mt[c] = nextafterf((float)(mt * 1.0001), INFINITY);
   }
   return id;
 }
@@ -939,14 +905,7 @@ SceneBuild::SceneBuild(const rfx_scene &scene, int tri_accel)
   }
   for (const HostTri &t : s->tris)
   {
-    const double cx = ((double)t.v0.x + t.v1.x + t.v2.x) / 3.0, cy = ((double)t.v0.y + t.v1.y + t.v2.y) / 3.0,
-                 cz = ((double)t.v0.z + t.v1.z + t.v2.z) / 3.0;
-    double r2 = 0.0;
-    for (const v3 &q : {t.v0, t.v1, t.v2})
-      r2 = fmax(r2, (q.x - cx) * (q.x - cx) + (q.y - cy) * (q.y - cy) + (q.z - cz) * (q.z - cz));
-    float r = (float)(sqrt(r2) * 1.0001 + 1e-6);
-    if (!(t.cond < 300.0)) r = INFINITY;
-    bd.push_back({(float)cx, (float)cy, (float)cz, r});
+    bd.push_back(tri_bound(t.v0, t.v1, t.v2, t.cond < 300.0));
   }
   // small-scene lane table (rfx_types.h CullRec)
   uint64_t cull_valid = 0;
@@ -1071,6 +1030,30 @@ SceneBuild::SceneBuild(const rfx_scene &scene, int tri_accel)
       }
     }
   }
+  // the device update's tables (rfx_scene.h)
+  if (!small && !s->tris.empty())
+  {
+    tslot.assign(s->tris.size(), -1);
+    for (size_t q = 0; q < tt.order.size(); ++q)
+      if (tt.order[q] >= 0) tslot[tt.order[q]] = (int32_t)q;
+    for (const HostTri &t : s->tris)
+    {
+      for (const v3 *v : {&t.v0, &t.v1, &t.v2}) { tverts.push_back(v->x); tverts.push_back(v->y); tverts.push_back(v->z); }
+      till.push_back(t.cond < 300.0 ? 0u : 1u);
+    }
+    // children follow their parent in build_pair_bvh's node order, so one backward pass has every child's height
+    std::vector<int> height(tt.nodes.size(), 0);
+    for (size_t i = tt.nodes.size(); i-- > 0;)
+      for (int c = 0; c < 2; ++c)
+        height[i] = std::max(height[i], 1 + (tt.nodes[i].child[c] >= 0 ? height[tt.nodes[i].child[c]] : 0));
+    hoff.assign(1, 0u);
+    for (int h = 1; hlist.size() < tt.nodes.size(); ++h)
+    {
+      for (size_t i = 0; i < tt.nodes.size(); ++i)
+        if (height[i] == h) hlist.push_back((int32_t)i);
+      hoff.push_back((uint32_t)hlist.size());
+    }
+  }
   for (const HostPlane &p : s->planes)
   {
     pg.push_back({p.pos.x, p.pos.y, p.pos.z, p.norm.x, p.norm.y, p.norm.z, p.obj, p.mat.dielectric});
@@ -1166,4 +1149,115 @@ extern "C" int rfx_scene_cull_dump(const rfx_scene *s, float recs[64 * 8], float
   if (tris) memcpy(tris, B.ct.data(), 32 * sizeof(CullTri));
   if (valid) *valid = B.d.cull_valid;
   return RFX_OK;
+}
+
+// ============================================================== moving meshes (host side)
+// rfx.h "Moving meshes".  The device side is rfx_update.cpp / rfx_update_kernels.hip; both take every formula from rfx_refit.h.
+extern "C" int rfx_scene_set_triangle_vertices(rfx_scene *s, uint32_t first, uint32_t count, const float *vertices9)
+{
+  if (!s || !vertices9 || !count || (uint64_t)first + count > s->tris.size())
+    return fail(RFX_ERR_ARG, "scene_set_triangle_vertices: a scene, vertices and a range within its %zu triangles",
+                s ? s->tris.size() : (size_t)0);
+  for (uint32_t i = 0; i < count; ++i)
+  {
+    const float *v = vertices9 + 9 * (size_t)i;
+    set_tri_vertices(s->tris[first + i], v, v + 3, v + 6);
+  }
+  return RFX_OK;
+}
+
+extern "C" int rfx_scene_object_triangle(const rfx_scene *s, int obj)
+{
+  if (!s || obj < 0 || obj >= (int)s->obj_kind.size() || s->obj_kind[obj] != 1)
+    return fail(RFX_ERR_ARG, "scene_object_triangle: object %d is not a triangle", obj);
+  return s->obj_idx[obj];
+}
+
+void rfx::tri_record_words(uint32_t *out, const TriGeo &g, const TriShade &h, const Bound &b, const float *verts9,
+                           bool well, const TriGeo *leaf)
+{
+  static_assert(kTriRecordWords == 41, "record layout");
+  memcpy(out, &g, 48);
+  memcpy(out + 12, &h.nx, 12);
+  memcpy(out + 15, &b, 16);
+  memcpy(out + 19, verts9, 36);
+  out[28] = well ? 1u : 0u;
+  memcpy(out + 29, leaf ? leaf : &g, 48);
+  for (int k = 0; k < kTriRecordWords; ++k)
+    if ((out[k] & 0x7FFFFFFFu) > 0x7F800000u) out[k] = 0x7FC00000u;  // a NaN's sign and payload carry nothing
+}
+
+extern "C" int rfx_scene_tri_records(const rfx_scene *s, uint32_t first, uint32_t count, uint32_t *out)
+{
+  if (!s || !out || !count || (uint64_t)first + count > s->tris.size())
+    return fail(RFX_ERR_ARG, "scene_tri_records: a scene, an output and a range within its %zu triangles",
+                s ? s->tris.size() : (size_t)0);
+  for (uint32_t i = 0; i < count; ++i)
+  {
+    const HostTri &t = s->tris[first + i];
+    const float v[9] = {t.v0.x, t.v0.y, t.v0.z, t.v1.x, t.v1.y, t.v1.z, t.v2.x, t.v2.y, t.v2.z};
+    TriSetup u{};
+    u.v0 = t.v0; u.ax = t.ax;
+    TriGeo g{};
+    tri_geo_set(g, u);
+    TriShade h{};
+    h.nx = t.norm.x; h.ny = t.norm.y; h.nz = t.norm.z;
+    tri_record_words(out + (size_t)kTriRecordWords * i, g, h, tri_bound(t.v0, t.v1, t.v2, t.cond < 300.0), v,
+                     t.cond < 300.0, nullptr);
+  }
+  return RFX_OK;
+}
+
+namespace {
+// the unwidened box below child c of the tree, writing every node's children on the way (rfx_refit.h refit_child)
+RefitBox refit_below(std::vector<BvhNode> &nodes, int c, const std::vector<RefitBox> &leaf, const double *ref, bool widen)
+{
+  if (c < 0) return leaf[~c];
+  RefitBox b;
+  refit_box_empty(b);
+  for (int k = 0; k < 2; ++k)
+  {
+    const RefitBox kid = refit_below(nodes, nodes[c].child[k], leaf, ref, widen);
+    refit_child(nodes[c], k, kid, ref, widen);
+    refit_box_join(b, kid);
+  }
+  return b;
+}
+}  // namespace
+
+extern "C" int rfx_scene_tri_bvh_refit(const rfx_scene *built, const float *vertices9_all, int widen, float *boxes,
+                                       float *mt)
+{
+  if (!built || !vertices9_all || widen < 0 || widen > 1) return fail(RFX_ERR_ARG, "scene_tri_bvh_refit: bad args");
+  if (built->spheres.size() <= 32 && built->tris.size() <= 32) return 0;  // a small scene: no tree
+  SceneBuild B(*built, 1);
+  TriTree &T = B.tt;
+  if (T.nodes.empty()) return 0;
+  const double ref[3] = {B.d.bvh_rx, B.d.bvh_ry, B.d.bvh_rz};
+  std::vector<RefitBox> leaf(T.leaves());
+  for (size_t g = 0; g < leaf.size(); ++g)
+  {
+    refit_box_empty(leaf[g]);
+    for (int e = 0; e < RFX_TRI_BVH_LEAF; ++e)
+    {
+      const int32_t i = T.order[RFX_TRI_BVH_LEAF * g + e];
+      if (i < 0) continue;
+      const float *v = vertices9_all + 9 * (size_t)i;
+      for (int q = 0; q < 3; ++q) refit_box_vertex(leaf[g], v + 3 * q);
+      if (!tri_well(tri_setup(mk(v[0], v[1], v[2]), mk(v[3], v[4], v[5]), mk(v[6], v[7], v[8])))) leaf[g].ill = 1;
+    }
+  }
+  refit_below(T.nodes, 0, leaf, ref, widen != 0);
+  for (size_t i = 0; i < T.nodes.size(); ++i)
+  {
+    const BvhNode &n = T.nodes[i];
+    if (boxes)
+      for (int c = 0; c < 2; ++c)
+      {
+        float *b = boxes + 12 * i + 6 * c;
+        b[0] = n.lx[c]; b[1] = n.ly[c]; b[2] = n.lz[c]; b[3] = n.hx[c]; b[4] = n.hy[c]; b[5] = n.hz[c];
+      }
+    if (mt) { mt[2 * i] = n.mt[0]; mt[2 * i + 1] = n.mt[1]; }
+  }
+  return 1;
 }

@@ -47,6 +47,18 @@ struct SceneBuild {
   DevScene d{};
   rfx_accel_info accel{};
   OrderBox order_box{};                      // the coherent order's key box (rfx.h "Coherent order")
+  // What rfx_renderer_update_triangles keeps beside the scene (rfx_update.cpp; non-small scenes with triangles, else
+  // empty): per triangle its vertices as given (9 floats), its record in tri_leaf (-1: outside the tree) and whether it
+  // is not well-conditioned; the tree's nodes by height (a leaf's is 0), lowest first -- hlist[hoff[h - 1] .. hoff[h])
+  // are the nodes of height h >= 1, each above both its children
+  std::vector<float> tverts;
+  std::vector<int32_t> tslot, hlist;
+  std::vector<uint32_t> till, hoff;
 };
+
+// rfx_scene.cpp, for rfx_update.cpp: one triangle's record words in rfx_scene_tri_records' layout (NaNs canonical)
+// from its geometry records, bound, vertices and class; `leaf`: the tree's copy (null: the triangle's own record)
+void tri_record_words(uint32_t *out, const TriGeo &g, const TriShade &h, const Bound &b, const float *verts9, bool well,
+                      const TriGeo *leaf);
 
 }  // namespace rfx

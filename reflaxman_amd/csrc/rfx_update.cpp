@@ -1,0 +1,167 @@
+// Moving meshes (include/rfx.h "Moving meshes"): rfx_renderer_update_triangles and its host form, the tables set_scene
+// uploads for them, and the read-backs the tests compare with the host mirror (rfx_scene.cpp).  The kernels are
+// rfx_update_kernels.hip; every formula is rfx_refit.h's, shared with the host builder.
+#include <string.h>
+
+#include <vector>
+
+#include "rfx_internal.h"
+
+using namespace rfx;
+
+template <class T>
+static int fill(DevBuf<T> &b, const std::vector<T> &v)
+{
+  if (v.empty()) return RFX_OK;
+  if (b.reserve(v.size()) < 0) return RFX_ERR_HIP;
+  HIP_CHECK(hipMemcpy(b.p, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice));
+  return RFX_OK;
+}
+
+int rfx::upload_update_tables(rfx_renderer *r, const SceneBuild &B)
+{
+  r->upd_tris = 0;
+  r->upd_leaves = (uint32_t)B.tt.leaves();
+  r->upd_hoff = B.hoff;
+  RCHECK(fill(r->upd_verts, B.tverts));
+  RCHECK(fill(r->upd_slot, B.tslot));
+  RCHECK(fill(r->upd_ill, B.till));
+  RCHECK(fill(r->upd_order, B.tt.order));
+  RCHECK(fill(r->upd_hlist, B.hlist));
+  if (r->upd_lbox.reserve(B.tt.leaves()) < 0 || r->upd_nbox.reserve(B.tt.nodes.size()) < 0) return RFX_ERR_HIP;
+  r->upd_tris = (uint32_t)B.tslot.size();  // last: non-zero only with every table in place
+  return RFX_OK;
+}
+
+// the update and the whole tree's refit, enqueued on st
+static int enqueue_update(rfx_renderer *r, uint32_t first, uint32_t count, const float *d_pos, uint32_t n_pos,
+                          const uint32_t *d_idx, hipStream_t st)
+{
+  const DevScene &d = r->dev;
+  UpdateParams U{};
+  U.tri_geo = const_cast<TriGeo *>(d.tri_geo);
+  U.tri_shade = const_cast<TriShade *>(d.tri_shade);
+  U.tri_bound = const_cast<Bound *>(d.bound) + d.n_sph;
+  U.tri_leaf = const_cast<TriGeo *>(d.tri_leaf);
+  U.verts = r->upd_verts;
+  U.ill = r->upd_ill;
+  U.slot = r->upd_slot;
+  U.pos = d_pos;
+  U.idx = d_idx;
+  U.n_pos = n_pos;
+  U.first = first;
+  U.count = count;
+  HIP_CHECK(launch_update_tris(U, st));
+  if (d.tri_bvh)
+  {
+    RefitParams F{};
+    F.nodes = const_cast<BvhNode *>(d.tri_bvh);
+    F.order = r->upd_order;
+    F.verts = r->upd_verts;
+    F.ill = r->upd_ill;
+    F.leaf_box = r->upd_lbox;
+    F.node_box = r->upd_nbox;
+    F.ref[0] = d.bvh_rx; F.ref[1] = d.bvh_ry; F.ref[2] = d.bvh_rz;
+    F.n = r->upd_leaves;
+    HIP_CHECK(launch_refit_leaves(F, st));
+    for (size_t h = 1; h < r->upd_hoff.size(); ++h)
+    {
+      F.list = r->upd_hlist.p + r->upd_hoff[h - 1];
+      F.n = r->upd_hoff[h] - r->upd_hoff[h - 1];
+      HIP_CHECK(launch_refit_nodes(F, st));
+    }
+  }
+  // the per-view masks are the old geometry's (as after set_scene); the streams, tile costs, timing sums, regroup queue
+  // and rewind state are not the update's to touch
+  ++r->scene_gen;
+  r->prim_key.clear();
+  r->prim_seen.clear();
+  return RFX_OK;
+}
+
+static int check_update(rfx_renderer *r, uint32_t first, uint32_t count, const void *pos, uint32_t n_pos,
+                        const void *idx, const char *call)
+{
+  RCHECK(enter_call(r, pos && count && (idx || (uint64_t)n_pos == 3ull * count), call,
+                    "a renderer, positions, count > 0 and, without indices, n_positions == 3 count"));
+  if ((uint64_t)first + count > (uint64_t)r->dev.n_tri)
+    return fail(RFX_ERR_ARG, "%s: triangles [%u, %llu) of %d", call, first, (unsigned long long)first + count, r->dev.n_tri);
+  if (!r->upd_tris)
+    return fail(RFX_ERR_STATE, "%s: a small scene (at most 32 spheres and 32 triangles) is uploaded again with "
+                "rfx_renderer_set_scene", call);
+  return RFX_OK;
+}
+
+extern "C" int rfx_renderer_update_triangles(rfx_renderer *r, uint32_t first, uint32_t count, const float *d_positions,
+                                             uint32_t n_positions, const uint32_t *d_indices, void *stream)
+{
+  RCHECK(check_update(r, first, count, d_positions, n_positions, d_indices, "renderer_update_triangles"));
+  return enqueue_update(r, first, count, d_positions, n_positions, d_indices, stream_or_own(r, stream));
+}
+
+extern "C" int rfx_renderer_update_triangles_host(rfx_renderer *r, uint32_t first, uint32_t count, const float *positions,
+                                                  uint32_t n_positions, const uint32_t *indices)
+{
+  RCHECK(check_update(r, first, count, positions, n_positions, indices, "renderer_update_triangles_host"));
+  const hipStream_t st = r->stream;
+  // (a grown staging array is a new allocation: the stream is idle after every earlier host-form call)
+  if (r->upd_pos.reserve(3 * (size_t)n_positions) < 0 || (indices && r->upd_idx.reserve(3 * (size_t)count) < 0))
+    return RFX_ERR_HIP;
+  HIP_CHECK(hipMemcpyAsync(r->upd_pos.p, positions, 12 * (size_t)n_positions, hipMemcpyHostToDevice, st));
+  if (indices) HIP_CHECK(hipMemcpyAsync(r->upd_idx.p, indices, 12 * (size_t)count, hipMemcpyHostToDevice, st));
+  RCHECK(enqueue_update(r, first, count, r->upd_pos, n_positions, indices ? r->upd_idx.p : nullptr, st));
+  HIP_CHECK(hipStreamSynchronize(st));
+  return RFX_OK;
+}
+
+extern "C" int rfx_renderer_tri_records(rfx_renderer *r, uint32_t first, uint32_t count, uint32_t *out)
+{
+  RCHECK(enter_call(r, out && count, "renderer_tri_records", "a renderer, an output and count > 0"));
+  if ((uint64_t)first + count > (uint64_t)r->dev.n_tri || !r->upd_tris)
+    return fail(RFX_ERR_ARG, "renderer_tri_records: a range within the %d triangles of a scene that is not small",
+                r->dev.n_tri);
+  const DevScene &d = r->dev;
+  HIP_CHECK(hipStreamSynchronize(r->stream));
+  std::vector<TriGeo> g(count), leaf((size_t)r->upd_leaves * RFX_TRI_BVH_LEAF);
+  std::vector<TriShade> h(count);
+  std::vector<Bound> b(count);
+  std::vector<float> v(9 * (size_t)count);
+  std::vector<uint32_t> ill(count);
+  std::vector<int32_t> slot(count);
+  HIP_CHECK(hipMemcpy(g.data(), d.tri_geo + first, count * sizeof(TriGeo), hipMemcpyDeviceToHost));
+  HIP_CHECK(hipMemcpy(h.data(), d.tri_shade + first, count * sizeof(TriShade), hipMemcpyDeviceToHost));
+  HIP_CHECK(hipMemcpy(b.data(), d.bound + d.n_sph + first, count * sizeof(Bound), hipMemcpyDeviceToHost));
+  HIP_CHECK(hipMemcpy(v.data(), r->upd_verts.p + 9 * (size_t)first, 36 * (size_t)count, hipMemcpyDeviceToHost));
+  HIP_CHECK(hipMemcpy(ill.data(), r->upd_ill.p + first, 4 * (size_t)count, hipMemcpyDeviceToHost));
+  HIP_CHECK(hipMemcpy(slot.data(), r->upd_slot.p + first, 4 * (size_t)count, hipMemcpyDeviceToHost));
+  if (d.tri_leaf && !leaf.empty())
+    HIP_CHECK(hipMemcpy(leaf.data(), d.tri_leaf, leaf.size() * sizeof(TriGeo), hipMemcpyDeviceToHost));
+  for (uint32_t i = 0; i < count; ++i)
+    tri_record_words(out + (size_t)kTriRecordWords * i, g[i], h[i], b[i], &v[9 * (size_t)i], ill[i] == 0,
+                     d.tri_leaf && slot[i] >= 0 ? &leaf[slot[i]] : nullptr);
+  return RFX_OK;
+}
+
+extern "C" int rfx_renderer_tri_bvh_nodes(rfx_renderer *r, float *out)
+{
+  RCHECK(enter_call(r, true, "renderer_tri_bvh_nodes", "a renderer"));
+  const int n = r->dev.n_tri_bvh;
+  if (!out || !n || !r->dev.tri_bvh) return n;
+  HIP_CHECK(hipStreamSynchronize(r->stream));
+  std::vector<BvhNode> nodes(n);
+  HIP_CHECK(hipMemcpy(nodes.data(), r->dev.tri_bvh, n * sizeof(BvhNode), hipMemcpyDeviceToHost));
+  static_assert(sizeof(BvhNode) == 16 * sizeof(float), "node layout");
+  for (int i = 0; i < n; ++i)
+  {
+    const BvhNode &q = nodes[i];
+    float *o = out + 16 * (size_t)i;
+    for (int c = 0; c < 2; ++c)
+    {
+      float *b = o + 6 * c;
+      b[0] = q.lx[c]; b[1] = q.ly[c]; b[2] = q.lz[c]; b[3] = q.hx[c]; b[4] = q.hy[c]; b[5] = q.hz[c];
+    }
+    memcpy(o + 12, q.child, 8);
+    o[14] = q.mt[0]; o[15] = q.mt[1];
+  }
+  return n;
+}

@@ -190,6 +190,41 @@ class Scene:
         return {"nodes": nodes, "leaves": leaves, "leaf_size": leaf, "depth": depth, "boxes": boxes,
                 "children": children, "leaf_ids": ids, "residual": res}
 
+    def setTriangleVertices(self, first: int, vertices):
+        """New vertices for triangles [first, first + n) (rfx.h rfx_scene_set_triangle_vertices): (n, 3, 3) floats, each
+        triangle's (v1, v2, v3) as addTriangle takes them.  Materials, textures and uv stay; the next upload of the scene
+        reads them."""
+        v = np.ascontiguousarray(vertices, dtype=np.float32).reshape(-1, 9)
+        check(_lib.load().rfx_scene_set_triangle_vertices(self._h, int(first), v.shape[0], _lib.fptr(v)),
+              "Scene.setTriangleVertices")
+        self._version += 1
+
+    def object_triangle(self, obj: int) -> int:
+        """The triangle index (insertion order among triangles) of object `obj` (rfx.h rfx_scene_object_triangle)."""
+        return check(_lib.load().rfx_scene_object_triangle(self._h, int(obj)), "Scene.object_triangle")
+
+    def tri_records(self, first: int = 0, count: Optional[int] = None) -> np.ndarray:
+        """The words that follow the triangles' vertices (rfx.h rfx_scene_tri_records; host only): (count,
+        RFX_TRI_RECORD_WORDS) uint32."""
+        n = self.counts()[1] - first if count is None else count
+        out = np.zeros((n, _lib.RFX_TRI_RECORD_WORDS), np.uint32)
+        check(_lib.load().rfx_scene_tri_records(self._h, int(first), n, _lib.u32ptr(out)), "Scene.tri_records")
+        return out
+
+    def tri_bvh_refit(self, vertices, widen: bool):
+        """This scene's triangle BVH refitted on the host to `vertices` ((triangles, 3, 3) floats), as the device update
+        refits it (rfx.h rfx_scene_tri_bvh_refit): (boxes (nodes, 2, 6), mt (nodes, 2)), or None without a tree."""
+        d = self.tri_bvh_dump()
+        if d is None:
+            return None
+        v = np.ascontiguousarray(vertices, dtype=np.float32).reshape(-1, 9)
+        if v.shape[0] != self.counts()[1]:
+            raise ValueError("tri_bvh_refit: vertices for every triangle of the scene")
+        boxes, mt = np.zeros((d["nodes"], 2, 6), np.float32), np.zeros((d["nodes"], 2), np.float32)
+        check(_lib.load().rfx_scene_tri_bvh_refit(self._h, _lib.fptr(v), int(bool(widen)), _lib.fptr(boxes),
+                                                  _lib.fptr(mt)), "Scene.tri_bvh_refit")
+        return boxes, mt
+
     def cull_dump(self):
         """The bundle-cull records of a small scene as a renderer would upload them (rfx.h rfx_scene_cull_dump; host
         only): (recs (64, 8), tris (32, 12), valid lanes as an int)."""
@@ -347,6 +382,70 @@ class Renderer:
             check(_lib.load().rfx_renderer_set_scene(self._h, scene._h), "rfx_renderer_set_scene")
             self._scene_key = key
             self._scene_ref = scene
+
+    def update_triangles(self, first: int, positions, indices=None):
+        """New vertices for triangles [first, first + n) of the uploaded scene, on the device (rfx.h "Moving meshes",
+        rfx_renderer_update_triangles): every later launch is the one a renderer gives whose set_scene got the scene
+        built at these vertices.  positions: (n, 3, 3) floats, each triangle's three vertices -- or, with indices (n, 3),
+        a vertex pool (m, 3) the index triples name (a triangle naming an index >= m keeps its vertices).  Torch tensors
+        on this renderer's device are read where they lie, on torch's current stream, with no host sync (trace_rays'
+        conventions); anything else goes through numpy and the host form, which synchronises.  A small scene raises
+        (set_scene uploads it again).  A later set_scene(scene) uploads again: move the Scene too
+        (Scene.setTriangleVertices) if it is to match."""
+        L = _lib.load()
+        try:
+            import torch
+            is_torch = isinstance(positions, torch.Tensor)
+        except ImportError:
+            is_torch = False
+        self._scene_key = None
+        if is_torch:
+            if not positions.is_cuda or positions.device.index != self.device:
+                raise ValueError("update_triangles: tensors on the renderer's device (or numpy arrays) are required")
+            p = positions.to(torch.float32).reshape(-1, 3).contiguous()
+            idx = None
+            if indices is not None:
+                if not (isinstance(indices, torch.Tensor) and indices.is_cuda and indices.device == positions.device):
+                    raise ValueError("update_triangles: indices on the positions' device")
+                # (uint32 words: torch has no unsigned kind on every build; a negative int32 names no vertex either way)
+                idx = indices.to(torch.int32).reshape(-1, 3).contiguous()
+            n = idx.shape[0] if idx is not None else p.shape[0] // 3
+            stream = torch.cuda.current_stream(p.device).cuda_stream
+            if not stream:
+                torch.cuda.current_stream(p.device).synchronize()
+            check(L.rfx_renderer_update_triangles(self._h, int(first), n, C.c_void_p(p.data_ptr()), p.shape[0],
+                                                  C.c_void_p(idx.data_ptr() if idx is not None else None),
+                                                  C.c_void_p(stream or None)), "rfx_renderer_update_triangles")
+            if not stream:
+                self.synchronize()
+            else:
+                self._keep_update = (p, idx)  # the launch reads them after this call returns
+            return
+        p = np.ascontiguousarray(positions, dtype=np.float32).reshape(-1, 3)
+        idx = None if indices is None else np.ascontiguousarray(indices, dtype=np.uint32).reshape(-1, 3)
+        n = idx.shape[0] if idx is not None else p.shape[0] // 3
+        check(L.rfx_renderer_update_triangles_host(self._h, int(first), n, _lib.fptr(p), p.shape[0],
+                                                   _lib.u32ptr(idx) if idx is not None else None),
+              "rfx_renderer_update_triangles_host")
+
+    def tri_records(self, first: int = 0, count: Optional[int] = None) -> np.ndarray:
+        """The uploaded triangles' words that follow their vertices, read back (rfx.h rfx_renderer_tri_records;
+        synchronises): (count, RFX_TRI_RECORD_WORDS) uint32."""
+        n = self._scene_ref.counts()[1] - first if count is None else count
+        out = np.zeros((n, _lib.RFX_TRI_RECORD_WORDS), np.uint32)
+        check(_lib.load().rfx_renderer_tri_records(self._h, int(first), n, _lib.u32ptr(out)), "rfx_renderer_tri_records")
+        return out
+
+    def tri_bvh_nodes(self):
+        """The uploaded triangle BVH read back (rfx.h rfx_renderer_tri_bvh_nodes; synchronises): (boxes (nodes, 2, 6)
+        float32, children (nodes, 2) int32, mt (nodes, 2) float32), or None without a tree."""
+        L = _lib.load()
+        n = check(L.rfx_renderer_tri_bvh_nodes(self._h, None), "rfx_renderer_tri_bvh_nodes")
+        if n == 0:
+            return None
+        out = np.zeros((n, 16), np.float32)
+        check(L.rfx_renderer_tri_bvh_nodes(self._h, _lib.fptr(out)), "rfx_renderer_tri_bvh_nodes")
+        return out[:, :12].reshape(n, 2, 6).copy(), out[:, 12:14].copy().view(np.int32), out[:, 14:16].copy()
 
     def set_rng(self, sphere_seed: int, jitter_seed: int):
         check(_lib.load().rfx_renderer_set_rng(self._h, sphere_seed & 0xFFFFFFFF, jitter_seed & 0xFFFFFFFF), "set_rng")
