@@ -135,6 +135,21 @@ int rfx_scene_tri_mates(const rfx_scene *scene, int32_t *leader, float *plane);
  * scene's launches take the far-light kernels under its current setting, 0 when not, < 0 on error. */
 int rfx_scene_set_far_lights(rfx_scene *scene, int mode);
 int rfx_scene_far_light(const rfx_scene *scene, int light, float terms[8]);
+/* A far light's occluder grid (host only; DESIGN.md "Shadow grid").  For a small scene (at most 32 spheres and 32
+ * triangles) with exactly one light, which is far, the builder cuts a world-axis box around the spheres and triangles
+ * into at most 2^16 cubic cells and keeps per cell a 64-bit mask, in rfx_scene_cull_dump's lane layout, of the objects a
+ * shadow ray toward the light may be reported to hit from any origin in the cell: the bundle cull's own verdict for the
+ * cell's circumscribed ball and the light's cone.  The far-light kernels OR the masks of a wave's hits instead of culling
+ * the wave's own shadow bundle, wherever every such hit lies inside the light's bound and the box (the same pixels).
+ * rfx_scene_set_shadow_grid (read by the next rfx_renderer_set_scene; a new scene takes RFX_SHADOW_GRID = 0, 1 or 2
+ * from the environment where set): 0 no grid; 1 (the default) where the scene's launches take the far-light kernels
+ * (rfx_scene_far_light returns 1); 2 for any small scene with one far light.
+ * rfx_scene_shadow_grid returns the number of cells the current setting builds (0: no grid), < 0 on error, and writes,
+ * where given, geom[6] = {box corner x y z, 1 / cell size, cell size, radius of the ball a cell's mask is made for
+ * about the cell's centre corner + (i + 1/2) size}, dims[3] = {nx, ny, nz} and the masks, cell (ix, iy, iz) at
+ * (iz ny + iy) nx + ix; capacity: the masks the caller has room for (RFX_ERR_ARG if fewer than the grid's). */
+int rfx_scene_set_shadow_grid(rfx_scene *scene, int mode);
+int rfx_scene_shadow_grid(const rfx_scene *scene, float geom[6], int32_t dims[3], uint64_t *masks, uint64_t capacity);
 
 /* ---------------------------------------------------------------- Camera */
 /* Camera(eye, at, fov): view = [ox | oy | oz] columns, row-major _11.._33 -- Camera.cpp:24-38 */

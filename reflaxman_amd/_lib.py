@@ -93,6 +93,8 @@ SIGNATURES = [
     ("rfx_scene_set_tri_mates", C.c_int, [C.c_void_p, C.c_int]),
     ("rfx_scene_tri_mates", C.c_int, [C.c_void_p, _i32p, _fp]),
     ("rfx_scene_set_far_lights", C.c_int, [C.c_void_p, C.c_int]),
+    ("rfx_scene_set_shadow_grid", C.c_int, [C.c_void_p, C.c_int]),
+    ("rfx_scene_shadow_grid", C.c_int, [C.c_void_p, _fp, _i32p, _u64p, C.c_uint64]),
     ("rfx_scene_far_light", C.c_int, [C.c_void_p, C.c_int, _fp]),
     ("rfx_scene_add_plane", C.c_int, [C.c_void_p, _fp, _fp, C.c_int, _fp, C.c_float, C.c_float]),
     ("rfx_scene_plane_count", C.c_int, [C.c_void_p]),

@@ -9,6 +9,7 @@
 #include <cstddef>
 #include <type_traits>
 
+#include "rfx_cull_rule.h"
 #include "rfx_math.h"
 #include "rfx_types.h"
 #include "rfx_shade_inputs.h"
@@ -130,13 +131,35 @@ __device__ __forceinline__ LightRec reread_light(const LightRec *l, uint64_t whe
   return *(const LightRec *)p;
 }
 
+// The far light's occluder grid (rfx_types.h ShadowGrid, the DevScene's last member) read from the kernarg segment where
+// the shadow pass uses it, as reread_light reads the light: its twelve dwords are not held in SGPRs across the closest
+// hit, and the asm is not volatile.  Every kernel that reaches the grid path takes the DevScene at kernarg offset 0
+// (kKernargSig).
+__device__ __forceinline__ ShadowGrid reread_grid(uint64_t when)
+{
+  typedef const __attribute__((address_space(4))) char *KP;
+  KP p = (KP)__builtin_amdgcn_kernarg_segment_ptr();
+  asm("" : "+s"(p) : "s"(when));
+  return *(const ShadowGrid *)(const __attribute__((address_space(4))) ShadowGrid *)(p + offsetof(DevScene, shadow_grid));
+}
+
 // FARL (with ONEL, SMALL and CULL, never STATS; RFX_FAR_LIGHT picks the halves): the scene's one light is far
 // (rfx_scene.cpp far_light_terms), so where a hit lies inside its bound the terms of the light that do not depend on the
 // hit -- dtl, its length and direction, ang > 0 and 1 - sqrt(ang) -- are read from the record, and a wave whose facing
 // hits all lie inside takes the shadow bundle's cone from it too (make_bundle_far).  Every other hit, and every other
 // instantiation, runs the expressions below as they stand.
+// GRID (FARL kernels that take the cone, RFX_SHADOW_GRID): where the scene carries the light's occluder grid and every
+// facing hit of the wave lies inside both the light's bound and the grid's box, the shadow mask is the OR of the facing
+// lanes' cell masks instead of a cull of the wave's bundle: a cell's mask is cull_small's verdict, made on the host, for
+// the bundle of every shadow ray that starts in the cell, and a lane's ray is one of them (DESIGN.md "Shadow grid").  One
+// ballot decides for the wave; a wave with a facing hit outside takes the bundle path unchanged.  Each hit lane loads
+// its cell's mask as soon as drop is known (RFX_SHADOW_GRID 2: the facing lanes, once the wave has chosen the grid).
+// SGRID false: a far-light kernel without the grid path -- the SSAA families, whose waves hold the samples of one or a
+// few pixels: their hits stay so close together that the wave's own bundle culls tighter than a cell's ball, and the
+// 4 x 4 screenshot traced 1.2% slower with the grid; and the parking form, which spilled one VGPR more with it
+// (DESIGN.md "Shadow grid").
 template <bool STATS, bool CULL, bool MANYL, bool SMALL, bool PLANES, bool PARK, class PK, bool ONEL = false,
-          bool TBVH = false, bool FARL = false>
+          bool TBVH = false, bool FARL = false, bool SGRID = FARL>
 __device__ __forceinline__ col trace_from(const DevScene &RFX_SCENE_PARAM, v3 origin, v3 ray, col mulc, col pix, int refl,
                                           int depth, v3 rd, const float *lut, Cnt &cnt, bool valid, const PK &park,
                                           bool &parked, const uint64_t *pm_tile = nullptr, bool pm_shadow = true)
@@ -147,6 +170,8 @@ __device__ __forceinline__ col trace_from(const DevScene &RFX_SCENE_PARAM, v3 or
   static_assert(!FARL || (ONEL && SMALL && CULL && !MANYL && !STATS), "FARL: the small-scene one-light culling kernels");
   constexpr bool FAR_SHADE = FARL && (RFX_FAR_LIGHT == 1 || RFX_FAR_LIGHT == 2);
   constexpr bool FAR_CONE = FARL && (RFX_FAR_LIGHT == 1 || RFX_FAR_LIGHT == 3);
+  constexpr bool GRID = FAR_CONE && SGRID && RFX_SHADOW_GRID != 0;
+  constexpr bool GRID_EARLY = GRID && RFX_SHADOW_GRID != 2;
   // the first segment of a plain small-scene trace: this tile's per-view masks (prim_cull_kernel) -- the closest
   // hit's, then one per light for its shadow rays
   bool seg0 = pm_tile != nullptr;
@@ -238,6 +263,20 @@ __device__ __forceinline__ col trace_from(const DevScene &RFX_SCENE_PARAM, v3 or
         const LightRec L = S.lights[base + q];
         bool facing = false;
         v3 sray = mk(0.0f, 0.0f, 0.0f);
+        // the grid: this lane's cell and, loaded ahead of the facing test, its mask (not where the per-view masks serve)
+        ShadowGrid G{};
+        bool in_grid = false;
+        int32_t cell = 0;
+        uint64_t cell_mask = 0;
+        if constexpr (GRID)
+        {
+          G = reread_grid(__ballot(hit));
+          // no lane is in the grid where there is none, or where the per-view masks serve this segment; the wave's
+          // choice below is then one ballot over its facing lanes and reads nothing else
+          in_grid = shadow_grid_cell(G, drop.x, drop.y, drop.z, &cell) & hit & (G.cells != nullptr) & !(seg0 && pm_shadow);
+          if constexpr (GRID_EARLY)
+            if (in_grid) cell_mask = G.cells[cell];
+        }
         if (hit)
         {
           RFX_CNT(C_L_EVAL);
@@ -258,6 +297,13 @@ __device__ __forceinline__ col trace_from(const DevScene &RFX_SCENE_PARAM, v3 or
             {
               if (!MANYL && seg0 && pm_shadow && q < kPrimLights)
                 om = pm_tile[1 + q];  // the primary hits' shadow mask for light q, precomputed for the view
+              else if (GRID && __ballot(facing & !(in_grid & near_light(L, drop))) == 0)
+              {
+                if constexpr (!GRID_EARLY)
+                  if (facing) cell_mask = G.cells[cell];
+                om = wave_or(facing ? cell_mask : 0ull) & S.cull_valid;
+                RFX_CULL_STAT(1, true, __ballot(facing), om, S.cull_valid);
+              }
               else
               {
                 Bundle SB;
@@ -466,12 +512,12 @@ __device__ __forceinline__ col trace_from(const DevScene &RFX_SCENE_PARAM, v3 or
 }
 
 template <bool STATS, bool CULL, bool MANYL, bool SMALL, bool PLANES, bool ONEL = false, bool TBVH = false,
-          bool FARL = false>
+          bool FARL = false, bool SGRID = FARL>
 __device__ __forceinline__ col trace(const DevScene &S, v3 origin, v3 ray, int depth, v3 rd, const float *lut,
                                      Cnt &cnt, bool valid, const uint64_t *pm_tile = nullptr, bool pm_shadow = true)
 {
   bool parked;
-  return trace_from<STATS, CULL, MANYL, SMALL, PLANES, false, Park, ONEL, TBVH, FARL>(S, origin, ray, mkc(1.0f, 1.0f, 1.0f), mkc(0.0f, 0.0f, 0.0f), 0,
+  return trace_from<STATS, CULL, MANYL, SMALL, PLANES, false, Park, ONEL, TBVH, FARL, SGRID>(S, origin, ray, mkc(1.0f, 1.0f, 1.0f), mkc(0.0f, 0.0f, 0.0f), 0,
                                                        depth, rd, lut, cnt, valid, Park{0, nullptr, nullptr, 0, 0},
                                                        parked, pm_tile, pm_shadow);
 }

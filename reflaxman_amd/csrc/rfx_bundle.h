@@ -1,34 +1,18 @@
 // rfx_bundle.h -- the wave's live rays as one cone (Bundle: make_bundle, make_bundle_ball for a light's shadow rays,
 // make_bundle_quad for a pixel's sample rectangle) and the exact culls against it: cull_chunk (64 bounding spheres, a
 // lane each), cull_small (a small scene's lane-layout records, optionally with the triangle footprint test), and the
-// mask helpers all_bits / pair_bits.  kCullRel, the margin every cull and the BVH boxes share, is defined here.
+// mask helpers all_bits / pair_bits.  The Bundle, kCullRel -- the margin every cull and the BVH boxes share -- and the
+// verdict on one lane record come from rfx_cull_rule.h, which the host includes too.  wave_or: a mask ORed over the wave.
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include "rfx_cull_rule.h"
 #include "rfx_math.h"
 #include "rfx_types.h"
 
 #pragma clang fp contract(off)
 
 namespace rfx {
-
-// ------------------------------------------------------------- wave ray bundles (exact culling)
-// The live rays of a wave form a bundle: origins within rw of (cx, cy, cz) -- the first live lane's
-// origin -- and directions within the half-angle acos(cosa) of that lane's direction (ax, ay, az).
-// A ray the reference's float test reports as hitting a sphere passes within r + 1.25e-3 |o - c| of the
-// centre (rounding of d = b^2 - 4ac is at most 104 u a |vco|^2, DESIGN.md "Exact work skipping"; observed worst
-// 7.6e-5, tests/test_cull_bound.py); kCullRel = 2e-3 covers the bound 1.6 times (round 2 used 4e-3: C5 trace -7%
-// with 2e-3, tools/ab.py), so an object whose bounding sphere, grown by rw and kCullRel (L + rw), lies outside the bundle's cone
-// is missed by every lane of the wave and its exact test is skipped for the whole wave.  Skipping a test
-// that misses changes no result: the closest hit and the any-hit only ever take hits.  Every cull
-// decision is a conjunction of comparisons, so a NaN anywhere keeps the object.
-constexpr float kCullRel = 2e-3f;
-
-struct Bundle {
-  float cx, cy, cz, rw;
-  float ax, ay, az, cosa, sina;
-  bool ok;  // wave-uniform: the bound is finite and the cone narrower than ~84 degrees
-};
 
 __device__ __forceinline__ float lane_bcast(float v, int lane)
 {
@@ -51,15 +35,21 @@ __device__ __forceinline__ float wave_max_nonneg(float v)
   return __int_as_float(__builtin_amdgcn_readlane((int)u, 63));
 }
 
-// Sums of products in the bundle and cull bounds (RFX_CULL_FMA): these are conservative decisions with margins far above
-// a rounding, not reference values, so they may fuse their multiply-adds.
-__device__ __forceinline__ float cdot(float ax, float ay, float az, float bx, float by, float bz)
+// OR over the wave of a 64-bit mask (every lane active): wave_max_nonneg's DPP chain on each half, lanes a shift leaves
+// without a source contribute 0.
+__device__ __forceinline__ uint32_t wave_or32(uint32_t u)
 {
-#if RFX_CULL_FMA
-  return __builtin_fmaf(az, bz, __builtin_fmaf(ay, by, ax * bx));
-#else
-  return ax * bx + ay * by + az * bz;
-#endif
+  u |= (uint32_t)__builtin_amdgcn_update_dpp(0, (int)u, 0x111, 0xf, 0xf, false);  // row_shr:1
+  u |= (uint32_t)__builtin_amdgcn_update_dpp(0, (int)u, 0x112, 0xf, 0xf, false);  // row_shr:2
+  u |= (uint32_t)__builtin_amdgcn_update_dpp(0, (int)u, 0x114, 0xf, 0xf, false);  // row_shr:4
+  u |= (uint32_t)__builtin_amdgcn_update_dpp(0, (int)u, 0x118, 0xf, 0xf, false);  // row_shr:8
+  u |= (uint32_t)__builtin_amdgcn_update_dpp(0, (int)u, 0x142, 0xa, 0xf, false);  // row_bcast:15
+  u |= (uint32_t)__builtin_amdgcn_update_dpp(0, (int)u, 0x143, 0xc, 0xf, false);  // row_bcast:31
+  return (uint32_t)__builtin_amdgcn_readlane((int)u, 63);
+}
+__device__ __forceinline__ uint64_t wave_or(uint64_t m)
+{
+  return (uint64_t)wave_or32((uint32_t)(m >> 32)) << 32 | wave_or32((uint32_t)m);
 }
 
 // Bundle of the rays (o, d) of the `live` lanes.  Call with every lane of the wave active and at least
@@ -234,37 +224,17 @@ __device__ __forceinline__ bool tri_footprint_misses(const CullTri &q, float sid
          u0 + v0 - R * q.nuv - m * (q.nu + q.nv) > 1.0f;
 }
 
-// Small scenes: lane l tests cull record l (rfx_types.h CullRec) -- the cone test of cull_chunk, and
-// for a triangle also its plane: when every origin lies more than rw (plus a margin) on one side and
-// every direction leaves that side (axis . n beyond sin of the cone's half-angle, plus a margin), every
-// ray has t <= 0 for the plane.  The reference's float test then sees -ao.z and ar.z of opposite signs too: for a
-// basis with cond <= 1000 their rounding error stays below 2e-4 of |o - v0| and |ray|, inside the 1e-3 margins (measured
-// with the record's own rounding: tests/test_bundle_cull_bound.py).  FOOT (the primary masks only): the footprint test above.
+// Small scenes: lane l tests cull record l (rfx_types.h CullRec) by rfx_cull_rule.h cull_record -- the cone test of
+// cull_chunk, and for a triangle also its plane.  FOOT (the primary masks only): the footprint test above.
 // Bits of lanes without an object are cleared.
 template <bool FOOT = false>
 __device__ __forceinline__ uint64_t cull_small(const CullRec *tab, uint64_t valid, const Bundle &B,
                                                const CullTri *ttab = nullptr)
 {
-  const CullRec g = tab[threadIdx.x & 63u];
-  const float vx = g.x - B.cx, vy = g.y - B.cy, vz = g.z - B.cz;
-  const float L2 = cdot(vx, vy, vz, vx, vy, vz);
-  const float L = __builtin_amdgcn_sqrtf(L2);
-#if RFX_CULL_FMA
-  const float rp = __builtin_fmaf(kCullRel, L + B.rw, g.r + B.rw);
-  const float va = cdot(vx, vy, vz, B.ax, B.ay, B.az);
-  const float lim = __builtin_fmaf(B.cosa, __builtin_amdgcn_sqrtf(fmaxf(__builtin_fmaf(-rp, rp, L2), 0.0f)), -(B.sina * rp));
-#else
-  const float rp = g.r + B.rw + kCullRel * (L + B.rw);
-  const float va = cdot(vx, vy, vz, B.ax, B.ay, B.az);
-  const float lim = B.cosa * __builtin_amdgcn_sqrtf(fmaxf(L2 - rp * rp, 0.0f)) - B.sina * rp;
-#endif
-  const float side = cdot(g.nx, g.ny, g.nz, B.cx, B.cy, B.cz) - g.d;
-  const float an = cdot(g.nx, g.ny, g.nz, B.ax, B.ay, B.az);
-  const float ms = B.rw + 1e-3f * (L + g.r + B.rw) + 1e-6f, ma = B.sina + 1e-3f;
-  const bool away = (side > ms && an > ma) || (side < -ms && an < -ma);
-  bool keep = !(L > rp && va < lim) && !away;
+  const CullVerdict v = cull_record(tab[threadIdx.x & 63u], B);
+  bool keep = v.keep;
   if constexpr (FOOT)
-    if ((threadIdx.x & 63u) >= 32u && keep) keep = !tri_footprint_misses(ttab[(threadIdx.x & 63u) - 32u], side, an, B);
+    if ((threadIdx.x & 63u) >= 32u && keep) keep = !tri_footprint_misses(ttab[(threadIdx.x & 63u) - 32u], v.side, v.an, B);
   return __ballot(keep) & valid;
 }
 

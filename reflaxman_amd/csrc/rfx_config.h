@@ -47,6 +47,12 @@
 #ifndef RFX_FAR_LIGHT
 #define RFX_FAR_LIGHT 1  // a far light's constant terms from its record: 0 never, 2 the shading terms only, 3 the shadow cone only (DESIGN.md "Far lights")
 #endif
+#ifndef RFX_SHADOW_GRID
+#define RFX_SHADOW_GRID 1  // a far light's per-cell occluder masks: 0 no grid is built and the kernels carry no grid path, 2 the mask load after the facing test (DESIGN.md "Shadow grid")
+#endif
+#ifndef RFX_SHADOW_GRID_CELLS
+#define RFX_SHADOW_GRID_CELLS (1 << 16)  // the grid's cell budget, 8 bytes a cell: (1 << 14) or (1 << 18) (DESIGN.md "Shadow grid")
+#endif
 #ifndef RFX_CULL_FMA
 #define RFX_CULL_FMA 1  // 0: the bundle and cull bounds without fused multiply-adds (DESIGN.md "Large scenes", fused cull bounds)
 #endif

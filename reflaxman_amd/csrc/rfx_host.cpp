@@ -297,7 +297,8 @@ extern "C" int rfx_renderer_set_scene(rfx_renderer *r, const rfx_scene *s)
       (rc = upload(r, B.ct, &d.cull_tri)) || (rc = upload(r, B.cb, &d.chunk_bound)) || (rc = upload(r, B.pg, &d.pln_geo)) ||
       (rc = upload(r, B.pm, &d.pln_mat)) || (rc = upload(r, B.loc, &d.obj_loc)) || (rc = upload(r, B.bvh, &d.bvh)) ||
       (rc = upload(r, B.tt.nodes, &d.tri_bvh)) || (rc = upload(r, B.tleaf, &d.tri_leaf)) ||
-      (rc = upload(r, B.tt.resid, &d.tri_resid)) || (rc = upload(r, B.aux, &d.bvh_aux)))
+      (rc = upload(r, B.tt.resid, &d.tri_resid)) || (rc = upload(r, B.aux, &d.bvh_aux)) ||
+      (rc = upload(r, B.gm, &d.shadow_grid.cells)))
     return rc;
   r->dev = d;
   if ((rc = upload_update_tables(r, B)) != RFX_OK) return rc;

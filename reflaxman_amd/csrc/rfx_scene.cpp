@@ -16,6 +16,7 @@
 #include <string>
 #include <vector>
 
+#include "rfx_cull_rule.h"
 #include "rfx_math.h"
 #include "rfx_refit.h"
 #include "rfx_scene.h"
@@ -64,6 +65,7 @@ struct rfx_scene {
   int skybox = -1;
   int tri_mates = 1;  // rfx_scene_set_tri_mates
   int far_lights = 1;  // rfx_scene_set_far_lights
+  int shadow_grid = 1;  // rfx_scene_set_shadow_grid (rfx_scene_create: RFX_SHADOW_GRID in the environment)
   std::vector<HostSphere> spheres;
   std::vector<HostTri> tris;
   std::vector<HostPlane> planes;
@@ -85,6 +87,9 @@ extern "C" rfx_scene *rfx_scene_create(float dr, float dg, float db, float dp)  
   s->diff_power = dp;
   s->env = cscale(s->diff, dp);
   default_half_tiles(s);
+  // A/B runs of one build: RFX_SHADOW_GRID=0, 1 or 2 in the environment is a new scene's rfx_scene_set_shadow_grid mode
+  if (const char *v = getenv("RFX_SHADOW_GRID"))
+    if ((v[0] == '0' || v[0] == '1' || v[0] == '2') && !v[1]) s->shadow_grid = v[0] - '0';
   return s;
 }
 
@@ -785,6 +790,142 @@ extern "C" int rfx_scene_far_light(const rfx_scene *s, int light, float terms[8]
   return far_light_scene(*s, rec) ? 1 : 0;
 }
 
+// ============================================================== a far light's occluder grid
+// DESIGN.md "Shadow grid".  The shadow rays toward a far light are nearly parallel over the whole scene, so which objects
+// one of them can meet depends almost only on where it starts.  The grid cuts a box around the scene into cubic cells
+// and keeps, per cell, cull_small's verdict (rfx_cull_rule.h cull_record, the kernels' own rule) for the bundle of
+// every shadow ray that starts inside the cell: origins within the cell's circumscribed ball, directions in the light's
+// cone (LightRec cone_cos / cone_sin, which hold L + rd radius for every |rd| <= 1 and every hit inside the light's
+// bound).  A wave whose facing hits all lie inside the bound and the box ORs its lanes' cell masks instead of culling
+// its own bundle (rfx_bounce.h GRID).
+//   box    every sphere's box and every triangle vertex, grown on every side by kGridBoxMargin of its longest edge (hits
+//          lie on the objects up to rounding; a hit outside the box only sends its wave down the bundle path)
+//   cells  the smallest size that keeps nx ny nz at or under RFX_SHADOW_GRID_CELLS, found by bisection and rounded up
+//   ball   centre lo + (i + 1/2) size rounded to float, radius the half-diagonal (sqrt(3) / 2) size widened by a relative
+//          1e-6 nmax + 1e-5 and by 2.5e-7 of the box's largest |coordinate|: the kernels find a point's cell in float32 --
+//          (p - lo) * (1 / size), three roundings, at most 2^-22 n cells off on an axis of n cells, i.e. 4.8e-7 n of the
+//          half size -- and the centre's own rounding is at most 2^-24 of a coordinate per axis
+// The grid is built when the scene is small, has exactly one light, that light is far, RFX_SHADOW_GRID is not 0 and:
+// mode 1, the scene's launches take the far-light kernels (far_light_scene); mode 2, always.
+constexpr double kGridBoxMargin = 1.0 / 1024.0;
+
+static bool shadow_grid_scene(const rfx_scene &s, const LightRec &rec, bool small)
+{
+  if (!RFX_SHADOW_GRID || s.shadow_grid == 0 || !small || s.lights.size() != 1 || !(rec.near > 0.0f)) return false;
+  return s.shadow_grid == 2 || far_light_scene(s, rec);
+}
+
+static void shadow_grid_build(const rfx_scene &s, const LightRec &light, SceneBuild &B)
+{
+  double lo[3] = {INFINITY, INFINITY, INFINITY}, hi[3] = {-INFINITY, -INFINITY, -INFINITY};
+  const auto take = [&](int a, double l, double h) { lo[a] = fmin(lo[a], l); hi[a] = fmax(hi[a], h); };
+  for (const HostSphere &h : s.spheres)
+  {
+    const double c[3] = {h.center.x, h.center.y, h.center.z};
+    for (int a = 0; a < 3; ++a) take(a, c[a] - h.radius, c[a] + h.radius);
+  }
+  for (const HostTri &t : s.tris)
+    for (const v3 *v : {&t.v0, &t.v1, &t.v2}) { take(0, v->x, v->x); take(1, v->y, v->y); take(2, v->z, v->z); }
+  double edge = 0.0;
+  for (int a = 0; a < 3; ++a)
+  {
+    if (!std::isfinite(lo[a]) || !std::isfinite(hi[a])) return;  // no object, or a NaN or infinite one
+    edge = fmax(edge, hi[a] - lo[a]);
+  }
+  if (!(edge > 0.0) || !(edge < 1.0e30)) return;
+  float flo[3];
+  double ext[3], cmax = 0.0;
+  for (int a = 0; a < 3; ++a)
+  {
+    flo[a] = (float)(lo[a] - kGridBoxMargin * edge);
+    if ((double)flo[a] > lo[a] - kGridBoxMargin * edge) flo[a] = nextafterf(flo[a], -INFINITY);
+    ext[a] = hi[a] + kGridBoxMargin * edge - (double)flo[a];
+  }
+  const auto cells = [&](double size, int32_t n[3]) {
+    double total = 1.0;
+    for (int a = 0; a < 3; ++a)
+    {
+      const double c = fmax(1.0, ceil(ext[a] / size));
+      n[a] = c < 1.0e9 ? (int32_t)c : 1000000000;
+      total *= c;
+    }
+    return total;
+  };
+  const double budget = (double)RFX_SHADOW_GRID_CELLS;
+  int32_t n[3];
+  double fits = fmax(ext[0], fmax(ext[1], ext[2])), over = cbrt(ext[0] * ext[1] * ext[2] / budget) * 0.5;
+  if (cells(over, n) <= budget) fits = over;  // (cannot be: nx ny nz >= volume / size^3)
+  else
+    for (int it = 0; it < 60; ++it)
+    {
+      const double mid = 0.5 * (fits + over);
+      (cells(mid, n) <= budget ? fits : over) = mid;
+    }
+  float size = (float)fits;
+  if ((double)size < fits) size = nextafterf(size, INFINITY);
+  while (cells((double)size, n) > budget) size = nextafterf(size * 1.000001f, INFINITY);
+  const float scale = 1.0f / size;
+  if (!(size > 0.0f) || !std::isfinite(size) || !std::isfinite(scale) || !(scale > 0.0f)) return;
+  for (int a = 0; a < 3; ++a) cmax = fmax(cmax, fmax(fabs((double)flo[a]), fabs((double)flo[a] + (double)n[a] * size)));
+  const int32_t nmax = std::max(n[0], std::max(n[1], n[2]));
+  const double ball = 0.5 * sqrt(3.0) * (double)size * (1.0 + 1.0e-6 * nmax + 1.0e-5) + 2.5e-7 * cmax;
+  float rw = (float)ball;
+  if ((double)rw < ball) rw = nextafterf(rw, INFINITY);
+  Bundle cone{};
+  cone.rw = rw;
+  cone.ax = light.ndx; cone.ay = light.ndy; cone.az = light.ndz;
+  cone.cosa = light.cone_cos; cone.sina = light.cone_sin;
+  cone.ok = true;
+  std::vector<int> lanes;
+  for (int l = 0; l < 64; ++l)
+    if ((B.d.cull_valid >> l) & 1u) lanes.push_back(l);
+  B.gm.assign((size_t)n[0] * n[1] * n[2], 0ull);
+  size_t k = 0;
+  for (int32_t iz = 0; iz < n[2]; ++iz)
+    for (int32_t iy = 0; iy < n[1]; ++iy)
+      for (int32_t ix = 0; ix < n[0]; ++ix, ++k)
+      {
+        cone.cx = (float)((double)flo[0] + (ix + 0.5) * (double)size);
+        cone.cy = (float)((double)flo[1] + (iy + 0.5) * (double)size);
+        cone.cz = (float)((double)flo[2] + (iz + 0.5) * (double)size);
+        uint64_t m = 0;
+        for (int l : lanes)
+          if (cull_record(B.cs[l], cone).keep) m |= 1ull << l;
+        B.gm[k] = m;
+      }
+  ShadowGrid &g = B.d.shadow_grid;
+  g.ox = flo[0]; g.oy = flo[1]; g.oz = flo[2];
+  g.scale = scale;
+  g.nx = n[0]; g.ny = n[1]; g.nz = n[2];
+  g.fnx = (float)n[0]; g.fny = (float)n[1]; g.fnz = (float)n[2];
+  B.grid_cell = size;
+  B.grid_ball = rw;
+}
+
+extern "C" int rfx_scene_set_shadow_grid(rfx_scene *s, int mode)
+{
+  if (!s || mode < 0 || mode > 2) return fail(RFX_ERR_ARG, "scene_set_shadow_grid: 0 (off), 1 (auto) or 2 (any far light)");
+  s->shadow_grid = mode;
+  return RFX_OK;
+}
+
+extern "C" int rfx_scene_shadow_grid(const rfx_scene *s, float geom[6], int32_t dims[3], uint64_t *masks, uint64_t capacity)
+{
+  if (!s) return fail(RFX_ERR_ARG, "scene_shadow_grid: no scene");
+  const SceneBuild B(*s, 0);
+  const ShadowGrid &g = B.d.shadow_grid;
+  if (geom)
+    for (float f : {g.ox, g.oy, g.oz, g.scale, B.grid_cell, B.grid_ball}) *geom++ = f;
+  if (dims)
+    for (int32_t v : {g.nx, g.ny, g.nz}) *dims++ = v;
+  if (masks)
+  {
+    if (capacity < B.gm.size()) return fail(RFX_ERR_ARG, "scene_shadow_grid: room for %zu masks needed", B.gm.size());
+    if (!B.gm.empty()) memcpy(masks, B.gm.data(), B.gm.size() * sizeof(uint64_t));
+  }
+  return (int)B.gm.size();
+}
+
 // ============================================================== the device form of a scene
 // The coherent order's key box (rfx.h "Coherent order"): float32 throughout, objects in insertion order, a NaN never
 // taken; planes are unbounded and do not count
@@ -1134,6 +1275,7 @@ SceneBuild::SceneBuild(const rfx_scene &scene, int tri_accel)
   d.env_r = s->env.r; d.env_g = s->env.g; d.env_b = s->env.b;
   d.half_tile_w = s->half_tile_w;
   d.half_tile_h = s->half_tile_h;
+  if (!lr.empty() && shadow_grid_scene(*s, lr[0], small)) shadow_grid_build(*s, lr[0], *this);
 }
 
 // The small-scene cull records as SceneBuild makes them (host only, for the tests of the bundle culls): the 64 lane

@@ -38,6 +38,8 @@ struct SceneBuild {
   std::vector<Bound> bd, cb;                 // bound, chunk_bound
   std::vector<CullRec> cs;                   // cull_small
   std::vector<CullTri> ct;                   // cull_tri
+  std::vector<uint64_t> gm;                  // shadow_grid.cells (empty: no grid; its other fields are set in d)
+  float grid_cell = 0, grid_ball = 0;        // the grid's cell size and the radius of a cell's widened ball (for the dump)
   std::vector<BvhNode> bvh;                  // bvh
   std::vector<uint32_t> aux, pool;           // bvh_aux, texels
   TriTree tt;                                // tri_bvh (nodes), tri_resid (resid)

@@ -283,7 +283,8 @@ __global__ __launch_bounds__(kWgThreads) __attribute__((amdgpu_waves_per_eu(
       // the tile's per-view masks (prim_cull_kernel<., true>; chunks: the pixel's closest-hit mask, every chunk)
       const uint64_t *pm = RFX_PRIM_LANES && SMALL && CULL && !STATS && P.prim_mask
                                ? P.prim_mask + (size_t)kPrimStride * t8 : nullptr;
-      const col c = trace<STATS, CULL, MANYL, SMALL, PLANES, ONEL, TBVH, FARL>(S, eye, ray, P.depth, rd, lut, cnt, valid, pm,
+      // (FARL without the occluder grid: rfx_bounce.h SGRID)
+      const col c = trace<STATS, CULL, MANYL, SMALL, PLANES, ONEL, TBVH, FARL, false>(S, eye, ray, P.depth, rd, lut, cnt, valid, pm,
                                                                         P.prim_shadow != 0);
       {
 #ifdef RFX_LAUNDER_PARAMS
@@ -416,7 +417,8 @@ __global__ __launch_bounds__(kWgThreads) __attribute__((amdgpu_waves_per_eu(
       if (valid) rd = load_rd(P, pr);
       const ParkTile park{P.park_after, P.queue, P.queue_count, P, wv, w8};
       const uint64_t *pm_tile = SMALL && CULL && !STATS && P.prim_mask ? P.prim_mask + (size_t)kPrimStride * t8 : nullptr;
-      const col c = trace_from<STATS, CULL, MANYL, SMALL, PLANES, PARK, ParkTile, ONEL, TBVH, FARL>(
+      // (the parking form without the occluder grid, rfx_bounce.h SGRID: with it the kernel spills one VGPR more)
+      const col c = trace_from<STATS, CULL, MANYL, SMALL, PLANES, PARK, ParkTile, ONEL, TBVH, FARL, FARL && !PARK>(
           S, eye, ray, mkc(1.0f, 1.0f, 1.0f), mkc(0.0f, 0.0f, 0.0f), 0, P.depth, rd, lut, cnt, valid, park, parked, pm_tile);
       out = cadd(mkc(0.0f, 0.0f, 0.0f), c);                                      // Render.cpp:185 (/ 1.0f exact)
     }

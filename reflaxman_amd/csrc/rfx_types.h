@@ -87,6 +87,17 @@ struct alignas(16) LightRec {
   float dlen, ndx, ndy, ndz, spec_add, near, cone_cos, cone_sin;
 };
 struct alignas(16) TexRec { uint32_t offset, w, h, pad; };
+// A far light's occluder grid (small scenes with one far light; rfx_scene.cpp shadow_grid_build, DESIGN.md "Shadow
+// grid"): cubic cells over a world-axis box, nx x ny x nz of them from the corner (ox, oy, oz), scale = 1 / cell size.
+// cells[(iz ny + iy) nx + ix], in CullRec's lane layout: the objects a shadow ray toward the light may be reported to
+// hit from any origin inside that cell.  cells == null: no grid.  fnx, fny, fnz: the dimensions as floats (the range
+// test of rfx_cull_rule.h shadow_grid_cell).
+struct ShadowGrid {
+  const uint64_t *cells;
+  float ox, oy, oz, scale;
+  float fnx, fny, fnz;
+  int32_t nx, ny, nz;
+};
 
 struct DevScene {
   const SphereGeo *sph_geo;   // n_sph
@@ -129,6 +140,7 @@ struct DevScene {
   int32_t tri_bvh_depth;      // its internal levels (<= kBvhStack)
   int32_t tri_bvh_narrow;     // narrow bundles (a tile's primary rays) walk the tree too (else: the bundle-culled chunks)
   int32_t far_light;          // host only: the launches may take the far-light kernels (rfx_scene_set_far_lights)
+  ShadowGrid shadow_grid;     // the one far light's occluder grid (rfx_scene_set_shadow_grid), cells null without one
 };
 
 // The bounce kernel with the BVH staged in LDS (rfx_parked.h bounce_kernel_lds): one workgroup of kLdsBvhWaves waves

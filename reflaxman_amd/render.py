@@ -261,6 +261,27 @@ class Scene:
         chosen = check(_lib.load().rfx_scene_far_light(self._h, int(light), _lib.fptr(terms)), "Scene.far_light")
         return bool(chosen), terms
 
+    def set_shadow_grid(self, mode: int):
+        """A far light's occluder grid (rfx.h rfx_scene_set_shadow_grid): 0 none, 1 where the far-light kernels run (the
+        default), 2 for any small scene with one far light.  No pixel changes; read by the next upload of the scene."""
+        check(_lib.load().rfx_scene_set_shadow_grid(self._h, int(mode)), "Scene.set_shadow_grid")
+        self._version += 1
+
+    def shadow_grid(self):
+        """The occluder grid a renderer would upload for this scene (rfx.h rfx_scene_shadow_grid; host only), or None
+        without one: dict of origin (3,) float32, scale, cell, ball (float32), dims (nx, ny, nz), masks (nz, ny, nx)
+        uint64."""
+        L = _lib.load()
+        n = check(L.rfx_scene_shadow_grid(self._h, None, None, None, 0), "Scene.shadow_grid")
+        if n == 0:
+            return None
+        geom, dims, masks = np.zeros(6, np.float32), np.zeros(3, np.int32), np.zeros(n, np.uint64)
+        check(L.rfx_scene_shadow_grid(self._h, _lib.fptr(geom), dims.ctypes.data_as(_lib._i32p), _lib.u64ptr(masks), n),
+              "Scene.shadow_grid")
+        nx, ny, nz = (int(v) for v in dims)
+        return {"origin": geom[:3].copy(), "scale": geom[3], "cell": geom[4], "ball": geom[5], "dims": (nx, ny, nz),
+                "masks": masks.reshape(nz, ny, nx)}
+
     def addPlane(self, pos: Vector3, norm: Vector3, material: Material) -> Plane:
         """Plane(pos, norm, material) (Plane.cpp:9-14) as a scene object, traced by Plane::trace (Plane.cpp:36-73)."""
         obj = check(_lib.load().rfx_scene_add_plane(self._h, farr(Vector3(*pos)), farr(Vector3(*norm)), material.type,

@@ -114,6 +114,10 @@ VARIANTS = {
     "far0": ["RFX_FAR_LIGHT=0"],  # far lights: no far-light kernels, every hit computes the light's terms
     "far2": ["RFX_FAR_LIGHT=2"],  # ... the shading terms from the light's record, the shadow cone from the rays
     "far3": ["RFX_FAR_LIGHT=3"],  # ... the shadow cone from the record, the shading terms computed
+    "grid0": ["RFX_SHADOW_GRID=0"],  # shadow grid: no grid path in the kernels, no grid built (the kernels before it)
+    "gridlate": ["RFX_SHADOW_GRID=2"],  # ... a lane's cell mask loaded after the facing test, once the wave takes the grid
+    "grid14": ["RFX_SHADOW_GRID_CELLS=(1<<14)"],  # ... a quarter of the cells
+    "grid18": ["RFX_SHADOW_GRID_CELLS=(1<<18)"],  # ... four times the cells
 }
 
 
@@ -153,7 +157,7 @@ def build_scene_with(L, desc):
 
 class Runner:
     def __init__(self, name, path, desc, W, H, depth, seed, tile_order=None, regroup=None, prim=None, ss=1, additive=0,
-                 tri_accel=None, exact=None, mates=None, far=None):
+                 tri_accel=None, exact=None, mates=None, far=None, grid=None):
         self.name = name
         L = self.L = _lib.bind(path, partial=True)
         self.scene, eye, view, fov = build_scene_with(L, desc)
@@ -161,6 +165,8 @@ class Runner:
             assert L.rfx_scene_set_tri_mates(self.scene, mates) == 0
         if far is not None:  # before the upload: the light's record and the kernels' choice are made by set_scene
             assert L.rfx_scene_set_far_lights(self.scene, far) == 0
+        if grid is not None:  # before the upload: the grid is built by set_scene
+            assert L.rfx_scene_set_shadow_grid(self.scene, grid) == 0
         self.r = C.c_void_p()
         rc = L.rfx_renderer_create(C.byref(self.r), 0)
         assert rc == 0, L.rfx_last_error()
@@ -245,16 +251,18 @@ def cmd_run(args):
     exacts = [None] if not args.exact else [int(v) for v in args.exact.split(",")]
     mates = [None] if not args.mates else [int(v) for v in args.mates.split(",")]
     fars = [None] if not args.far else [int(v) for v in args.far.split(",")]
+    grids = [None] if not args.grid else [int(v) for v in args.grid.split(",")]
     runners = [Runner(n + ("" if g is None else f"@park{g}") + ("" if q is None else f"@prim{q}") +
                       ("" if t is None else f"@tri{t}") + ("" if e is None else f"@exact{e}") +
-                      ("" if m is None else f"@mates{m}") + ("" if fl is None else f"@far{fl}"), p, desc, args.width,
+                      ("" if m is None else f"@mates{m}") + ("" if fl is None else f"@far{fl}") + ("" if sg is None else f"@grid{sg}"), p, desc, args.width,
                       args.height, args.depth, 1350490027, regroup=g, prim=q, ss=args.ss, additive=args.additive,
-                      tri_accel=t, exact=e, mates=m, far=fl)
+                      tri_accel=t, exact=e, mates=m, far=fl, grid=sg)
                for n, p in zip(names, paths) for g in regroups for q in prims for t in tris
                # a build from before the switch (tools/build_rev.py) runs once, as it is
                for e in (exacts if hasattr(C.CDLL(p), "rfx_renderer_set_prim_exact") else [None])
                for m in (mates if hasattr(C.CDLL(p), "rfx_scene_set_tri_mates") else [None])
-               for fl in (fars if hasattr(C.CDLL(p), "rfx_scene_set_far_lights") else [None])]
+               for fl in (fars if hasattr(C.CDLL(p), "rfx_scene_set_far_lights") else [None])
+               for sg in (grids if hasattr(C.CDLL(p), "rfx_scene_set_shadow_grid") else [None])]
     # parity of every variant: frame 1 against the reference's full-frame hash (when the manifest has one), and
     # frame 1 + LATER frames (rendered in the learned longest-tile-first order, after the tile sorts) against
     # the product build rendering the same frames in raster order
@@ -323,6 +331,8 @@ def main():
                     "(0: every triangle its own mate group, so the kernels recompute every z stage)")
     ap.add_argument("--far", default="", help="comma list of rfx_scene_set_far_lights settings to run each build with "
                     "(0: the general kernels, 1: the far-light kernels where the scene qualifies, 2: for any far light)")
+    ap.add_argument("--grid", default="", help="comma list of rfx_scene_set_shadow_grid settings to run each build with "
+                    "(0: no occluder grid, 1: where the far-light kernels run, 2: for any small scene with one far light)")
     args = ap.parse_args()
     if args.cmd == "build":
         cmd_build(args.variants.split(","))

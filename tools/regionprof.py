@@ -37,11 +37,13 @@ def main():
                     help="rfx_scene_set_tri_mates setting (0: every triangle its own mate group)")
     ap.add_argument("--far", type=int, default=None,
                     help="rfx_scene_set_far_lights setting (0: the general kernels)")
+    ap.add_argument("--grid", type=int, default=None,
+                    help="rfx_scene_set_shadow_grid setting (0: every shadow bundle culled by the wave's own cone)")
     a = ap.parse_args()
     path = os.path.join(_build.LIBDIR, "diag", a.lib)
     scene = a.scene
     r = ab.Runner("prof", path, scenes.get_scene(scene), a.width, a.height, a.depth, 1350490027, regroup=a.regroup,
-                  prim=a.prim, exact=a.exact, mates=a.mates, far=a.far)
+                  prim=a.prim, exact=a.exact, mates=a.mates, far=a.far, grid=a.grid)
     r.render(2)
     assert r.L.rfx_synchronize(r.r) == 0
     buf = (C.c_ulonglong * 16)()
@@ -64,7 +66,7 @@ def main():
         cull["closest_large"] = {"bundles": v[0], "usable": round(v[1] / n, 3), "live_lanes": round(v[2] / n, 1),
                                  "kept_chunks": round(v[3] / n, 2), "kept_spheres": round(v[4] / n, 1),
                                  "pair_tests": round(v[5] / n, 1)}
-    print(json.dumps({"scene": scene, "lib": os.path.basename(path), "prim_masks": a.prim, "prim_exact": a.exact, "tri_mates": a.mates, "cycles": {k: int(v) for k, v in zip(REGIONS, buf[:8])},
+    print(json.dumps({"scene": scene, "lib": os.path.basename(path), "prim_masks": a.prim, "prim_exact": a.exact, "tri_mates": a.mates, "shadow_grid": a.grid, "cycles": {k: int(v) for k, v in zip(REGIONS, buf[:8])},
                       "wave_executions": {k: int(v) for k, v in zip(REGIONS, buf[8:])},
                       "share_of_trace": {k: round(v / tot, 4) for k, v in zip(REGIONS, buf[:8])},
                       "cull": cull}))
