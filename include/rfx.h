@@ -670,6 +670,56 @@ int rfx_scene_tri_bvh_refit(const rfx_scene *built, const float *vertices9_all, 
  * the 2 children as int32, the 2 margin terms.  Returns the node count (0: no tree); out may be NULL to ask for it. */
 int rfx_renderer_tri_bvh_nodes(rfx_renderer *r, float *out);
 
+/* ---------------------------------------------------------------- Re-cutting
+ * The other half of moving meshes: rfx_renderer_update_triangles keeps the tree's topology as rfx_renderer_set_scene cut
+ * it, and a mesh that has left that shape is traced through ever looser boxes.  rfx_renderer_recut_triangles rebuilds
+ * the uploaded triangle BVH's topology and leaf membership on the device from the triangles' current vertices -- what
+ * the updates so far left -- and refits every box.  Stream-ordered (NULL = the renderer's stream), no host sync, no
+ * allocation.  (Added under RFX_ABI_VERSION 5; detect it by symbol.)  Nothing calls it by itself: when to re-cut is the
+ * caller's policy.
+ *
+ * Values contract: no value of any launch changes.  The tree is a schedule (DESIGN.md "Triangle BVH -> Device": winners
+ * do not depend on visiting order), so after a re-cut frames of every mode, rfx_trace_rays, the hit queries and spans,
+ * the ordered forms and rfx_paths_step return word for word what they returned before it -- and so what a fresh
+ * rfx_renderer_set_scene of the moved scene returns.  The call drops the per-view masks, as the update does, and
+ * touches no random stream, tile cost, timing sum, regroup queue or rewind state.
+ *
+ * What stays as rfx_renderer_set_scene left it: the set of in-tree triangles (the T triangles that were well-conditioned
+ * then), the residual list, the leaf count G = ceil(T / leaf size), the node count G - 1 (rfx_renderer_accel_info's
+ * tri_nodes), the margin reference point and every device pointer.  tri_depth becomes ceil(log2 G).  After a re-cut
+ * rfx_renderer_update_triangles keeps working, on the new tree.
+ *
+ * The cut is a function of the current vertices alone.  Every operation is IEEE float32 with no contraction, so a
+ * float32 restatement gives the same bits:
+ *   1. Per in-tree triangle t, from its current vertices and the class flag ill[t] the update keeps (word [28] of
+ *      rfx_renderer_tri_records, inverted): s_a = (v1_a + v2_a) + v3_a per axis -- three times the centroid, with no
+ *      division.  t is placed iff ill[t] == 0 and s_x, s_y, s_z are all finite.
+ *   2. Box: per axis, lo_a = min and hi_a = max of s_a over the placed triangles (exact, so in any order);
+ *      e = max_a (hi_a - lo_a); scale = 1024 / e where e is finite and > 0, else 0.  One scale for all axes: the cells
+ *      are cubic.  The sign of a zero bound does not reach a key.
+ *   3. Key: q_a = (uint32) fminf(fmaxf((s_a - lo_a) * scale, 0), 1023); bit b of q_x at 3b, of q_y at 3b + 1, of q_z
+ *      at 3b + 2, 30 bits in all.  An in-tree triangle that is not placed takes key 0x40000000: ill triangles gather in
+ *      the last leaves, where the all-space (NaN) boxes the refit gives them spoil only one spine of the tree.
+ *   4. Order: the in-tree triangles are stably sorted by key, equal keys in ascending triangle index.  Leaf g holds the
+ *      sorted entries [L g, L g + L), L = the leaf size (4); the last leaf is padded with -1, and padding records are all
+ *      zero.  A leaf record is the triangle's twelve geometry words with its triangle and object index behind them.
+ *   5. Topology: fixed by G alone.  node(a, b) over leaves [a, b) with b - a >= 2 takes the next index in pre-order (the
+ *      root is node 0) and splits at mid = a + (b - a) / 2; a one-leaf side is the child ~a.  Depth ceil(log2 G) <= 15.
+ *      Then the refit of "Moving meshes": every box from the current vertices, NaN bounds above an ill triangle.
+ * The sort is rfx_rays_order's and shares the renderer's sort scratch with it (reserved for the in-tree count by
+ * rfx_renderer_set_scene): as there, a re-cut and an order call of one renderer, or two re-cuts, on streams that are not
+ * ordered with each other are the caller's error.
+ *
+ * Errors: NULL renderer: RFX_ERR_ARG; no scene uploaded, a small scene, or a scene without a triangle tree
+ * (rfx_renderer_accel_info's tri_nodes == 0): RFX_ERR_STATE. */
+int rfx_renderer_recut_triangles(rfx_renderer *r, void *stream);
+/* The same cut on the host (no device): `built`'s in-tree set and residual list, the triangles classed and cut at
+ * cut_vertices9_all, the boxes fitted to vertices9_all (NULL: the cut's) -- 9 floats for every triangle of the scene.
+ * counts, boxes, children and leaf_ids in rfx_scene_tri_bvh_dump's layouts (counts[2] the residual count, counts[4] the
+ * new depth), mt and widen as rfx_scene_tri_bvh_refit's; the arrays may be NULL.  Returns 1 with a tree, 0 without. */
+int rfx_scene_tri_bvh_recut(const rfx_scene *built, const float *cut_vertices9_all, const float *vertices9_all, int widen,
+                            int32_t counts[5], float *boxes, int32_t *children, int32_t *leaf_ids, float *mt);
+
 /* ---------------------------------------------------------------- Device groups (multi-GPU, one process)
  * A group renders the frame of Render::renderNext (Render.cpp:136-215) on several devices of this process: row bands,
  * one per member, each member counting its slice of the frame's random stream and pushing it to the others (the one

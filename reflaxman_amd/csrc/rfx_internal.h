@@ -212,6 +212,15 @@ struct rfx_renderer {
   rfx::DevBuf<rfx::RefitBox> upd_lbox, upd_nbox;
   std::vector<uint32_t> upd_hoff;
   uint32_t upd_tris = 0, upd_leaves = 0;
+  // re-cutting (rfx_update.cpp; filled by set_scene for a scene with a triangle tree, cut_tris its in-tree count, else
+  // 0): the in-tree triangles ascending, the cut's children and by-height node list with their host-known shape, and
+  // the key box's six words.  The sort's scratch (order_keys, order_idx, order_table) is reserved for cut_tris pairs at
+  // set_scene, so the call allocates nothing.
+  rfx::DevBuf<uint32_t> cut_in, cut_box;
+  rfx::DevBuf<int32_t> cut_child, cut_hlist;
+  std::vector<uint32_t> cut_hoff;
+  int cut_depth = 0;
+  uint32_t cut_tris = 0;
   // per-phase event timing: triples {start, after pre-pass, after trace} on every timing_every-th frame (the events'
   // own cost stays off the other frames: ~10 us per frame for three records at C1's 640x480)
   bool timing = false, timing_this = false;

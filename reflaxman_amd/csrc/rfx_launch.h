@@ -92,4 +92,10 @@ struct RefitParams;
 hipError_t launch_update_tris(const UpdateParams &P, hipStream_t st);
 hipError_t launch_refit_leaves(const RefitParams &P, hipStream_t st);
 hipError_t launch_refit_nodes(const RefitParams &P, hipStream_t st);
+// ... and re-cutting: the in-tree triangles' sort keys from their current vertices (the box reduction, then the keys);
+// after the sort, the slots, leaf records and the cut's topology put in place
+struct RecutParams;
+struct RecutPlaceParams;
+hipError_t launch_recut_keys(const RecutParams &P, hipStream_t st);
+hipError_t launch_recut_place(const RecutPlaceParams &P, hipStream_t st);
 }  // namespace rfx

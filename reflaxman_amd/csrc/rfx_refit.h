@@ -1,6 +1,6 @@
 // What follows a triangle's vertices, written once for the three places that compute it: the host scene builder
-// (rfx_scene.cpp: rfx_scene_add_triangle, SceneBuild, build_pair_bvh), the host refit (rfx_scene_tri_bvh_refit) and the
-// device update (rfx_update_kernels.hip).  Float steps are rfx_math.h's (the reference's Triangle constructor, operation for
+// (rfx_scene.cpp: rfx_scene_add_triangle, SceneBuild, build_pair_bvh), the host refit and re-cut (rfx_scene_tri_bvh_refit,
+// rfx_scene_tri_bvh_recut) and the device update and re-cut (rfx_update_kernels.hip).  Float steps are rfx_math.h's (the reference's Triangle constructor, operation for
 // operation); double steps are IEEE add, multiply, divide and sqrt, so with FP contraction off the device gives the
 // host's words.  No HIP needed: a plain C++ compiler builds rfx_scene.cpp with this.
 #pragma once
@@ -179,6 +179,81 @@ struct RefitParams {
   const int32_t *list;
   uint32_t n;            // leaves (refit_leaves_kernel) or nodes of this height (refit_nodes_kernel)
   double ref[3];         // DevScene::bvh_rx, bvh_ry, bvh_rz
+};
+
+// ---- Re-cutting (rfx.h "Re-cutting"): the cut's formulas, shared by the host mirror (rfx_scene.cpp
+// rfx_scene_tri_bvh_recut) and the kernels (rfx_update_kernels.hip).  Every step is one IEEE float32 operation, with no
+// contraction, so a float32 restatement gives the same bits.
+// three times the centroid, per axis (v1 + v2) + v3: no division
+RFX_HD void recut_sum(const float *v9, float s[3])
+{
+  for (int a = 0; a < 3; ++a) s[a] = (v9[a] + v9[3 + a]) + v9[6 + a];
+}
+RFX_HD bool recut_finite(float x) { return (f2u(x) & 0x7F800000u) != 0x7F800000u; }
+// a triangle of the tree is placed -- it has a cell of the cut's box -- when it is well-conditioned and its sums are finite
+RFX_HD bool recut_placed(const float s[3], uint32_t ill)
+{
+  return !ill && recut_finite(s[0]) && recut_finite(s[1]) && recut_finite(s[2]);
+}
+// one scale for the three axes (cubic cells) from the placed sums' box [lo, hi]; an empty box (lo = +inf, hi = -inf: the
+// extent is -inf), a point and an extent that overflows give 0: every placed triangle then takes key 0
+RFX_HD float recut_scale(const float lo[3], const float hi[3])
+{
+  float e = hi[0] - lo[0];
+  e = fmaxf(e, hi[1] - lo[1]);
+  e = fmaxf(e, hi[2] - lo[2]);
+  return e > 0.0f && recut_finite(e) ? 1024.0f / e : 0.0f;
+}
+// The key of a placed triangle: 10 bits of cell per axis, bit b of x at 3 b, of y at 3 b + 1, of z at 3 b + 2.
+// The sign of a zero bound does not reach the key.  lo_a is a minimum of the sums, and which of -0 and +0 a minimum of
+// both returns depends on the reduction's order (the device's integer encoding puts -0 below +0; fminf may keep either).
+// For s_a != 0, s_a - (+-0) is s_a.  For s_a = +-0 the difference is a zero of either sign, its product with the scale
+// is a zero, fmaxf of two zeros is a zero and the conversion of either zero is 0.  hi_a - lo_a is compared with 0 and
+// divides 1024 only where it is positive, so a zero's sign ends there too.
+constexpr uint32_t kRecutCells = 1024, kRecutCellBits = 10;
+constexpr uint32_t kRecutLastKey = 0x40000000u;  // an in-tree triangle that is not placed: behind every placed one
+RFX_HD uint32_t recut_key(const float s[3], const float lo[3], float scale)
+{
+  uint32_t key = 0;
+  for (int a = 0; a < 3; ++a)
+  {
+    const uint32_t q = (uint32_t)fminf(fmaxf((s[a] - lo[a]) * scale, 0.0f), (float)(kRecutCells - 1u));  // NaN: the 0
+    for (uint32_t b = 0; b < kRecutCellBits; ++b) key |= ((q >> b) & 1u) << (3u * b + (uint32_t)a);
+  }
+  return key;
+}
+// An order-preserving code of a non-NaN float for integer atomic min / max: a < b as floats => code(a) < code(b), and
+// -0 below +0
+RFX_HD uint32_t recut_code(float x)
+{
+  const uint32_t u = f2u(x);
+  return u & 0x80000000u ? ~u : u | 0x80000000u;
+}
+RFX_HD float recut_decode(uint32_t c) { return u2f(c & 0x80000000u ? c & 0x7FFFFFFFu : ~c); }
+
+// The re-cut's launches (rfx_update_kernels.hip).  box: six words, [a] the code of lo_a, [3 + a] the complement of the
+// code of hi_a, so that both are atomic minima and one fill with ones empties the box.
+struct RecutParams {
+  const uint32_t *intree;  // the n in-tree triangles, ascending
+  const float *verts;
+  const uint32_t *ill;
+  uint32_t *box;
+  uint32_t *keys;          // n sort keys, in intree's order
+  uint32_t n;
+};
+// ... and after the sort: slot q < slots of `order` (leaves x RFX_TRI_BVH_LEAF, -1 padding) names its triangle; the
+// triangle's slot, the leaf record, and -- lanes q < nodes -- the cut's children and by-height list put in place
+struct RecutPlaceParams {
+  const int32_t *order;
+  int32_t *slot;
+  const TriGeo *tri_geo;
+  const TriShade *tri_shade;
+  TriGeo *tri_leaf;
+  BvhNode *nodes;
+  const int32_t *cut_child;  // nodes x 2
+  const int32_t *cut_hlist;  // nodes
+  int32_t *hlist;
+  uint32_t slots, nodes_n;
 };
 
 }  // namespace rfx

@@ -623,6 +623,46 @@ static void tri_ref_point(const std::vector<HostTri> &tris, double *ref)
   for (int k = 0; k < 3; ++k) ref[k] = lo[k] <= hi[k] ? (double)(float)(0.5 * (lo[k] + hi[k])) : 0.0;
 }
 
+// The nodes of a tree by height (a leaf's is 0), lowest first: hlist[hoff[h - 1] .. hoff[h]) are the nodes of height
+// h >= 1, each above both its children.  child: nodes x 2, children after their parent (build_pair_bvh's node order and
+// cut_topology's pre-order), so one backward pass has every child's height.
+static void height_lists(const std::vector<int32_t> &child, std::vector<int32_t> &hlist, std::vector<uint32_t> &hoff)
+{
+  const size_t n = child.size() / 2;
+  std::vector<int> height(n, 0);
+  for (size_t i = n; i-- > 0;)
+    for (int c = 0; c < 2; ++c) height[i] = std::max(height[i], 1 + (child[2 * i + c] >= 0 ? height[child[2 * i + c]] : 0));
+  hlist.clear();
+  hoff.assign(1, 0u);
+  for (int h = 1; hlist.size() < n; ++h)
+  {
+    for (size_t i = 0; i < n; ++i)
+      if (height[i] == h) hlist.push_back((int32_t)i);
+    hoff.push_back((uint32_t)hlist.size());
+  }
+}
+
+static int cut_node(std::vector<int32_t> &child, size_t a, size_t b, int level, int &depth)
+{
+  if (b - a == 1) return ~(int)a;
+  depth = std::max(depth, level + 1);
+  const size_t id = child.size() / 2, mid = a + (b - a) / 2;
+  child.resize(child.size() + 2);
+  const int l = cut_node(child, a, mid, level + 1, depth), r = cut_node(child, mid, b, level + 1, depth);
+  child[2 * id] = l;
+  child[2 * id + 1] = r;
+  return (int)id;
+}
+
+CutTopology rfx::cut_topology(size_t leaves)
+{
+  CutTopology c;
+  if (leaves < 2) return c;
+  cut_node(c.child, 0, leaves, 0, c.depth);
+  height_lists(c.child, c.hlist, c.hoff);
+  return c;
+}
+
 extern "C" int rfx_scene_tri_bvh_dump(const rfx_scene *s, int32_t counts[5], float *boxes, int32_t *children,
                                       int32_t *leaf_ids, int32_t *residual)
 {
@@ -1182,17 +1222,16 @@ SceneBuild::SceneBuild(const rfx_scene &scene, int tri_accel)
       for (const v3 *v : {&t.v0, &t.v1, &t.v2}) { tverts.push_back(v->x); tverts.push_back(v->y); tverts.push_back(v->z); }
       till.push_back(t.cond < 300.0 ? 0u : 1u);
     }
-    // children follow their parent in build_pair_bvh's node order, so one backward pass has every child's height
-    std::vector<int> height(tt.nodes.size(), 0);
-    for (size_t i = tt.nodes.size(); i-- > 0;)
-      for (int c = 0; c < 2; ++c)
-        height[i] = std::max(height[i], 1 + (tt.nodes[i].child[c] >= 0 ? height[tt.nodes[i].child[c]] : 0));
-    hoff.assign(1, 0u);
-    for (int h = 1; hlist.size() < tt.nodes.size(); ++h)
+    std::vector<int32_t> child;
+    for (const BvhNode &n : tt.nodes) { child.push_back(n.child[0]); child.push_back(n.child[1]); }
+    height_lists(child, hlist, hoff);
+    // the re-cut's tables: a binary tree over G leaves has G - 1 nodes whatever its splits, so the cut's nodes take the
+    // built tree's array one for one (were that ever not so, the scene has no re-cut: RFX_ERR_STATE)
+    if (!tt.nodes.empty() && tt.nodes.size() + 1 == tt.leaves())
     {
-      for (size_t i = 0; i < tt.nodes.size(); ++i)
-        if (height[i] == h) hlist.push_back((int32_t)i);
-      hoff.push_back((uint32_t)hlist.size());
+      for (size_t i = 0; i < s->tris.size(); ++i)
+        if (tslot[i] >= 0) tin.push_back((uint32_t)i);
+      cut = cut_topology(tt.leaves());
     }
   }
   for (const HostPlane &p : s->planes)
@@ -1367,6 +1406,42 @@ RefitBox refit_below(std::vector<BvhNode> &nodes, int c, const std::vector<Refit
 }
 }  // namespace
 
+// every box of the tree `nodes` over the leaves order[RFX_TRI_BVH_LEAF g ..] from the vertices given, classed there
+static void refit_tree(std::vector<BvhNode> &nodes, const std::vector<int32_t> &order, const float *vertices9_all,
+                       const double *ref, bool widen)
+{
+  std::vector<RefitBox> leaf(order.size() / RFX_TRI_BVH_LEAF);
+  for (size_t g = 0; g < leaf.size(); ++g)
+  {
+    refit_box_empty(leaf[g]);
+    for (int e = 0; e < RFX_TRI_BVH_LEAF; ++e)
+    {
+      const int32_t i = order[RFX_TRI_BVH_LEAF * g + e];
+      if (i < 0) continue;
+      const float *v = vertices9_all + 9 * (size_t)i;
+      for (int q = 0; q < 3; ++q) refit_box_vertex(leaf[g], v + 3 * q);
+      if (!tri_well(tri_setup(mk(v[0], v[1], v[2]), mk(v[3], v[4], v[5]), mk(v[6], v[7], v[8])))) leaf[g].ill = 1;
+    }
+  }
+  refit_below(nodes, 0, leaf, ref, widen);
+}
+
+// the nodes' boxes in rfx_scene_tri_bvh_dump's layout and their margin terms; either may be null
+static void report_nodes(const std::vector<BvhNode> &nodes, float *boxes, float *mt)
+{
+  for (size_t i = 0; i < nodes.size(); ++i)
+  {
+    const BvhNode &n = nodes[i];
+    if (boxes)
+      for (int c = 0; c < 2; ++c)
+      {
+        float *b = boxes + 12 * i + 6 * c;
+        b[0] = n.lx[c]; b[1] = n.ly[c]; b[2] = n.lz[c]; b[3] = n.hx[c]; b[4] = n.hy[c]; b[5] = n.hz[c];
+      }
+    if (mt) { mt[2 * i] = n.mt[0]; mt[2 * i + 1] = n.mt[1]; }
+  }
+}
+
 extern "C" int rfx_scene_tri_bvh_refit(const rfx_scene *built, const float *vertices9_all, int widen, float *boxes,
                                        float *mt)
 {
@@ -1376,30 +1451,62 @@ extern "C" int rfx_scene_tri_bvh_refit(const rfx_scene *built, const float *vert
   TriTree &T = B.tt;
   if (T.nodes.empty()) return 0;
   const double ref[3] = {B.d.bvh_rx, B.d.bvh_ry, B.d.bvh_rz};
-  std::vector<RefitBox> leaf(T.leaves());
-  for (size_t g = 0; g < leaf.size(); ++g)
+  refit_tree(T.nodes, T.order, vertices9_all, ref, widen != 0);
+  report_nodes(T.nodes, boxes, mt);
+  return 1;
+}
+
+// rfx.h "Re-cutting": the device re-cut's mirror.  The in-tree set, the residual list and the reference point are
+// `built`'s; the order is the stable sort of the in-tree triangles by rfx_refit.h's key at cut_vertices9_all; the
+// topology is cut_topology's; the boxes are the refit's at vertices9_all.
+extern "C" int rfx_scene_tri_bvh_recut(const rfx_scene *built, const float *cut_vertices9_all, const float *vertices9_all,
+                                       int widen, int32_t counts[5], float *boxes, int32_t *children, int32_t *leaf_ids,
+                                       float *mt)
+{
+  if (!built || !cut_vertices9_all || !counts || widen < 0 || widen > 1)
+    return fail(RFX_ERR_ARG, "scene_tri_bvh_recut: bad args");
+  for (int k = 0; k < 5; ++k) counts[k] = 0;
+  counts[3] = RFX_TRI_BVH_LEAF;
+  if (built->spheres.size() <= 32 && built->tris.size() <= 32) return 0;  // a small scene: no tree
+  SceneBuild B(*built, 1);
+  if (B.tin.empty()) return 0;
+  const size_t n = B.tin.size(), leaves = B.tt.leaves();
+  // steps 1 and 2: the sums, the placed ones' box
+  std::vector<float> sum(3 * n);
+  std::vector<uint8_t> placed(n);
+  float lo[3] = {INFINITY, INFINITY, INFINITY}, hi[3] = {-INFINITY, -INFINITY, -INFINITY};
+  for (size_t j = 0; j < n; ++j)
   {
-    refit_box_empty(leaf[g]);
-    for (int e = 0; e < RFX_TRI_BVH_LEAF; ++e)
-    {
-      const int32_t i = T.order[RFX_TRI_BVH_LEAF * g + e];
-      if (i < 0) continue;
-      const float *v = vertices9_all + 9 * (size_t)i;
-      for (int q = 0; q < 3; ++q) refit_box_vertex(leaf[g], v + 3 * q);
-      if (!tri_well(tri_setup(mk(v[0], v[1], v[2]), mk(v[3], v[4], v[5]), mk(v[6], v[7], v[8])))) leaf[g].ill = 1;
-    }
+    const float *v = cut_vertices9_all + 9 * (size_t)B.tin[j];
+    recut_sum(v, &sum[3 * j]);
+    const bool well = tri_well(tri_setup(mk(v[0], v[1], v[2]), mk(v[3], v[4], v[5]), mk(v[6], v[7], v[8])));
+    placed[j] = recut_placed(&sum[3 * j], well ? 0u : 1u);
+    if (placed[j])
+      for (int a = 0; a < 3; ++a) { lo[a] = fminf(lo[a], sum[3 * j + a]); hi[a] = fmaxf(hi[a], sum[3 * j + a]); }
   }
-  refit_below(T.nodes, 0, leaf, ref, widen != 0);
-  for (size_t i = 0; i < T.nodes.size(); ++i)
+  // steps 3 and 4: the keys, the stable order (tin ascends, so equal keys keep ascending triangle indices)
+  const float scale = recut_scale(lo, hi);
+  std::vector<uint32_t> key(n), at(n);
+  for (size_t j = 0; j < n; ++j)
   {
-    const BvhNode &n = T.nodes[i];
-    if (boxes)
-      for (int c = 0; c < 2; ++c)
-      {
-        float *b = boxes + 12 * i + 6 * c;
-        b[0] = n.lx[c]; b[1] = n.ly[c]; b[2] = n.lz[c]; b[3] = n.hx[c]; b[4] = n.hy[c]; b[5] = n.hz[c];
-      }
-    if (mt) { mt[2 * i] = n.mt[0]; mt[2 * i + 1] = n.mt[1]; }
+    key[j] = placed[j] ? recut_key(&sum[3 * j], lo, scale) : kRecutLastKey;
+    at[j] = (uint32_t)j;
   }
+  std::stable_sort(at.begin(), at.end(), [&](uint32_t x, uint32_t y) { return key[x] < key[y]; });
+  std::vector<int32_t> order(leaves * RFX_TRI_BVH_LEAF, -1);
+  for (size_t j = 0; j < n; ++j) order[j] = (int32_t)B.tin[at[j]];
+  // step 5: the topology of the leaf count, in the built tree's node array, then the refit
+  std::vector<BvhNode> nodes(B.cut.child.size() / 2);
+  for (size_t i = 0; i < nodes.size(); ++i) { nodes[i].child[0] = B.cut.child[2 * i]; nodes[i].child[1] = B.cut.child[2 * i + 1]; }
+  const double ref[3] = {B.d.bvh_rx, B.d.bvh_ry, B.d.bvh_rz};
+  refit_tree(nodes, order, vertices9_all ? vertices9_all : cut_vertices9_all, ref, widen != 0);
+  counts[0] = (int32_t)nodes.size();
+  counts[1] = (int32_t)leaves;
+  counts[2] = (int32_t)B.tt.resid.size();
+  counts[4] = B.cut.depth;
+  report_nodes(nodes, boxes, mt);
+  if (children)
+    for (size_t i = 0; i < nodes.size(); ++i) { children[2 * i] = nodes[i].child[0]; children[2 * i + 1] = nodes[i].child[1]; }
+  if (leaf_ids) std::copy(order.begin(), order.end(), leaf_ids);
   return 1;
 }

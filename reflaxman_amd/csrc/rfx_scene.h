@@ -24,6 +24,17 @@ struct TriTree {
   size_t leaves() const { return order.size() / RFX_TRI_BVH_LEAF; }
 };
 
+// The re-cut's topology (rfx.h "Re-cutting"; rfx_scene.cpp cut_topology), a function of the leaf count alone: node(a, b)
+// over leaves [a, b), b - a >= 2, takes the next index in pre-order (the root is node 0) and splits at a + (b - a) / 2; a
+// one-leaf side is the child ~a.  child: nodes x 2; hlist / hoff: the nodes by height, as SceneBuild's below; depth:
+// ceil(log2 leaves)
+struct CutTopology {
+  std::vector<int32_t> child, hlist;
+  std::vector<uint32_t> hoff;
+  int depth = 0;
+};
+CutTopology cut_topology(size_t leaves);
+
 // Everything rfx_renderer_set_scene puts on the device, built on the host from a scene and the renderer's
 // rfx_renderer_set_tri_accel mode: one vector per DevScene array (named as there in the comments), the scalar fields
 // of `d` (its pointers stay null: the upload sets them) and the hierarchies' summary.
@@ -56,6 +67,10 @@ struct SceneBuild {
   std::vector<float> tverts;
   std::vector<int32_t> tslot, hlist;
   std::vector<uint32_t> till, hoff;
+  // What rfx_renderer_recut_triangles keeps beside them (scenes with a triangle tree, else empty): the in-tree
+  // triangles, ascending, and the cut's topology over the tree's leaves
+  std::vector<uint32_t> tin;
+  CutTopology cut;
 };
 
 // rfx_scene.cpp, for rfx_update.cpp: one triangle's record words in rfx_scene_tri_records' layout (NaNs canonical)

@@ -1,11 +1,12 @@
-// Moving meshes (include/rfx.h "Moving meshes"): rfx_renderer_update_triangles and its host form, the tables set_scene
-// uploads for them, and the read-backs the tests compare with the host mirror (rfx_scene.cpp).  The kernels are
-// rfx_update_kernels.hip; every formula is rfx_refit.h's, shared with the host builder.
+// Moving meshes (include/rfx.h "Moving meshes", "Re-cutting"): rfx_renderer_update_triangles and its host form,
+// rfx_renderer_recut_triangles, the tables set_scene uploads for them, and the read-backs the tests compare with the host
+// mirrors (rfx_scene.cpp).  The kernels are rfx_update_kernels.hip (and, for the re-cut's sort, rfx_order_sort.hip
+// through rfx_order.cpp's order_sort); every formula is rfx_refit.h's, shared with the host builder.
 #include <string.h>
 
 #include <vector>
 
-#include "rfx_internal.h"
+#include "rfx_query_host.h"
 
 using namespace rfx;
 
@@ -21,6 +22,7 @@ static int fill(DevBuf<T> &b, const std::vector<T> &v)
 int rfx::upload_update_tables(rfx_renderer *r, const SceneBuild &B)
 {
   r->upd_tris = 0;
+  r->cut_tris = 0;
   r->upd_leaves = (uint32_t)B.tt.leaves();
   r->upd_hoff = B.hoff;
   RCHECK(fill(r->upd_verts, B.tverts));
@@ -30,7 +32,51 @@ int rfx::upload_update_tables(rfx_renderer *r, const SceneBuild &B)
   RCHECK(fill(r->upd_hlist, B.hlist));
   if (r->upd_lbox.reserve(B.tt.leaves()) < 0 || r->upd_nbox.reserve(B.tt.nodes.size()) < 0) return RFX_ERR_HIP;
   r->upd_tris = (uint32_t)B.tslot.size();  // last: non-zero only with every table in place
+  // the re-cut's tables, and the sort's scratch for its pairs: rfx_renderer_recut_triangles allocates nothing
+  r->cut_hoff = B.cut.hoff;
+  r->cut_depth = B.cut.depth;
+  if (B.tin.empty()) return RFX_OK;
+  RCHECK(fill(r->cut_in, B.tin));
+  RCHECK(fill(r->cut_child, B.cut.child));
+  RCHECK(fill(r->cut_hlist, B.cut.hlist));
+  if (r->cut_box.reserve(6) < 0) return RFX_ERR_HIP;
+  int rc;
+  if ((rc = order_scratch(r, (uint32_t)B.tin.size())) < 0) return rc;
+  r->cut_tris = (uint32_t)B.tin.size();
   return RFX_OK;
+}
+
+// Every box of the uploaded triangle tree from the current vertices, enqueued on st: the leaves, then one launch per
+// height over the by-height lists as they stand (the built tree's, or the last re-cut's).  Nothing without a tree.
+static int enqueue_refit(rfx_renderer *r, hipStream_t st)
+{
+  const DevScene &d = r->dev;
+  if (!d.tri_bvh) return RFX_OK;
+  RefitParams F{};
+  F.nodes = const_cast<BvhNode *>(d.tri_bvh);
+  F.order = r->upd_order;
+  F.verts = r->upd_verts;
+  F.ill = r->upd_ill;
+  F.leaf_box = r->upd_lbox;
+  F.node_box = r->upd_nbox;
+  F.ref[0] = d.bvh_rx; F.ref[1] = d.bvh_ry; F.ref[2] = d.bvh_rz;
+  F.n = r->upd_leaves;
+  HIP_CHECK(launch_refit_leaves(F, st));
+  for (size_t h = 1; h < r->upd_hoff.size(); ++h)
+  {
+    F.list = r->upd_hlist.p + r->upd_hoff[h - 1];
+    F.n = r->upd_hoff[h] - r->upd_hoff[h - 1];
+    HIP_CHECK(launch_refit_nodes(F, st));
+  }
+  return RFX_OK;
+}
+
+// what set_scene, an update and a re-cut all do to the per-view masks: the next frame builds them again
+static void drop_masks(rfx_renderer *r)
+{
+  ++r->scene_gen;
+  r->prim_key.clear();
+  r->prim_seen.clear();
 }
 
 // the update and the whole tree's refit, enqueued on st
@@ -52,30 +98,10 @@ static int enqueue_update(rfx_renderer *r, uint32_t first, uint32_t count, const
   U.first = first;
   U.count = count;
   HIP_CHECK(launch_update_tris(U, st));
-  if (d.tri_bvh)
-  {
-    RefitParams F{};
-    F.nodes = const_cast<BvhNode *>(d.tri_bvh);
-    F.order = r->upd_order;
-    F.verts = r->upd_verts;
-    F.ill = r->upd_ill;
-    F.leaf_box = r->upd_lbox;
-    F.node_box = r->upd_nbox;
-    F.ref[0] = d.bvh_rx; F.ref[1] = d.bvh_ry; F.ref[2] = d.bvh_rz;
-    F.n = r->upd_leaves;
-    HIP_CHECK(launch_refit_leaves(F, st));
-    for (size_t h = 1; h < r->upd_hoff.size(); ++h)
-    {
-      F.list = r->upd_hlist.p + r->upd_hoff[h - 1];
-      F.n = r->upd_hoff[h] - r->upd_hoff[h - 1];
-      HIP_CHECK(launch_refit_nodes(F, st));
-    }
-  }
+  RCHECK(enqueue_refit(r, st));
   // the per-view masks are the old geometry's (as after set_scene); the streams, tile costs, timing sums, regroup queue
   // and rewind state are not the update's to touch
-  ++r->scene_gen;
-  r->prim_key.clear();
-  r->prim_seen.clear();
+  drop_masks(r);
   return RFX_OK;
 }
 
@@ -111,6 +137,49 @@ extern "C" int rfx_renderer_update_triangles_host(rfx_renderer *r, uint32_t firs
   if (indices) HIP_CHECK(hipMemcpyAsync(r->upd_idx.p, indices, 12 * (size_t)count, hipMemcpyHostToDevice, st));
   RCHECK(enqueue_update(r, first, count, r->upd_pos, n_positions, indices ? r->upd_idx.p : nullptr, st));
   HIP_CHECK(hipStreamSynchronize(st));
+  return RFX_OK;
+}
+
+// rfx.h "Re-cutting".  Keys from the current vertices, the renderer's radix sort over the in-tree list straight into the
+// leaf membership (its padding, behind the in-tree count, stays -1 from set_scene), slots / leaf records / topology, refit.
+extern "C" int rfx_renderer_recut_triangles(rfx_renderer *r, void *stream)
+{
+  RCHECK(enter_call(r, true, "renderer_recut_triangles", "a renderer"));
+  if (!r->cut_tris || !r->dev.tri_bvh)
+    return fail(RFX_ERR_STATE, "renderer_recut_triangles: the uploaded scene has no triangle tree (a small scene, or "
+                "rfx_renderer_set_tri_accel left it out)");
+  const hipStream_t st = stream_or_own(r, stream);
+  const DevScene &d = r->dev;
+  int rc;
+  if ((rc = order_scratch(r, r->cut_tris)) < 0) return rc;  // reserved at set_scene: no allocation here
+  RecutParams K{};
+  K.intree = r->cut_in;
+  K.verts = r->upd_verts;
+  K.ill = r->upd_ill;
+  K.box = r->cut_box;
+  K.keys = r->order_keys;
+  K.n = r->cut_tris;
+  HIP_CHECK(launch_recut_keys(K, st));
+  RCHECK(order_sort(r, r->cut_tris, r->cut_in, reinterpret_cast<uint32_t *>(r->upd_order.p), st));
+  RecutPlaceParams Q{};
+  Q.order = r->upd_order;
+  Q.slot = r->upd_slot;
+  Q.tri_geo = d.tri_geo;
+  Q.tri_shade = d.tri_shade;
+  Q.tri_leaf = const_cast<TriGeo *>(d.tri_leaf);
+  Q.nodes = const_cast<BvhNode *>(d.tri_bvh);
+  Q.cut_child = r->cut_child;
+  Q.cut_hlist = r->cut_hlist;
+  Q.hlist = r->upd_hlist;
+  Q.slots = r->upd_leaves * RFX_TRI_BVH_LEAF;
+  Q.nodes_n = (uint32_t)d.n_tri_bvh;
+  HIP_CHECK(launch_recut_place(Q, st));
+  // host-known: the by-height lists' shape and the depth are the cut's from here on
+  r->upd_hoff = r->cut_hoff;
+  r->dev.tri_bvh_depth = r->cut_depth;
+  r->accel.tri_depth = r->cut_depth;
+  RCHECK(enqueue_refit(r, st));
+  drop_masks(r);
   return RFX_OK;
 }
 

@@ -10,6 +10,7 @@
 // The refit is one launch per height, lowest first (at most kBvhStack + 1 launches): a parent reads what its children's
 // launch wrote, and the stream's order is the only hand-off -- no workgroup waits or spins on another, no loop without a
 // static bound.  Every box is a function of the current vertices alone (nothing is grown from the box before).
+// The re-cut's kernels (include/rfx.h "Re-cutting") follow the refit's, with their own heading.
 #include <hip/hip_runtime.h>
 
 #include "rfx_launch.h"
@@ -103,7 +104,103 @@ __global__ __launch_bounds__(kUpdateThreads) void refit_nodes_kernel(const Refit
   P.node_box[id] = b;
 }
 
+// ------------------------------------------------------------- re-cutting (rfx.h "Re-cutting", rfx_refit.h)
+//   recut_box_kernel   : a lane per in-tree triangle; the placed sums' box by a workgroup reduction in LDS (integer
+//                        atomics on rfx_refit.h's order-preserving code: min and max of finite floats are exact, so
+//                        any order gives the same box), then six global atomics per workgroup.
+//   recut_keys_kernel  : a lane per in-tree triangle, its key from the finished box.
+//   (the renderer's radix sort, rfx_order_sort.hip, orders the in-tree list by key between these and the next)
+//   recut_place_kernel : a lane per leaf slot: the triangle's slot and its leaf record from tri_geo / tri_shade (a padding
+//                        slot: zeros); the first lanes also install the cut's children and by-height list.
+// The stream's order is the only hand-off between the launches, as in the refit.
+__global__ __launch_bounds__(kUpdateThreads) void recut_box_kernel(const RecutParams P)
+{
+  __shared__ uint32_t s_box[6];
+  if (threadIdx.x < 6) s_box[threadIdx.x] = 0xFFFFFFFFu;
+  __syncthreads();
+  const uint32_t j = blockIdx.x * kUpdateThreads + threadIdx.x;
+  if (j < P.n)
+  {
+    const uint32_t t = P.intree[j];
+    float s[3];
+    recut_sum(P.verts + 9 * (size_t)t, s);
+    if (recut_placed(s, P.ill[t]))
+    {
+#pragma unroll
+      for (int a = 0; a < 3; ++a)
+      {
+        const uint32_t c = recut_code(s[a]);
+        atomicMin(&s_box[a], c);
+        atomicMin(&s_box[3 + a], ~c);
+      }
+    }
+  }
+  __syncthreads();
+  if (threadIdx.x < 6 && s_box[threadIdx.x] != 0xFFFFFFFFu) atomicMin(&P.box[threadIdx.x], s_box[threadIdx.x]);
+}
+
+__global__ __launch_bounds__(kUpdateThreads) void recut_keys_kernel(const RecutParams P)
+{
+  const uint32_t j = blockIdx.x * kUpdateThreads + threadIdx.x;
+  if (j >= P.n) return;
+  const uint32_t t = P.intree[j];
+  float s[3];
+  recut_sum(P.verts + 9 * (size_t)t, s);
+  uint32_t key = kRecutLastKey;
+  if (recut_placed(s, P.ill[t]))
+  {
+    // (a placed lane: the box holds at least this triangle's sums, so the six words decode to finite floats)
+    float lo[3], hi[3];
+#pragma unroll
+    for (int a = 0; a < 3; ++a)
+    {
+      lo[a] = recut_decode(P.box[a]);
+      hi[a] = recut_decode(~P.box[3 + a]);
+    }
+    key = recut_key(s, lo, recut_scale(lo, hi));
+  }
+  P.keys[j] = key;
+}
+
+__global__ __launch_bounds__(kUpdateThreads) void recut_place_kernel(const RecutPlaceParams P)
+{
+  const uint32_t q = blockIdx.x * kUpdateThreads + threadIdx.x;
+  if (q < P.nodes_n)
+  {
+    P.nodes[q].child[0] = P.cut_child[2 * (size_t)q];
+    P.nodes[q].child[1] = P.cut_child[2 * (size_t)q + 1];
+    P.hlist[q] = P.cut_hlist[q];
+  }
+  if (q >= P.slots) return;
+  const int32_t t = P.order[q];
+  if (t < 0)
+  {
+    P.tri_leaf[q] = TriGeo{};
+    return;
+  }
+  TriGeo l = P.tri_geo[t];
+  l.pad[0] = __builtin_bit_cast(float, t);
+  l.pad[1] = __builtin_bit_cast(float, P.tri_shade[t].obj);
+  P.tri_leaf[q] = l;
+  P.slot[t] = (int32_t)q;
+}
+
 static dim3 update_grid(uint32_t n) { return dim3((n + kUpdateThreads - 1) / kUpdateThreads); }
+
+hipError_t launch_recut_keys(const RecutParams &P, hipStream_t st)
+{
+  hipError_t e = hipMemsetAsync(P.box, 0xFF, 6 * sizeof(uint32_t), st);
+  if (e != hipSuccess) return e;
+  hipLaunchKernelGGL(recut_box_kernel, update_grid(P.n), dim3(kUpdateThreads), 0, st, P);
+  hipLaunchKernelGGL(recut_keys_kernel, update_grid(P.n), dim3(kUpdateThreads), 0, st, P);
+  return hipGetLastError();
+}
+
+hipError_t launch_recut_place(const RecutPlaceParams &P, hipStream_t st)
+{
+  hipLaunchKernelGGL(recut_place_kernel, update_grid(P.slots), dim3(kUpdateThreads), 0, st, P);
+  return hipGetLastError();
+}
 
 hipError_t launch_update_tris(const UpdateParams &P, hipStream_t st)
 {

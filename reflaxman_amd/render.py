@@ -225,6 +225,30 @@ class Scene:
                                                   _lib.fptr(mt)), "Scene.tri_bvh_refit")
         return boxes, mt
 
+    def tri_bvh_recut(self, cut_vertices, vertices=None, widen: bool = False):
+        """This scene's triangle BVH re-cut on the host at `cut_vertices` and fitted to `vertices` (None: the cut's), as
+        Renderer.recut_triangles does it on the device (rfx.h "Re-cutting", rfx_scene_tri_bvh_recut): tri_bvh_dump's
+        dict -- the in-tree set and the residual list stay this scene's -- plus mt (nodes, 2), or None without a tree."""
+        d = self.tri_bvh_dump()
+        if d is None:
+            return None
+        n = self.counts()[1]
+        cut = np.ascontiguousarray(cut_vertices, dtype=np.float32).reshape(-1, 9)
+        fit = cut if vertices is None else np.ascontiguousarray(vertices, dtype=np.float32).reshape(-1, 9)
+        if cut.shape[0] != n or fit.shape[0] != n:
+            raise ValueError("tri_bvh_recut: vertices for every triangle of the scene")
+        cnt = (C.c_int32 * 5)()
+        boxes, mt = np.zeros((d["nodes"], 2, 6), np.float32), np.zeros((d["nodes"], 2), np.float32)
+        children, ids = np.zeros((d["nodes"], 2), np.int32), np.zeros((d["leaves"], d["leaf_size"]), np.int32)
+        i32 = lambda a: a.ctypes.data_as(_lib._i32p)
+        if check(_lib.load().rfx_scene_tri_bvh_recut(self._h, _lib.fptr(cut), None if vertices is None else _lib.fptr(fit),
+                                                     int(bool(widen)), cnt, _lib.fptr(boxes), i32(children), i32(ids),
+                                                     _lib.fptr(mt)), "Scene.tri_bvh_recut") == 0:
+            return None
+        assert (cnt[0], cnt[1]) == (d["nodes"], d["leaves"])
+        return {"nodes": int(cnt[0]), "leaves": int(cnt[1]), "leaf_size": int(cnt[3]), "depth": int(cnt[4]), "boxes": boxes,
+                "children": children, "leaf_ids": ids, "residual": d["residual"], "mt": mt}
+
     def cull_dump(self):
         """The bundle-cull records of a small scene as a renderer would upload them (rfx.h rfx_scene_cull_dump; host
         only): (recs (64, 8), tris (32, 12), valid lanes as an int)."""
@@ -448,6 +472,15 @@ class Renderer:
         check(L.rfx_renderer_update_triangles_host(self._h, int(first), n, _lib.fptr(p), p.shape[0],
                                                    _lib.u32ptr(idx) if idx is not None else None),
               "rfx_renderer_update_triangles_host")
+
+    def recut_triangles(self, stream=None):
+        """Re-cut the uploaded triangle BVH at the triangles' current vertices, on the device (rfx.h "Re-cutting",
+        rfx_renderer_recut_triangles): no value of any launch changes, only how fast a moved mesh is traced.
+        Stream-ordered with no host sync: stream is a raw stream pointer as render_frame takes it (an update from torch
+        tensors runs on torch's current stream: pass that one), None the renderer's own.  Raises without a triangle
+        tree."""
+        check(_lib.load().rfx_renderer_recut_triangles(self._h, C.c_void_p(stream or None)),
+              "rfx_renderer_recut_triangles")
 
     def tri_records(self, first: int = 0, count: Optional[int] = None) -> np.ndarray:
         """The uploaded triangles' words that follow their vertices, read back (rfx.h rfx_renderer_tri_records;

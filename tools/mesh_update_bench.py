@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
-"""Moving meshes (GPU box): what rfx_renderer_update_triangles costs against rfx_renderer_set_scene of the moved scene,
-and what a frame costs on a refitted tree against a freshly built one -- ONE process on ONE GPU, the arms alternating
-round by round (medians over the rounds), in the manner of tools/hits_bench.py.
+"""Moving meshes (GPU box): what rfx_renderer_update_triangles and rfx_renderer_recut_triangles cost against
+rfx_renderer_set_scene of the moved scene, and what a frame costs on a refitted (stale) tree, on a re-cut tree and on a
+freshly built one -- ONE process on ONE GPU, the arms alternating round by round (medians over the rounds), in the
+manner of tools/hits_bench.py.
 
     python tools/mesh_update_bench.py --scene mesh40x32 [--rounds R] [--calls F] [--out DIR]
     python tools/mesh_update_bench.py --scene soup100000 ...
@@ -14,16 +15,21 @@ Update cost, per call:
     update_all      the whole mesh's vertices (device array, 9 floats a triangle) and the whole tree's refit: F calls
                     between two device events, R rounds (R F >= 200 calls)
     update_1pct     the same for a range of 1% of the triangles (the refit is still the whole tree's)
+    recut           rfx_renderer_recut_triangles at the vertices the last update left: keys, sort, leaf records,
+                    topology and the whole tree's refit, timed the same way
     set_scene       rfx_renderer_set_scene of the host scene moved to the same vertices: a host clock around the call,
                     which ends synchronised -- the only way to move a mesh before this entry point; scene_edit is the
                     host's rfx_scene_set_triangle_vertices before it
 Trace cost after a refit, per deformation (wave: every vertex on a height wave of amplitude 0.1; shuffle: every triangle
 moved by up to +-6 units on each axis, so the topology cut at the old positions is stale):
-    frame_refit     frames on a renderer that got the old scene and then the update
+    frame_refit     frames on a renderer that got the old scene and then the update: the stale tree
+    frame_recut     ... and then the re-cut
     frame_fresh     frames on a renderer whose set_scene got the moved scene
-Before timing the two renderers' frames must be equal word for word from one stream state.  Frames are W x H, depth D
-(--frame W H D), G frames between two device events (--frames G).  One JSON object goes to stdout and to
-DIR/mesh_update_<scene>.json (default profiles/r21).
+Before timing the three renderers' frames must be equal word for word from one stream state.  Frames are W x H, depth D
+(--frame W H D), G frames between two device events (--frames G).  Beside each arm's time goes its tree's quality, a
+surface-area figure computed here from rfx_renderer_tri_bvh_nodes: the sum of every finite child box's area over the
+root box's area (the expected number of boxes a random line through the root meets; lower is better).  One JSON object
+goes to stdout and to DIR/mesh_update_<scene>.json (default profiles/r23).
 """
 import argparse
 import ctypes as C
@@ -75,6 +81,19 @@ def deform(V, kind):
     return V
 
 
+def sah(nodes):
+    """sum of the finite child boxes' areas over the area of the root box -- the union of the finite boxes: a tree with
+    an ill triangle under each child of the root has no finite box at the top -- and how many child boxes are all of
+    space (NaN), which the sum leaves out though every ray descends through them"""
+    boxes = nodes[0].astype(np.float64).reshape(-1, 6)
+    finite = np.isfinite(boxes).all(axis=1)
+    boxes = boxes[finite]
+    d = boxes[:, 3:] - boxes[:, :3]
+    area = d[:, 0] * d[:, 1] + d[:, 1] * d[:, 2] + d[:, 2] * d[:, 0]
+    r = boxes[:, 3:].max(axis=0) - boxes[:, :3].min(axis=0)
+    return {"sah": float(area.sum() / (r[0] * r[1] + r[1] * r[2] + r[2] * r[0])), "all_space_boxes": int((~finite).sum())}
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--scene", choices=("mesh40x32", "soup100000"), default="mesh40x32")
@@ -82,7 +101,7 @@ def main():
     ap.add_argument("--calls", type=int, default=40, help="update calls per timed window")
     ap.add_argument("--frames", type=int, default=4, help="frames per timed window")
     ap.add_argument("--frame", type=int, nargs=3, default=(1280, 720, 6), metavar=("W", "H", "D"))
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "r21"))
+    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "r23"))
     args = ap.parse_args()
     import torch
     if not torch.cuda.is_available():
@@ -95,7 +114,7 @@ def main():
     sp = C.c_void_p(stream.cuda_stream)
     W, H, D = args.frame
     frame = make_frame(cam, W, H, D, 1)
-    img = [torch.zeros(H * W * 3, dtype=torch.float32, device="cuda") for _ in range(2)]
+    img = [torch.zeros(H * W * 3, dtype=torch.float32, device="cuda") for _ in range(3)]
 
     def renderer():
         r = Renderer(sphere_seed=SEED, jitter_seed=0)
@@ -132,14 +151,18 @@ def main():
         _lib.check(L.rfx_renderer_update_triangles(ru._h, n // 2, one, C.c_void_p(d_v[flip[0]].data_ptr() + 36 * (n // 2)),
                                                    3 * one, None, sp))
 
+    def recut():
+        _lib.check(L.rfx_renderer_recut_triangles(ru._h, sp))
+
     rs = renderer()
-    t = {"update_all": [], "update_1pct": [], "set_scene": [], "scene_edit": []}
-    for fn in (upd_all, upd_part):  # warm-up: code objects loaded, every shape once
+    t = {"update_all": [], "update_1pct": [], "recut": [], "set_scene": [], "scene_edit": []}
+    for fn in (upd_all, upd_part, recut):  # warm-up: code objects loaded, every shape once
         window(fn, 4)
     rs.set_scene(scene)
     for rnd in range(args.rounds):
         t["update_all"].append(window(upd_all, args.calls))
         t["update_1pct"].append(window(upd_part, args.calls))
+        t["recut"].append(window(recut, args.calls))
         v = V1 if rnd % 2 == 0 else V0
         t0 = time.perf_counter()
         _lib.check(L.rfx_scene_set_triangle_vertices(scene._h, 0, n, _lib.fptr(v)))
@@ -155,6 +178,7 @@ def main():
            "ms": {k: {"median": statistics.median(v), "min": min(v), "max": max(v)} for k, v in t.items()},
            "device_sha256": _lib.device_sha256()}
     out["set_scene_over_update_all"] = out["ms"]["set_scene"]["median"] / out["ms"]["update_all"]["median"]
+    out["set_scene_over_recut"] = out["ms"]["set_scene"]["median"] / out["ms"]["recut"]["median"]
     ru.close()
     rs.close()
 
@@ -163,31 +187,40 @@ def main():
     out["trace"] = {}
     for kind in ("wave", "shuffle"):
         Vk = deform(V0, kind)
-        refit, fresh = renderer(), renderer()
-        _lib.check(L.rfx_renderer_set_scene(refit._h, scene._h))  # the old positions' tree
+        refit, cut, fresh = renderer(), renderer(), renderer()
         d_k = torch.from_numpy(Vk).cuda()
         stream.synchronize()
-        _lib.check(L.rfx_renderer_update_triangles(refit._h, 0, n, C.c_void_p(d_k.data_ptr()), 3 * n, None, sp))
+        for r in (refit, cut):
+            _lib.check(L.rfx_renderer_set_scene(r._h, scene._h))  # the old positions' tree
+            _lib.check(L.rfx_renderer_update_triangles(r._h, 0, n, C.c_void_p(d_k.data_ptr()), 3 * n, None, sp))
+        _lib.check(L.rfx_renderer_recut_triangles(cut._h, sp))
         _lib.check(L.rfx_scene_set_triangle_vertices(scene._h, 0, n, _lib.fptr(Vk)))
         _lib.check(L.rfx_renderer_set_scene(fresh._h, scene._h))
         _lib.check(L.rfx_scene_set_triangle_vertices(scene._h, 0, n, _lib.fptr(V0)))
-        arms = {"frame_refit": (refit, img[0]), "frame_fresh": (fresh, img[1])}
+        arms = {"frame_refit": (refit, img[0]), "frame_recut": (cut, img[1]), "frame_fresh": (fresh, img[2])}
         for r, buf in arms.values():
             r.set_rng(SEED, 0)
             r.render_frame(frame, buf.data_ptr(), stream=stream.cuda_stream)
         stream.synchronize()
-        if not torch.equal(img[0], img[1]):
-            sys.exit(f"mesh_update_bench: {kind}: the refitted renderer's frame differs from the fresh one's")
+        if not (torch.equal(img[0], img[2]) and torch.equal(img[1], img[2])):
+            sys.exit(f"mesh_update_bench: {kind}: the refitted or the re-cut renderer's frame differs from the fresh one's")
         tk = {k: [] for k in arms}
         for rnd in range(args.rounds):
-            for k in (list(arms) if rnd % 2 == 0 else list(arms)[::-1]):
+            for k in (list(arms)[rnd % 3:] + list(arms)[:rnd % 3]):
                 r, buf = arms[k]
                 tk[k].append(window(lambda: r.render_frame(frame, buf.data_ptr(), stream=stream.cuda_stream), args.frames))
         out["trace"][kind] = {k: {"median": statistics.median(v), "min": min(v), "max": max(v)} for k, v in tk.items()}
         out["trace"][kind]["refit_over_fresh"] = (out["trace"][kind]["frame_refit"]["median"] /
                                                   out["trace"][kind]["frame_fresh"]["median"])
+        out["trace"][kind]["recut_over_fresh"] = (out["trace"][kind]["frame_recut"]["median"] /
+                                                  out["trace"][kind]["frame_fresh"]["median"])
+        out["trace"][kind]["refit_over_recut"] = (out["trace"][kind]["frame_refit"]["median"] /
+                                                  out["trace"][kind]["frame_recut"]["median"])
         out["trace"][kind]["fresh_residual"] = fresh.accel_info().tri_residual
+        out["trace"][kind]["sah"] = {k: sah(r.tri_bvh_nodes()) for k, (r, _) in arms.items()}
+        out["trace"][kind]["tri_depth"] = {k: r.accel_info().tri_depth for k, (r, _) in arms.items()}
         refit.close()
+        cut.close()
         fresh.close()
     os.makedirs(args.out, exist_ok=True)
     line = json.dumps(out)
