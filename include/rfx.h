@@ -669,6 +669,17 @@ int rfx_scene_tri_bvh_refit(const rfx_scene *built, const float *vertices9_all, 
 /* The uploaded triangle BVH's nodes read back (synchronises): 16 words per node -- 12 box floats in the dump's layout,
  * the 2 children as int32, the 2 margin terms.  Returns the node count (0: no tree); out may be NULL to ask for it. */
 int rfx_renderer_tri_bvh_nodes(rfx_renderer *r, float *out);
+/* The uploaded triangle BVH's leaves read back (host only; synchronises the renderer's stream), as the last
+ * rfx_renderer_set_scene or rfx_renderer_recut_triangles left them and the updates since rewrote them.  Returns the slot
+ * count, leaves x (triangles per leaf), or 0 without a tree; any of the arrays may be NULL:
+ *   leaf_ids : one int32 per slot -- the leaf membership the refit reads, in rfx_scene_tri_bvh_dump's leaf_ids layout;
+ *   slot     : one int32 per triangle of the scene -- the slot an update writes the triangle's leaf record to, -1 for a
+ *              triangle outside the tree;
+ *   records  : 14 words per slot, read by position (not through `slot`): the leaf record's twelve geometry words, then
+ *              the triangle index and the object index as stored (a padding slot: fourteen zero words).  Every NaN is
+ *              reported as 0x7FC00000, as in rfx_renderer_tri_records.
+ * Errors: NULL renderer: RFX_ERR_ARG; no scene uploaded: RFX_ERR_STATE. */
+int rfx_renderer_tri_leaves(rfx_renderer *r, int32_t *leaf_ids, int32_t *slot, uint32_t *records);
 
 /* ---------------------------------------------------------------- Re-cutting
  * The other half of moving meshes: rfx_renderer_update_triangles keeps the tree's topology as rfx_renderer_set_scene cut

@@ -176,6 +176,7 @@ SIGNATURES = [
     ("rfx_renderer_tri_records", C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, _u32p]),
     ("rfx_scene_tri_bvh_refit", C.c_int, [C.c_void_p, _fp, C.c_int, _fp, _fp]),
     ("rfx_renderer_tri_bvh_nodes", C.c_int, [C.c_void_p, _fp]),
+    ("rfx_renderer_tri_leaves", C.c_int, [C.c_void_p, _i32p, _i32p, _u32p]),
     ("rfx_renderer_recut_triangles", C.c_int, [C.c_void_p, C.c_void_p]),
     ("rfx_scene_tri_bvh_recut", C.c_int, [C.c_void_p, _fp, _fp, C.c_int, _i32p, _fp, _i32p, _i32p, _fp]),
     ("rfx_group_create", C.c_int, [C.POINTER(C.c_void_p), C.POINTER(C.c_int), C.c_int]),

@@ -2,6 +2,7 @@
 // rfx_renderer_recut_triangles, the tables set_scene uploads for them, and the read-backs the tests compare with the host
 // mirrors (rfx_scene.cpp).  The kernels are rfx_update_kernels.hip (and, for the re-cut's sort, rfx_order_sort.hip
 // through rfx_order.cpp's order_sort); every formula is rfx_refit.h's, shared with the host builder.
+#include <stddef.h>
 #include <string.h>
 
 #include <vector>
@@ -233,4 +234,29 @@ extern "C" int rfx_renderer_tri_bvh_nodes(rfx_renderer *r, float *out)
     o[14] = q.mt[0]; o[15] = q.mt[1];
   }
   return n;
+}
+
+extern "C" int rfx_renderer_tri_leaves(rfx_renderer *r, int32_t *leaf_ids, int32_t *slot, uint32_t *records)
+{
+  RCHECK(enter_call(r, true, "renderer_tri_leaves", "a renderer"));
+  const DevScene &d = r->dev;
+  if (!d.n_tri_bvh || !d.tri_bvh || !d.tri_leaf || !r->upd_tris) return 0;
+  const size_t slots = (size_t)r->upd_leaves * RFX_TRI_BVH_LEAF;
+  HIP_CHECK(hipStreamSynchronize(r->stream));
+  if (leaf_ids) HIP_CHECK(hipMemcpy(leaf_ids, r->upd_order.p, 4 * slots, hipMemcpyDeviceToHost));
+  if (slot) HIP_CHECK(hipMemcpy(slot, r->upd_slot.p, 4 * (size_t)r->upd_tris, hipMemcpyDeviceToHost));
+  if (records && slots)
+  {
+    std::vector<TriGeo> leaf(slots);
+    HIP_CHECK(hipMemcpy(leaf.data(), d.tri_leaf, slots * sizeof(TriGeo), hipMemcpyDeviceToHost));
+    static_assert(offsetof(TriGeo, pad) == 48, "twelve geometry words, then pad[0] and pad[1]");
+    for (size_t q = 0; q < slots; ++q)
+    {
+      uint32_t *o = records + 14 * q;
+      memcpy(o, &leaf[q], 56);
+      for (int k = 0; k < 14; ++k)
+        if ((o[k] & 0x7FFFFFFFu) > 0x7F800000u) o[k] = 0x7FC00000u;  // as tri_record_words reports a NaN
+    }
+  }
+  return (int)slots;
 }

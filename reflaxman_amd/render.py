@@ -479,6 +479,7 @@ class Renderer:
         Stream-ordered with no host sync: stream is a raw stream pointer as render_frame takes it (an update from torch
         tensors runs on torch's current stream: pass that one), None the renderer's own.  Raises without a triangle
         tree."""
+        self._scene_key = None  # (as after an update: a later set_scene(scene) uploads again, and restores the built tree)
         check(_lib.load().rfx_renderer_recut_triangles(self._h, C.c_void_p(stream or None)),
               "rfx_renderer_recut_triangles")
 
@@ -500,6 +501,21 @@ class Renderer:
         out = np.zeros((n, 16), np.float32)
         check(L.rfx_renderer_tri_bvh_nodes(self._h, _lib.fptr(out)), "rfx_renderer_tri_bvh_nodes")
         return out[:, :12].reshape(n, 2, 6).copy(), out[:, 12:14].copy().view(np.int32), out[:, 14:16].copy()
+
+    def tri_leaves(self):
+        """The uploaded triangle BVH's leaves read back (rfx.h rfx_renderer_tri_leaves; synchronises): (leaf_ids
+        (leaves, 4) int32, slot (triangles,) int32, records (slots, 14) uint32 by position), or None without a tree."""
+        L = _lib.load()
+        slots = check(L.rfx_renderer_tri_leaves(self._h, None, None, None), "rfx_renderer_tri_leaves")
+        if slots == 0:
+            return None
+        leaf = self.accel_info().tri_leaf_size
+        ids = np.zeros((slots // leaf, leaf), np.int32)
+        slot = np.zeros(self._scene_ref.counts()[1], np.int32)
+        rec = np.zeros((slots, 14), np.uint32)
+        i32 = lambda a: a.ctypes.data_as(_lib._i32p)
+        check(L.rfx_renderer_tri_leaves(self._h, i32(ids), i32(slot), _lib.u32ptr(rec)), "rfx_renderer_tri_leaves")
+        return ids, slot, rec
 
     def set_rng(self, sphere_seed: int, jitter_seed: int):
         check(_lib.load().rfx_renderer_set_rng(self._h, sphere_seed & 0xFFFFFFFF, jitter_seed & 0xFFFFFFFF), "set_rng")

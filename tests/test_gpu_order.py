@@ -170,6 +170,68 @@ def test_order_is_the_stable_argsort_of_the_keys():
     r.close()
 
 
+# Past 256 workgroups order_scan_kernel walks a digit's row of per-workgroup counts in more than one chunk of 256, with a
+# carry: 256, 257 and 516 workgroups run the loop's body once, twice and three times, the last chunk partial.
+BIG = (515 * T + 5, 256 * T, 256 * T + 1)
+_BIG_RAYS = {}
+
+
+def big_rays(r, n):
+    """n rays on the `default` renderer r: the first half repeated_rays (heavy ties across workgroups), the second half
+    seeded uniform origins over the box order_box() reports with seeded random directions of mixed sign.  Both halves
+    are drawn once for the largest n and cut to size."""
+    if not _BIG_RAYS:
+        half = (max(BIG) + 1) // 2
+        lo, scale = r.order_box()
+        assert (scale > 0).all()
+        hi = lo + np.float32(1 << oh.CB) / scale
+        rng = np.random.default_rng(20240)
+        uni = np.concatenate([rng.uniform(lo, hi, (half, 3)), rng.normal(size=(half, 3))], axis=1).astype(np.float32)
+        assert all((uni[:, 3 + a] < 0).any() and (uni[:, 3 + a] > 0).any() for a in range(3))
+        _BIG_RAYS.update(rep=repeated_rays(half), uni=uni)
+    return np.concatenate([_BIG_RAYS["rep"][:n // 2], _BIG_RAYS["uni"][:n - n // 2]])
+
+
+def test_order_past_256_workgroups():
+    """One renderer, the scratch reused downward and up again: 516, 256 and 257 workgroups.  Every one of the 256 digit
+    values occurs in each of the four passes, so every row of the scan's table carries counts across its chunks."""
+    r, s, cam = renderer("default")
+    assert [-(-n // T) for n in BIG] == [516, 256, 257]
+    for n in BIG:
+        rays = big_rays(r, n)
+        order, keys = check_sort(r, rays, ("big", n))
+        for p in range(4):
+            seen = np.bincount((keys >> np.uint32(8 * p)) & np.uint32(255), minlength=256)
+            assert (seen > 0).all(), (n, p, np.flatnonzero(seen == 0).tolist())
+        assert len(np.unique(keys[:n // 2])) < n // 64  # the first half's keys repeat heavily
+    r.close()
+
+
+def test_paths_order_past_256_workgroups():
+    """rfx_paths_order at the same scale: 256 T + 100 paths begun without a draw, an index array of 256 T + 200 slots of
+    which 100 name no path -- the stable order of the restated keys, the 100 dead entries last, in index order"""
+    n, slots = 256 * T + 100, 256 * T + 200
+    r, s, cam = renderer("default")
+    rays = big_rays(r, n)
+    rng = np.random.default_rng(77)
+    index = np.concatenate([rng.permutation(n), n + 1000 * np.arange(99), [0xFFFFFFFF]]).astype(np.uint32)[rng.permutation(slots)]
+    real = index < n
+    assert (~real).sum() == 100 and -(-slots // T) == 257
+    before = r.get_rng()
+    p = r.paths(rays, draw=False)
+    got = p.order(index)
+    p.close()
+    assert r.get_rng() == before
+    k = np.full(slots, 0xFFFFFFFF, np.uint32)
+    k[real] = oh.keys(rays[index[real]], *r.order_box())
+    assert (k[real] != 0xFFFFFFFF).all()
+    want = index[oh.order(k)]
+    bad = np.flatnonzero(got != want)
+    assert bad.size == 0, (bad[:8].tolist(), got[bad[:8]].tolist(), want[bad[:8]].tolist())
+    assert np.array_equal(got[-100:], index[~real])
+    r.close()
+
+
 @pytest.mark.parametrize("n", [65, T + 1, 3 * T + 5])
 def test_order_of_special_inputs(n):
     """All rays identical: the identity (stability); two alternating rays: one's indices, then the other's; input

@@ -18,14 +18,16 @@ _BIG = {}
 
 
 def case(key):
-    """(description, built Scene, camera) of a case; soup4200 (more in-tree triangles than the sort's tile) is this file's"""
-    if key != "soup4200":
+    """(description, built Scene, camera) of a case; soup4200 (more in-tree triangles than the sort's tile) and the leaf-count
+    edges soup63 and soup64 (tests/test_tri_recut_host.py test_leaf_edges) are this file's"""
+    own = {"soup4200": 4200, "soup63": 61, "soup64": 62}  # (the soup's two ground triangles come on top)
+    if key not in own:
         return (desc_of(key), *built(key))
-    if not _BIG:
+    if key not in _BIG:
         from reflaxman_amd.render import build_scene
-        desc = scenes.soup_scene(4200)
-        _BIG["c"] = (desc, *build_scene(desc))
-    return _BIG["c"]
+        desc = scenes.soup_scene(own[key])
+        _BIG[key] = (desc, *build_scene(desc))
+    return _BIG[key]
 
 
 def mirror_nodes(s, cut, fit=None):
@@ -44,7 +46,7 @@ def check_records(rr, desc, V):
 
 
 # ------------------------------------------------------------------------------------------------ nodes and records
-@pytest.mark.parametrize("key", ["mesh", "degenerate", "soup33", "soup4200"])
+@pytest.mark.parametrize("key", ["mesh", "degenerate", "soup33", "soup4200", "soup63", "soup64"])
 def test_nodes_equal_the_mirror_and_stay_in_step(key):
     desc, s, _ = case(key)
     V = tri_vertices(desc)
@@ -76,6 +78,100 @@ def test_nodes_equal_the_mirror_and_stay_in_step(key):
     b = rr.tri_bvh_nodes()
     assert same_nodes(a, b) and same_nodes(a, mirror_nodes(s, second))
     check_records(rr, desc, second)
+    rr.close()
+
+
+# ------------------------------------------------------------------------------------------------ degenerate cuts
+def degenerate_cuts():
+    """{case: (X, placed, ill)}: the vertex sets of tests/test_tri_recut_host.py's box edge cases and the ones only the
+    device's box reduction can get wrong -- an empty box, one and two placed triangles, an extent that overflows, a
+    non-finite sum from finite vertices -- with the placed and ill counts of the restatement on the CPU"""
+    if "cuts" not in _BIG:
+        V = tri_vertices(case("mesh")[0])
+        n = len(V)
+        S = rh.shuffle(V)
+        c = {"same": (np.broadcast_to(V[5], V.shape).copy(), n, 0)}
+        flat = V.copy()
+        flat[..., 1] = 0.0
+        c["flat"] = (flat, n, 0)
+        for tag, pick in (("even", slice(0, None, 2)), ("first", slice(0, 1)), ("all", slice(None))):
+            signed = flat.copy()
+            signed[pick, :, 1] = -0.0
+            c["signed_zero_" + tag] = (signed, n, 0)
+        step = flat.copy()
+        step[::3, :, 1] = 4.0
+        step[1::3, :, 1] = -0.0
+        c["zero_bound"] = (step, n, 0)
+        far = S.copy()
+        far[0::2, :, 0] += F(1e38)
+        far[1::2, :, 0] -= F(1e38)
+        c["overflow_extent"] = (far, 344, 40)
+        inf = S.copy()
+        inf[7, :, 2] = 2e38
+        c["inf_sum"] = (inf, n - 1, 0)
+        ill = S.copy()
+        ill[:, 2] = ill[:, 1]
+        c["all_ill"] = (ill, 0, n)
+        one = ill.copy()
+        one[100] = S[100]
+        c["one_placed"] = (one, 1, n - 1)
+        two = one.copy()
+        two[300] = S[300]
+        c["two_placed"] = (two, 2, n - 2)
+        _BIG["cuts"] = c
+    return _BIG["cuts"]
+
+
+CUTS = ["same", "flat", "signed_zero_even", "signed_zero_first", "signed_zero_all", "zero_bound", "overflow_extent",
+        "inf_sum", "all_ill", "one_placed", "two_placed"]
+# the mesh is out of the 4,096 rays' reach in overflow_extent (x = +-1e38): they hit the eight spheres alone, 341 times
+# by the reference composed on the CPU (hits_helpers.compose), so that case's full check asks for 300 hits, not 1,000
+FULL = {"all_ill": 1000, "one_placed": 1000, "overflow_extent": 300}
+
+
+@pytest.mark.parametrize("name", CUTS)
+def test_degenerate_cuts_equal_the_mirror(name):
+    """update to X, re-cut: the tree, membership, slots and leaf records are the host mirror's and the float32
+    restatement's, where the device's integer box reduction and the host's fminf / fmaxf fold take different roads; a tree
+    that is all NaN spines still gives a fresh renderer's words"""
+    import mesh_sequence as ms
+    from test_gpu_mesh_sequences import cheap_checks, full_check
+    X, placed, ill = degenerate_cuts()[name]
+    m = ms.Model("mesh")
+    classes = rh.classes(m.desc, X)
+    want = rh.restated(X, classes, m.tree)
+    assert (int(want["placed"].sum()), int(classes.sum())) == (placed, ill)
+    keys = want["keys"]
+    if name in ("same", "one_placed", "overflow_extent"):
+        assert want["scale"] == 0 and set(keys[want["placed"]].tolist()) == {0}
+    if name == "same":
+        assert np.array_equal(want["leaf_ids"].reshape(-1), m.tree)  # one key: index order
+    if name == "flat" or name.startswith("signed_zero"):
+        assert (keys & 0x12492492).sum() == 0 and want["scale"] > 0  # no y bit in any key
+        assert np.array_equal(want["leaf_ids"], rh.restated(degenerate_cuts()["flat"][0], classes, m.tree)["leaf_ids"])
+    if name == "zero_bound":
+        assert want["lo"][1] == 0 and want["hi"][1] == 12 and (keys & 0x12492492).any()
+    if name == "inf_sum":
+        assert classes[7] == 0 and not want["placed"][7] and keys[7] == rh.LAST_KEY  # well-conditioned, and not placed
+    if name == "all_ill":
+        assert want["lo"] is None and (keys == rh.LAST_KEY).all()
+    if name == "two_placed":
+        assert abs(float(want["scale"]) - 17.02) < 0.01
+    rr = renderer(m.scene, 1)
+    i = rr.accel_info()
+    info0 = (i.tri_nodes, i.tri_residual, i.tri_in_leaves)
+    rr.update_triangles(0, dev(X))
+    rr.recut_triangles()
+    m.apply(ms.Op("whole", 0, X))
+    m.apply(ms.Op("recut"))
+    e = m.expected()  # (scene.tri_bvh_recut(X, widen=True), and the records of the Scene edited to X)
+    assert np.array_equal(e["leaf_ids"], want["leaf_ids"]) and np.array_equal(e["children"], want["children"])
+    nan = int(np.isnan(e["boxes"]).any(axis=2).sum())
+    assert nan == {"overflow_extent": 23, "all_ill": 190, "one_placed": 190, "two_placed": 190}.get(name, 0), nan
+    cheap_checks(rr, m, e, info0, name)
+    assert np.array_equal(rr.tri_leaves()[0], want["leaf_ids"])
+    if name in FULL:
+        full_check(rr, m.desc, X, name, min_hits=FULL[name])
     rr.close()
 
 
