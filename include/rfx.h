@@ -624,8 +624,8 @@ int rfx_paths_order(rfx_renderer *r, const rfx_paths *p, uint64_t n, const uint3
  *
  * Works on non-small scenes (more than 32 spheres or more than 32 triangles), with or without a triangle BVH.  A small
  * scene is RFX_ERR_STATE: its 64 lane records, footprints and mate groups are uploaded again by
- * rfx_renderer_set_scene in microseconds.  Materials, textures, uv and object indices stay; spheres and lights do not
- * move.
+ * rfx_renderer_set_scene in microseconds.  Materials, textures, uv and object indices stay; spheres move by "Moving
+ * spheres" below, lights do not move.
  *
  * Triangles [first, first + count) take new vertices; `first` counts triangles in insertion order (0 = the scene's
  * first triangle, rfx_scene_tri_mates' numbering; rfx_scene_object_triangle maps an object index to it).
@@ -730,6 +730,90 @@ int rfx_renderer_recut_triangles(rfx_renderer *r, void *stream);
  * new depth), mt and widen as rfx_scene_tri_bvh_refit's; the arrays may be NULL.  Returns 1 with a tree, 0 without. */
 int rfx_scene_tri_bvh_recut(const rfx_scene *built, const float *cut_vertices9_all, const float *vertices9_all, int widen,
                             int32_t counts[5], float *boxes, int32_t *children, int32_t *leaf_ids, float *mt);
+
+/* ---------------------------------------------------------------- Moving spheres
+ * Spheres of the uploaded scene take new centres and radii on the device, stream-ordered, without the host rebuild and
+ * re-upload of rfx_renderer_set_scene.  (Added under RFX_ABI_VERSION 5; detect the calls by symbol.)
+ *
+ * Contract: after the call every launch on the renderer returns, word for word, what a renderer returns whose
+ * rfx_renderer_set_scene got the same scene built at the new spheres -- frames of every mode, rfx_trace_rays, the hit
+ * queries and spans, the ordered forms, rfx_paths_step -- settings, random streams and inputs being the same.  The update
+ * touches neither random stream (rfx_renderer_get_rng reads the same before and after), nor the tile costs, the timing
+ * sums, the regroup queue or the rewind state; it drops the per-view masks, as rfx_renderer_set_scene does.  The
+ * coherent order's key box (rfx_renderer_order_box) and the regroup sort's cells stay as rfx_renderer_set_scene computed
+ * them: they are schedule inputs, and no value depends on them.
+ *
+ * What follows a sphere (DESIGN.md "Moving spheres"): its centre and squared radius in both device forms, its bounding
+ * sphere, the bound of its 64-sphere chunk, and the pair tree's boxes -- every node refitted on every update from the
+ * current bounds alone, by the builder's own formulas, so repeated updates do not drift.  The device order of the spheres,
+ * the tree's topology and its margin reference point stay as built: only speed follows spheres that have moved far from
+ * where the tree was cut, and rfx_renderer_set_scene restores it.  Materials and object indices stay; lights do not move.
+ * A sphere that is not finite (a NaN or infinite centre or radius) is never hit, as in the reference; its bounds come
+ * out of the same formulas, and every cull keeps what it cannot bound.
+ *
+ * Works on every non-small scene (more than 32 spheres or more than 32 triangles): with a pair tree (more than 32
+ * spheres), without one (at most 32 spheres beside more than 32 triangles, or a tree the walkers cannot take), with or
+ * without a triangle tree.  A small scene is RFX_ERR_STATE: rfx_renderer_set_scene uploads it again in microseconds.
+ * rfx_renderer_update_spheres, rfx_renderer_update_triangles and rfx_renderer_recut_triangles may follow each other on
+ * one stream in any order.
+ *
+ * d_spheres4 holds four floats per record: centre x, y, z, then the radius.  The radius gets the constructor's clamp
+ * (Sphere.cpp:13-19, as rfx_scene_add_sphere: radius <= VERY_SMALL_NUMBER becomes VERY_SMALL_NUMBER; a NaN passes), and
+ * the squared radius is radius * radius in float.  `first` counts spheres in insertion order (0 = the scene's first
+ * sphere; rfx_scene_object_sphere maps an object index to it).
+ *   d_ids == NULL : spheres [first, first + count) take records 0 .. count - 1.
+ *   d_ids != NULL : `first` is ignored; record k goes to sphere d_ids[k].  An id >= the scene's sphere count is a dead
+ *                   lane (it cannot be an error without a sync).  Two records that name one sphere with different values
+ *                   are the caller's error: the sphere's arrays could each take a different winner.
+ * Stream-ordered (NULL = the renderer's stream), no host sync, no allocation.
+ * Errors: NULL renderer or spheres, count == 0, d_ids == NULL with first + count > the scene's spheres: RFX_ERR_ARG; no
+ * scene uploaded, or a small scene: RFX_ERR_STATE. */
+int rfx_renderer_update_spheres(rfx_renderer *r, uint32_t first, uint32_t count, const float *d_spheres4,
+                                const uint32_t *d_ids /* or NULL */, void *stream);
+/* The same on host arrays: copies them in on the renderer's stream and synchronises. */
+int rfx_renderer_update_spheres_host(rfx_renderer *r, uint32_t first, uint32_t count, const float *spheres4,
+                                     const uint32_t *ids /* or NULL */);
+/* The host scene kept in step: spheres [first, first + count) take the centres and (clamped) radii given.  Material and
+ * object index stay.  Read by the next rfx_renderer_set_scene. */
+int rfx_scene_set_spheres(rfx_scene *scene, uint32_t first, uint32_t count, const float *spheres4);
+/* The sphere index (insertion order among spheres) of an object, or RFX_ERR_ARG for a non-sphere. */
+int rfx_scene_object_sphere(const rfx_scene *scene, int object_index);
+/* The words that follow a sphere's centre and radius, RFX_SPH_RECORD_WORDS uint32 per sphere of [first, first + count)
+ * in insertion order, from the host scene and -- a device read-back, synchronises; not for a small scene -- from the
+ * uploaded one:
+ *   [0, 4)  the sphere's record: centre x y z, squared radius;
+ *   [4, 8)  its lane of its pair record (the same four; the host scene: words [0, 4) again);
+ *   [8, 12) its bounding sphere: centre x y z, radius * 1.00001f.
+ * Every NaN is reported as 0x7FC00000, as in rfx_scene_tri_records. */
+#define RFX_SPH_RECORD_WORDS 12
+int rfx_scene_sph_records(const rfx_scene *scene, uint32_t first, uint32_t count, uint32_t *out);
+int rfx_renderer_sph_records(rfx_renderer *r, uint32_t first, uint32_t count, uint32_t *out);
+/* The pair tree a renderer builds for the scene's spheres (host only): counts = {nodes, leaves, spheres per leaf,
+ * depth}; boxes -- nodes x 2 children x (lo x y z, hi x y z), as built, without the cull margin; children -- nodes x 2
+ * (>= 0 a node, < 0 the leaf ~c); leaf_ids -- leaves x (spheres per leaf) sphere indices of the insertion order, -1
+ * padding the last leaf; device_index -- per sphere of the insertion order its index in the device order (leaf g holds
+ * device indices [g L, g L + L), chunk k [64 k, 64 k + 64)), filled with or without a tree.  The arrays may be NULL.
+ * Returns 1 with a tree, 0 without (a small scene, at most 32 spheres, or a tree the walkers cannot take). */
+int rfx_scene_sph_bvh_dump(const rfx_scene *scene, int32_t counts[4], float *boxes, int32_t *children,
+                           int32_t *leaf_ids, uint32_t *device_index);
+/* The tree rfx_scene_sph_bvh_dump reports for `built` -- its topology, device order and reference point -- refitted on
+ * the host to the spheres given (4 floats for every sphere of the scene, insertion order), as the device update refits
+ * it: boxes and mt as rfx_scene_tri_bvh_refit's; chunk_bounds -- 4 floats per 64-sphere chunk of the device order
+ * (filled with or without a tree); any may be NULL.  widen = 0: the boxes as built (at the scene's own spheres: the
+ * dump's, bit for bit); widen = 1: the device copy.  Every NaN is reported as 0x7FC00000.  Returns 1 with a tree, 0
+ * without. */
+int rfx_scene_sph_bvh_refit(const rfx_scene *built, const float *spheres4_all, int widen, float *boxes, float *mt,
+                            float *chunk_bounds);
+/* The uploaded pair tree's nodes read back (synchronises): 16 words per node, as rfx_renderer_tri_bvh_nodes, every NaN
+ * reported as 0x7FC00000.  Returns the node count (0: no tree); out may be NULL to ask for it. */
+int rfx_renderer_sph_bvh_nodes(rfx_renderer *r, float *out);
+/* The uploaded chunk bounds read back (synchronises): 4 floats per chunk, NaNs as above.  Returns the chunk count; out
+ * may be NULL to ask for it. */
+int rfx_renderer_sph_chunk_bounds(rfx_renderer *r, float *out);
+/* The padding lanes of the uploaded pair records read back (synchronises): the second lane of an odd count's last pair
+ * and, with more than 32 spheres, the pairs that fill the last leaf -- 4 words per lane (centre 0, squared radius -inf:
+ * never hit).  No update writes them.  Returns the lane count; out may be NULL to ask for it. */
+int rfx_renderer_sph_padding(rfx_renderer *r, uint32_t *out);
 
 /* ---------------------------------------------------------------- Device groups (multi-GPU, one process)
  * A group renders the frame of Render::renderNext (Render.cpp:136-215) on several devices of this process: row bands,

@@ -21,7 +21,8 @@ INCLUDE = os.path.join(ROOT, "include")
 # the trace kernel families compile as separate TUs in parallel (one hipcc per source), then link
 SOURCES = ["rfx_kernels.hip", "rfx_host.cpp", "rfx_scene.cpp", "rfx_group.cpp", "rfx_kat.cpp", "rfx_rays.cpp", "rfx_trace_rays.hip",
            "rfx_hits.cpp", "rfx_trace_hits.hip", "rfx_span.cpp", "rfx_trace_span.hip", "rfx_order.cpp", "rfx_order_sort.hip", "rfx_trace_ordered.hip",
-           "rfx_paths.cpp", "rfx_trace_paths.hip", "rfx_trace_plain_park.hip", "rfx_update.cpp", "rfx_update_kernels.hip"] + [
+           "rfx_paths.cpp", "rfx_trace_paths.hip", "rfx_trace_plain_park.hip", "rfx_update.cpp", "rfx_update_kernels.hip",
+           "rfx_sphere_update_kernels.hip"] + [
     f"rfx_trace_{m}_{s}.hip" for m in ("plain", "ssaa", "lanes", "chunks", "block") for s in ("fast", "stats")]
 # every header, and every text a header includes (rfx_rays_body.inc), counts towards _sources_digest
 HEADERS = sorted(f for f in os.listdir(CSRC) if f.endswith((".h", ".inc")))

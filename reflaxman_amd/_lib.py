@@ -17,6 +17,7 @@ RFX_ABI_VERSION = 5
 # the coherent order's key widths and the sort's rays per workgroup (rfx.h "Coherent order")
 RFX_ORDER_CELL_BITS, RFX_ORDER_DIR_BITS, RFX_ORDER_TILE = 4, 10, 4096
 RFX_TRI_RECORD_WORDS = 41  # rfx.h "Moving meshes": words per triangle of rfx_scene_tri_records / rfx_renderer_tri_records
+RFX_SPH_RECORD_WORDS = 12  # rfx.h "Moving spheres": words per sphere of rfx_scene_sph_records / rfx_renderer_sph_records
 METAL, DIELECTRIC = 0, 1
 
 _fp = C.POINTER(C.c_float)
@@ -179,6 +180,17 @@ SIGNATURES = [
     ("rfx_renderer_tri_leaves", C.c_int, [C.c_void_p, _i32p, _i32p, _u32p]),
     ("rfx_renderer_recut_triangles", C.c_int, [C.c_void_p, C.c_void_p]),
     ("rfx_scene_tri_bvh_recut", C.c_int, [C.c_void_p, _fp, _fp, C.c_int, _i32p, _fp, _i32p, _i32p, _fp]),
+    ("rfx_renderer_update_spheres", C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]),
+    ("rfx_renderer_update_spheres_host", C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, _fp, _u32p]),
+    ("rfx_scene_set_spheres", C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, _fp]),
+    ("rfx_scene_object_sphere", C.c_int, [C.c_void_p, C.c_int]),
+    ("rfx_scene_sph_records", C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, _u32p]),
+    ("rfx_renderer_sph_records", C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, _u32p]),
+    ("rfx_scene_sph_bvh_dump", C.c_int, [C.c_void_p, _i32p, _fp, _i32p, _i32p, _u32p]),
+    ("rfx_scene_sph_bvh_refit", C.c_int, [C.c_void_p, _fp, C.c_int, _fp, _fp, _fp]),
+    ("rfx_renderer_sph_bvh_nodes", C.c_int, [C.c_void_p, _fp]),
+    ("rfx_renderer_sph_chunk_bounds", C.c_int, [C.c_void_p, _fp]),
+    ("rfx_renderer_sph_padding", C.c_int, [C.c_void_p, _u32p]),
     ("rfx_group_create", C.c_int, [C.POINTER(C.c_void_p), C.POINTER(C.c_int), C.c_int]),
     ("rfx_group_destroy", None, [C.c_void_p]),
     ("rfx_group_size", C.c_int, [C.c_void_p]),

@@ -221,6 +221,15 @@ struct rfx_renderer {
   std::vector<uint32_t> cut_hoff;
   int cut_depth = 0;
   uint32_t cut_tris = 0;
+  // moving spheres (rfx_update.cpp; filled by set_scene for a non-small scene with spheres, upd_sph its count, else 0):
+  // per sphere of the insertion order its device index; per 64-sphere chunk the update's dirty flag; the pair tree's
+  // nodes by height (sph_hoff: the heights' ends in sph_hlist) and the refit's unwidened boxes; the host form's staging
+  rfx::DevBuf<uint32_t> sph_slot, sph_dirty, sph_ids;
+  rfx::DevBuf<int32_t> sph_hlist;
+  rfx::DevBuf<rfx::SphBox> sph_lbox, sph_nbox;
+  rfx::DevBuf<float> sph_data;
+  std::vector<uint32_t> sph_hoff;
+  uint32_t upd_sph = 0;
   // per-phase event timing: triples {start, after pre-pass, after trace} on every timing_every-th frame (the events'
   // own cost stays off the other frames: ~10 us per frame for three records at C1's 640x480)
   bool timing = false, timing_this = false;

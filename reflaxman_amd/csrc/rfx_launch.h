@@ -98,4 +98,12 @@ struct RecutParams;
 struct RecutPlaceParams;
 hipError_t launch_recut_keys(const RecutParams &P, hipStream_t st);
 hipError_t launch_recut_place(const RecutPlaceParams &P, hipStream_t st);
+// ---- rfx_sphere_update_kernels.hip: moving spheres (rfx_refit.h) -- the updated spheres' records, the dirty chunks'
+// bounds, the pair tree's leaf boxes, and its nodes of one height from the boxes below them
+struct SphUpdateParams;
+struct SphRefitParams;
+hipError_t launch_update_spheres(const SphUpdateParams &P, hipStream_t st);
+hipError_t launch_refit_chunks(const SphRefitParams &P, hipStream_t st);
+hipError_t launch_refit_pair_leaves(const SphRefitParams &P, hipStream_t st);
+hipError_t launch_refit_pair_nodes(const SphRefitParams &P, hipStream_t st);
 }  // namespace rfx

@@ -256,4 +256,88 @@ struct RecutPlaceParams {
   uint32_t slots, nodes_n;
 };
 
+// ---- Moving spheres (rfx.h "Moving spheres"): what follows a sphere's centre and radius, shared by the host builder
+// (rfx_scene.cpp SceneBuild, sphere_bvh), the host mirror (rfx_scene_sph_bvh_refit) and the kernels
+// (rfx_sphere_update_kernels.hip).  None of it tests for a non-finite value: DESIGN.md "Moving spheres" has the argument.
+// Sphere.cpp:13-19 as rfx_scene_add_sphere runs it: the constructor's clamp (a NaN radius fails the compare and passes)
+RFX_HD float sphere_radius(float radius) { return radius <= kVerySmall ? kVerySmall : radius; }
+// a sphere's own bound for the wave-bundle cull: the radius grown by a relative 1e-5
+RFX_HD Bound sphere_bound(float cx, float cy, float cz, float radius)
+{
+  Bound b;
+  b.x = cx; b.y = cy; b.z = cz; b.r = radius * 1.00001f;
+  return b;
+}
+// The bound of a chunk of n <= 64 consecutive spheres of the device order from their bounds: centred on the mean centre,
+// a sequential double sum in device-index order (the order is part of the value), reaching the farthest sphere
+RFX_HD Bound sphere_chunk_bound(const Bound *bd, uint32_t n)
+{
+  double m[3] = {0.0, 0.0, 0.0};
+  for (uint32_t i = 0; i < n; ++i) { m[0] += bd[i].x; m[1] += bd[i].y; m[2] += bd[i].z; }
+  for (int k = 0; k < 3; ++k) m[k] /= (double)n;
+  double r = 0.0;
+  for (uint32_t i = 0; i < n; ++i)
+  {
+    const double dx = bd[i].x - m[0], dy = bd[i].y - m[1], dz = bd[i].z - m[2];
+    r = fmax(r, sqrt(dx * dx + dy * dy + dz * dz) + (double)bd[i].r);
+  }
+  Bound b;
+  b.x = (float)m[0]; b.y = (float)m[1]; b.z = (float)m[2]; b.r = (float)(r * 1.0001 + 1e-6);
+  return b;
+}
+// An unwidened box of the pair tree: six doubles (c -+ (double)bound.r does not fit the triangle tree's float RefitBox).
+// fmin / fmax drop a NaN, and the join is an exact min / max, so joining node by node gives the builder's range scan.
+struct alignas(16) SphBox { double lo[3], hi[3]; };
+RFX_HD void sph_box_empty(SphBox &b)
+{
+  for (int k = 0; k < 3; ++k) { b.lo[k] = INFINITY; b.hi[k] = -INFINITY; }
+}
+RFX_HD void sph_box_sphere(SphBox &b, const Bound &s)
+{
+  const double c[3] = {s.x, s.y, s.z}, rr = s.r;
+  for (int k = 0; k < 3; ++k) { b.lo[k] = fmin(b.lo[k], c[k] - rr); b.hi[k] = fmax(b.hi[k], c[k] + rr); }
+}
+RFX_HD void sph_box_join(SphBox &b, const SphBox &o)
+{
+  for (int k = 0; k < 3; ++k) { b.lo[k] = fmin(b.lo[k], o.lo[k]); b.hi[k] = fmax(b.hi[k], o.hi[k]); }
+}
+// the box of leaf g of the pair tree: the 2 RFX_BVH_LEAF_PAIRS spheres of the device order it holds, n_sph in all
+constexpr uint32_t kSphLeaf = 2 * RFX_BVH_LEAF_PAIRS;
+RFX_HD SphBox sph_leaf_box(const Bound *bd, uint32_t g, uint32_t n_sph)
+{
+  SphBox b;
+  sph_box_empty(b);
+  const uint32_t q0 = kSphLeaf * g, q1 = q0 + kSphLeaf < n_sph ? q0 + kSphLeaf : n_sph;
+  for (uint32_t q = q0; q < q1; ++q) sph_box_sphere(b, bd[q]);
+  return b;
+}
+
+// the per-sphere words rfx_scene_sph_records / rfx_renderer_sph_records report
+constexpr int kSphRecordWords = 12;
+
+// One launch of the sphere update (rfx_sphere_update_kernels.hip update_spheres_kernel): record k of `data` (centre,
+// radius) goes to sphere ids[k], or -- ids null -- first + k; a sphere index >= n_sph is a dead lane
+struct SphUpdateParams {
+  SphereGeo *sph_geo;
+  SpherePair *sph_pair;
+  Bound *bound;
+  uint32_t *dirty;        // per 64-sphere chunk: holds an updated sphere
+  const uint32_t *slot;   // insertion index -> device index
+  const float *data;
+  const uint32_t *ids;
+  uint32_t n_sph, first, count;
+};
+// ... and its refits: the dirty chunks' bounds (refit_chunks_kernel, n = chunks), the leaves' boxes
+// (refit_pair_leaves_kernel, n = leaves), then the nodes of one height (refit_pair_nodes_kernel, list[0 .. n))
+struct SphRefitParams {
+  BvhNode *nodes;
+  const Bound *bound;
+  Bound *chunk_bound;
+  uint32_t *dirty;
+  SphBox *leaf_box, *node_box;
+  const int32_t *list;
+  uint32_t n, n_sph;
+  double ref[3];          // DevScene::bvh_rx, bvh_ry, bvh_rz
+};
+
 }  // namespace rfx

@@ -534,6 +534,35 @@ int build_pair_bvh(std::vector<BvhNode> &nodes, std::vector<uint32_t> &pairs, si
   return id;
 }
 
+// The pair tree of a large scene's spheres (more than 32) from their bounds in device order: the leaves are groups of
+// RFX_BVH_LEAF_PAIRS consecutive pairs (compact clusters of the median-split order; rfx_refit.h sph_leaf_box, shared
+// with the refits), the reference point the root box centre as the float the kernel measures from.  Returns the depth;
+// no nodes (depth 0) for a tree deeper than the kernel's stack or larger than its int16 stack slots hold (rfx_bvh.h):
+// the chunk loops.
+int sphere_bvh(const std::vector<Bound> &bd, size_t nsph, bool widen, std::vector<BvhNode> &bvh, double *ref)
+{
+  const size_t npairs = ((nsph + 1) / 2 + RFX_BVH_LEAF_PAIRS - 1) / RFX_BVH_LEAF_PAIRS;
+  std::vector<PairBox> box(npairs);
+  for (size_t j = 0; j < npairs; ++j)
+  {
+    const SphBox b = sph_leaf_box(bd.data(), (uint32_t)j, (uint32_t)nsph);
+    for (int k = 0; k < 3; ++k) { box[j].lo[k] = b.lo[k]; box[j].hi[k] = b.hi[k]; box[j].c[k] = 0.5 * (b.lo[k] + b.hi[k]); }
+  }
+  std::vector<uint32_t> pairs(npairs);
+  for (size_t j = 0; j < npairs; ++j) pairs[j] = (uint32_t)j;
+  for (int k = 0; k < 3; ++k)
+  {
+    double lo = INFINITY, hi = -INFINITY;
+    for (const PairBox &pb : box) { lo = fmin(lo, pb.lo[k]); hi = fmax(hi, pb.hi[k]); }
+    ref[k] = (double)(float)(0.5 * (lo + hi));
+  }
+  int depth = 0;
+  bvh.clear();
+  build_pair_bvh(bvh, pairs, 0, npairs, box, ref, 0, depth, widen);
+  if (depth > kBvhStack || bvh.size() > 32767 || npairs > 32768) { bvh.clear(); depth = 0; }
+  return depth;
+}
+
 // the spatial order of build_tri_tree (below)
 void tri_spatial_order(std::vector<int32_t> &idx, size_t a, size_t b, const std::vector<double> &cen)
 {
@@ -1067,23 +1096,12 @@ SceneBuild::SceneBuild(const rfx_scene &scene, int tri_accel)
   for (uint32_t oi : order)
   {
     const HostSphere &hs = s->spheres[oi];
-    bd.push_back({hs.center.x, hs.center.y, hs.center.z, hs.radius * 1.00001f});
+    bd.push_back(sphere_bound(hs.center.x, hs.center.y, hs.center.z, hs.radius));
   }
-  // chunk bounds: 64 consecutive spheres of the device order, centred on their mean centre
+  // chunk bounds: 64 consecutive spheres of the device order, centred on their mean centre (rfx_refit.h, shared with the
+  // device update)
   for (size_t first = 0; first < nsph; first += 64)
-  {
-    const size_t last = std::min(nsph, first + 64);
-    double m[3] = {0.0, 0.0, 0.0};
-    for (size_t i = first; i < last; ++i) { m[0] += bd[i].x; m[1] += bd[i].y; m[2] += bd[i].z; }
-    for (double &v : m) v /= (double)(last - first);
-    double r = 0.0;
-    for (size_t i = first; i < last; ++i)
-    {
-      const double dx = bd[i].x - m[0], dy = bd[i].y - m[1], dz = bd[i].z - m[2];
-      r = fmax(r, sqrt(dx * dx + dy * dy + dz * dz) + (double)bd[i].r);
-    }
-    cb.push_back({(float)m[0], (float)m[1], (float)m[2], (float)(r * 1.0001 + 1e-6)});
-  }
+    cb.push_back(sphere_chunk_bound(&bd[first], (uint32_t)(std::min(nsph, first + 64) - first)));
   for (const HostTri &t : s->tris)
   {
     bd.push_back(tri_bound(t.v0, t.v1, t.v2, t.cond < 300.0));
@@ -1161,35 +1179,7 @@ SceneBuild::SceneBuild(const rfx_scene &scene, int tri_accel)
   // pair BVH (large scenes; spheres of a pair whose second slot is padding: r2 = -inf, never hit)
   int bvh_depth = 0;
   double bvh_ref[3] = {0.0, 0.0, 0.0};
-  if (nsph > 32)
-  {
-    // leaves: groups of RFX_BVH_LEAF_PAIRS consecutive pairs (compact clusters of the median-split order)
-    const size_t npairs = ((nsph + 1) / 2 + RFX_BVH_LEAF_PAIRS - 1) / RFX_BVH_LEAF_PAIRS;
-    constexpr size_t kLeafSph = 2 * RFX_BVH_LEAF_PAIRS;
-    std::vector<PairBox> box(npairs);
-    for (size_t j = 0; j < npairs; ++j)
-    {
-      PairBox &b = box[j];
-      for (int k = 0; k < 3; ++k) { b.lo[k] = INFINITY; b.hi[k] = -INFINITY; }
-      for (size_t q = kLeafSph * j; q < std::min(nsph, kLeafSph * j + kLeafSph); ++q)
-      {
-        const double c[3] = {bd[q].x, bd[q].y, bd[q].z}, rr = bd[q].r;
-        for (int k = 0; k < 3; ++k) { b.lo[k] = fmin(b.lo[k], c[k] - rr); b.hi[k] = fmax(b.hi[k], c[k] + rr); }
-      }
-      for (int k = 0; k < 3; ++k) b.c[k] = 0.5 * (b.lo[k] + b.hi[k]);
-    }
-    std::vector<uint32_t> pairs(npairs);
-    for (size_t j = 0; j < npairs; ++j) pairs[j] = (uint32_t)j;
-    for (int k = 0; k < 3; ++k)
-    {
-      double lo = INFINITY, hi = -INFINITY;
-      for (const PairBox &pb : box) { lo = fmin(lo, pb.lo[k]); hi = fmax(hi, pb.hi[k]); }
-      bvh_ref[k] = (double)(float)(0.5 * (lo + hi));  // the float the kernel measures from
-    }
-    build_pair_bvh(bvh, pairs, 0, npairs, box, bvh_ref, 0, bvh_depth);
-    if (bvh_depth > kBvhStack) { bvh.clear(); bvh_depth = 0; }  // deeper than the kernel's stack: chunk loops
-    if (bvh.size() > 32767 || npairs > 32768) { bvh.clear(); bvh_depth = 0; }  // int16 stack slots (rfx_bvh.h)
-  }
+  if (nsph > 32) bvh_depth = sphere_bvh(bd, nsph, true, bvh, bvh_ref);
   // triangle BVH (rfx_types.h RFX_TRI_BVH), when rfx_renderer_set_tri_accel asks for it: the nodes, the leaves' copy
   // of the triangle records and the residual list
   const bool want_tri = RFX_TRI_BVH && !small &&
@@ -1234,6 +1224,15 @@ SceneBuild::SceneBuild(const rfx_scene &scene, int tri_accel)
       cut = cut_topology(tt.leaves());
     }
   }
+  // ... and the sphere update's (rfx.h "Moving spheres"): insertion index -> device index, the pair tree's nodes by height
+  small_scene = small;
+  sslot.assign(nsph, 0u);
+  for (size_t di = 0; di < nsph; ++di) sslot[order[di]] = (uint32_t)di;
+  {
+    std::vector<int32_t> child;
+    for (const BvhNode &n : bvh) { child.push_back(n.child[0]); child.push_back(n.child[1]); }
+    height_lists(child, shlist, shoff);
+  }
   for (const HostPlane &p : s->planes)
   {
     pg.push_back({p.pos.x, p.pos.y, p.pos.z, p.norm.x, p.norm.y, p.norm.z, p.obj, p.mat.dielectric});
@@ -1242,12 +1241,10 @@ SceneBuild::SceneBuild(const rfx_scene &scene, int tri_accel)
   // object index -> (kind, index in the device arrays): spheres through their spatial order
   loc.assign(s->obj_kind.size(), 0);
   {
-    std::vector<int32_t> sph_dev(nsph);
-    for (size_t di = 0; di < nsph; ++di) sph_dev[order[di]] = (int32_t)di;
     for (size_t o = 0; o < loc.size(); ++o)
     {
       const int kind = s->obj_kind[o], idx = s->obj_idx[o];
-      loc[o] = kind << 28 | (kind == 0 ? sph_dev[idx] : idx);
+      loc[o] = kind << 28 | (kind == 0 ? (int32_t)sslot[idx] : idx);
     }
   }
   for (const HostLight &l : s->lights) lr.push_back(far_light_terms(l));
@@ -1508,5 +1505,131 @@ extern "C" int rfx_scene_tri_bvh_recut(const rfx_scene *built, const float *cut_
   if (children)
     for (size_t i = 0; i < nodes.size(); ++i) { children[2 * i] = nodes[i].child[0]; children[2 * i + 1] = nodes[i].child[1]; }
   if (leaf_ids) std::copy(order.begin(), order.end(), leaf_ids);
+  return 1;
+}
+
+// ============================================================== moving spheres (host side)
+// rfx.h "Moving spheres".  The device side is rfx_update.cpp / rfx_sphere_update_kernels.hip; both take every formula
+// from rfx_refit.h.
+extern "C" int rfx_scene_set_spheres(rfx_scene *s, uint32_t first, uint32_t count, const float *spheres4)
+{
+  if (!s || !spheres4 || !count || (uint64_t)first + count > s->spheres.size())
+    return fail(RFX_ERR_ARG, "scene_set_spheres: a scene, spheres and a range within its %zu spheres",
+                s ? s->spheres.size() : (size_t)0);
+  for (uint32_t i = 0; i < count; ++i)
+  {
+    const float *v = spheres4 + 4 * (size_t)i;
+    HostSphere &h = s->spheres[first + i];
+    h.center = mk(v[0], v[1], v[2]);
+    h.radius = sphere_radius(v[3]);
+    h.sq_radius = h.radius * h.radius;                                               // Sphere.cpp:19
+  }
+  return RFX_OK;
+}
+
+extern "C" int rfx_scene_object_sphere(const rfx_scene *s, int obj)
+{
+  if (!s || obj < 0 || obj >= (int)s->obj_kind.size() || s->obj_kind[obj] != 0)
+    return fail(RFX_ERR_ARG, "scene_object_sphere: object %d is not a sphere", obj);
+  return s->obj_idx[obj];
+}
+
+void rfx::sph_record_words(uint32_t *out, const SphereGeo &g, const SpherePair &p, int lane, const Bound &b)
+{
+  static_assert(kSphRecordWords == 12, "record layout");
+  const float w[12] = {g.cx, g.cy, g.cz, g.sq_radius, p.cx[lane], p.cy[lane], p.cz[lane], p.r2[lane], b.x, b.y, b.z, b.r};
+  memcpy(out, w, sizeof(w));
+  canonical_nans(out, kSphRecordWords);
+}
+
+extern "C" int rfx_scene_sph_records(const rfx_scene *s, uint32_t first, uint32_t count, uint32_t *out)
+{
+  if (!s || !out || !count || (uint64_t)first + count > s->spheres.size())
+    return fail(RFX_ERR_ARG, "scene_sph_records: a scene, an output and a range within its %zu spheres",
+                s ? s->spheres.size() : (size_t)0);
+  for (uint32_t i = 0; i < count; ++i)
+  {
+    const HostSphere &h = s->spheres[first + i];
+    const SphereGeo g{h.center.x, h.center.y, h.center.z, h.sq_radius};
+    SpherePair p{};
+    p.cx[0] = g.cx; p.cy[0] = g.cy; p.cz[0] = g.cz; p.r2[0] = g.sq_radius;
+    sph_record_words(out + (size_t)kSphRecordWords * i, g, p, 0, sphere_bound(g.cx, g.cy, g.cz, h.radius));
+  }
+  return RFX_OK;
+}
+
+extern "C" int rfx_scene_sph_bvh_dump(const rfx_scene *s, int32_t counts[4], float *boxes, int32_t *children,
+                                      int32_t *leaf_ids, uint32_t *device_index)
+{
+  if (!s || !counts) return fail(RFX_ERR_ARG, "sph_bvh_dump: bad args");
+  for (int k = 0; k < 4; ++k) counts[k] = 0;
+  counts[2] = (int32_t)kSphLeaf;
+  const SceneBuild B(*s, 0);
+  const size_t nsph = s->spheres.size();
+  if (device_index) std::copy(B.sslot.begin(), B.sslot.end(), device_index);
+  if (B.bvh.empty()) return 0;  // a small scene, at most 32 spheres, or a tree the walkers cannot take
+  std::vector<BvhNode> nodes;
+  double ref[3];
+  const int depth = sphere_bvh(B.bd, nsph, false, nodes, ref);  // the boxes as built: the topology is the uploaded tree's
+  const size_t leaves = nodes.size() + 1;
+  counts[0] = (int32_t)nodes.size();
+  counts[1] = (int32_t)leaves;
+  counts[3] = depth;
+  report_nodes(nodes, boxes, nullptr);
+  if (boxes) canonical_nans(boxes, 12 * nodes.size());
+  if (children)
+    for (size_t i = 0; i < nodes.size(); ++i) { children[2 * i] = nodes[i].child[0]; children[2 * i + 1] = nodes[i].child[1]; }
+  if (leaf_ids)
+  {
+    std::fill(leaf_ids, leaf_ids + leaves * kSphLeaf, -1);
+    for (size_t i = 0; i < nsph; ++i) leaf_ids[B.sslot[i]] = (int32_t)i;
+  }
+  return 1;
+}
+
+namespace {
+// the unwidened box below child c of the pair tree, writing every node's children on the way
+SphBox sph_refit_below(std::vector<BvhNode> &nodes, int c, const std::vector<SphBox> &leaf, const double *ref, bool widen)
+{
+  if (c < 0) return leaf[~c];
+  SphBox b;
+  sph_box_empty(b);
+  for (int k = 0; k < 2; ++k)
+  {
+    const SphBox kid = sph_refit_below(nodes, nodes[c].child[k], leaf, ref, widen);
+    bvh_child_set(nodes[c], k, kid.lo, kid.hi, ref, widen);
+    sph_box_join(b, kid);
+  }
+  return b;
+}
+}  // namespace
+
+extern "C" int rfx_scene_sph_bvh_refit(const rfx_scene *built, const float *spheres4_all, int widen, float *boxes, float *mt,
+                                       float *chunk_bounds)
+{
+  if (!built || !spheres4_all || widen < 0 || widen > 1) return fail(RFX_ERR_ARG, "scene_sph_bvh_refit: bad args");
+  SceneBuild B(*built, 0);
+  const size_t nsph = built->spheres.size();
+  std::vector<Bound> bd(nsph);
+  for (size_t i = 0; i < nsph; ++i)
+  {
+    const float *v = spheres4_all + 4 * i;
+    bd[B.sslot[i]] = sphere_bound(v[0], v[1], v[2], sphere_radius(v[3]));
+  }
+  if (chunk_bounds)
+    for (size_t first = 0; first < nsph; first += 64)
+    {
+      const Bound c = sphere_chunk_bound(&bd[first], (uint32_t)(std::min(nsph, first + 64) - first));
+      memcpy(chunk_bounds + 4 * (first / 64), &c, sizeof(c));
+      canonical_nans(chunk_bounds + 4 * (first / 64), 4);
+    }
+  if (B.bvh.empty()) return 0;
+  std::vector<SphBox> leaf(B.bvh.size() + 1);
+  for (size_t g = 0; g < leaf.size(); ++g) leaf[g] = sph_leaf_box(bd.data(), (uint32_t)g, (uint32_t)nsph);
+  const double ref[3] = {B.d.bvh_rx, B.d.bvh_ry, B.d.bvh_rz};
+  sph_refit_below(B.bvh, 0, leaf, ref, widen != 0);
+  report_nodes(B.bvh, boxes, mt);
+  if (boxes) canonical_nans(boxes, 12 * B.bvh.size());
+  if (mt) canonical_nans(mt, 2 * B.bvh.size());
   return 1;
 }

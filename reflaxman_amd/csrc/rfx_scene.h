@@ -71,11 +71,26 @@ struct SceneBuild {
   // triangles, ascending, and the cut's topology over the tree's leaves
   std::vector<uint32_t> tin;
   CutTopology cut;
+  // What rfx_renderer_update_spheres keeps beside the scene (rfx.h "Moving spheres"): per sphere of the insertion order
+  // its index in the device arrays, and the pair tree's nodes by height as hlist / hoff above (hoff = {0} without a tree)
+  bool small_scene = false;
+  std::vector<uint32_t> sslot, shoff;
+  std::vector<int32_t> shlist;
 };
 
 // rfx_scene.cpp, for rfx_update.cpp: one triangle's record words in rfx_scene_tri_records' layout (NaNs canonical)
 // from its geometry records, bound, vertices and class; `leaf`: the tree's copy (null: the triangle's own record)
 void tri_record_words(uint32_t *out, const TriGeo &g, const TriShade &h, const Bound &b, const float *verts9, bool well,
                       const TriGeo *leaf);
+
+// every NaN of n words reported as 0x7FC00000: its sign and payload carry nothing and differ between processors
+inline void canonical_nans(void *words, size_t n)
+{
+  uint32_t *w = static_cast<uint32_t *>(words);
+  for (size_t k = 0; k < n; ++k)
+    if ((w[k] & 0x7FFFFFFFu) > 0x7F800000u) w[k] = 0x7FC00000u;
+}
+// ... and one sphere's, in rfx_scene_sph_records' layout: its sph_geo record, its lane of its sph_pair record, its bound
+void sph_record_words(uint32_t *out, const SphereGeo &g, const SpherePair &p, int lane, const Bound &b);
 
 }  // namespace rfx

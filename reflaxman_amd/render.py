@@ -249,6 +249,61 @@ class Scene:
         return {"nodes": int(cnt[0]), "leaves": int(cnt[1]), "leaf_size": int(cnt[3]), "depth": int(cnt[4]), "boxes": boxes,
                 "children": children, "leaf_ids": ids, "residual": d["residual"], "mt": mt}
 
+    def setSpheres(self, first: int, spheres):
+        """New centres and radii for spheres [first, first + n) (rfx.h rfx_scene_set_spheres): (n, 4) floats, centre
+        then radius (clamped as addSphere clamps it).  Materials stay; the next upload of the scene reads them."""
+        v = np.ascontiguousarray(spheres, dtype=np.float32).reshape(-1, 4)
+        check(_lib.load().rfx_scene_set_spheres(self._h, int(first), v.shape[0], _lib.fptr(v)), "Scene.setSpheres")
+        self._version += 1
+
+    def object_sphere(self, obj: int) -> int:
+        """The sphere index (insertion order among spheres) of object `obj` (rfx.h rfx_scene_object_sphere)."""
+        return check(_lib.load().rfx_scene_object_sphere(self._h, int(obj)), "Scene.object_sphere")
+
+    def sph_records(self, first: int = 0, count: Optional[int] = None) -> np.ndarray:
+        """The words that follow the spheres' centres and radii (rfx.h rfx_scene_sph_records; host only): (count,
+        RFX_SPH_RECORD_WORDS) uint32."""
+        n = self.counts()[0] - first if count is None else count
+        out = np.zeros((n, _lib.RFX_SPH_RECORD_WORDS), np.uint32)
+        check(_lib.load().rfx_scene_sph_records(self._h, int(first), n, _lib.u32ptr(out)), "Scene.sph_records")
+        return out
+
+    def sph_bvh_dump(self):
+        """The pair tree a renderer would build for this scene's spheres (rfx.h rfx_scene_sph_bvh_dump; host only):
+        dict of nodes, leaves, leaf_size, depth, boxes (nodes, 2, 6), children (nodes, 2), leaf_ids (leaves, leaf_size)
+        and device_index (spheres,); without a tree nodes is 0, the arrays are empty and device_index alone is filled."""
+        L = _lib.load()
+        cnt = (C.c_int32 * 4)()
+        dev = np.zeros(self.counts()[0], np.uint32)
+        check(L.rfx_scene_sph_bvh_dump(self._h, cnt, None, None, None, _lib.u32ptr(dev)), "Scene.sph_bvh_dump")
+        nodes, leaves, leaf, depth = (int(x) for x in cnt)
+        boxes = np.zeros((nodes, 2, 6), np.float32)
+        children = np.zeros((nodes, 2), np.int32)
+        ids = np.zeros((leaves, leaf), np.int32)
+        i32 = lambda a: a.ctypes.data_as(_lib._i32p)
+        if nodes:
+            check(L.rfx_scene_sph_bvh_dump(self._h, cnt, _lib.fptr(boxes), i32(children), i32(ids), None),
+                  "Scene.sph_bvh_dump")
+        return {"nodes": nodes, "leaves": leaves, "leaf_size": leaf, "depth": depth, "boxes": boxes,
+                "children": children, "leaf_ids": ids, "device_index": dev}
+
+    def sph_bvh_refit(self, spheres, widen: bool):
+        """This scene's pair tree refitted on the host to `spheres` ((spheres, 4) floats: centre, radius), as the device
+        update refits it (rfx.h rfx_scene_sph_bvh_refit): (boxes (nodes, 2, 6), mt (nodes, 2), chunk_bounds (chunks, 4));
+        without a tree the first two are empty."""
+        L = _lib.load()
+        n = self.counts()[0]
+        v = np.ascontiguousarray(spheres, dtype=np.float32).reshape(-1, 4)
+        if v.shape[0] != n:
+            raise ValueError("sph_bvh_refit: a centre and radius for every sphere of the scene")
+        cnt = (C.c_int32 * 4)()
+        check(L.rfx_scene_sph_bvh_dump(self._h, cnt, None, None, None, None), "Scene.sph_bvh_dump")
+        boxes, mt = np.zeros((cnt[0], 2, 6), np.float32), np.zeros((cnt[0], 2), np.float32)
+        chunks = np.zeros(((n + 63) // 64, 4), np.float32)
+        check(L.rfx_scene_sph_bvh_refit(self._h, _lib.fptr(v), int(bool(widen)), _lib.fptr(boxes), _lib.fptr(mt),
+                                        _lib.fptr(chunks)), "Scene.sph_bvh_refit")
+        return boxes, mt, chunks
+
     def cull_dump(self):
         """The bundle-cull records of a small scene as a renderer would upload them (rfx.h rfx_scene_cull_dump; host
         only): (recs (64, 8), tris (32, 12), valid lanes as an int)."""
@@ -516,6 +571,91 @@ class Renderer:
         i32 = lambda a: a.ctypes.data_as(_lib._i32p)
         check(L.rfx_renderer_tri_leaves(self._h, i32(ids), i32(slot), _lib.u32ptr(rec)), "rfx_renderer_tri_leaves")
         return ids, slot, rec
+
+    def update_spheres(self, first: int, spheres, ids=None):
+        """New centres and radii for spheres of the uploaded scene, on the device (rfx.h "Moving spheres",
+        rfx_renderer_update_spheres): every later launch is the one a renderer gives whose set_scene got the scene built
+        at these spheres.  spheres: (n, 4) floats, centre then radius, for spheres [first, first + n) of the insertion
+        order -- or, with ids (n,), for the spheres the ids name (`first` is ignored; an id beyond the scene's spheres is
+        skipped).  Torch tensors on this renderer's device are read where they lie, on torch's current stream, with no
+        host sync (update_triangles' conventions); anything else goes through numpy and the host form, which
+        synchronises.  A small scene raises.  A later set_scene(scene) uploads again: move the Scene too
+        (Scene.setSpheres) if it is to match."""
+        L = _lib.load()
+        try:
+            import torch
+            is_torch = isinstance(spheres, torch.Tensor)
+        except ImportError:
+            is_torch = False
+        self._scene_key = None
+        if is_torch:
+            if not spheres.is_cuda or spheres.device.index != self.device:
+                raise ValueError("update_spheres: tensors on the renderer's device (or numpy arrays) are required")
+            p = spheres.to(torch.float32).reshape(-1, 4).contiguous()
+            idx = None
+            if ids is not None:
+                if not (isinstance(ids, torch.Tensor) and ids.is_cuda and ids.device == spheres.device):
+                    raise ValueError("update_spheres: ids on the spheres' device")
+                idx = ids.to(torch.int32).reshape(-1).contiguous()  # (uint32 words: a negative int32 names no sphere)
+                if idx.shape[0] != p.shape[0]:
+                    raise ValueError("update_spheres: one id per sphere record")
+            stream = torch.cuda.current_stream(p.device).cuda_stream
+            if not stream:
+                torch.cuda.current_stream(p.device).synchronize()
+            check(L.rfx_renderer_update_spheres(self._h, int(first), p.shape[0], C.c_void_p(p.data_ptr()),
+                                                C.c_void_p(idx.data_ptr() if idx is not None else None),
+                                                C.c_void_p(stream or None)), "rfx_renderer_update_spheres")
+            if not stream:
+                self.synchronize()
+            else:
+                self._keep_update = (p, idx)  # the launch reads them after this call returns
+            return
+        p = np.ascontiguousarray(spheres, dtype=np.float32).reshape(-1, 4)
+        idx = None if ids is None else np.ascontiguousarray(ids, dtype=np.uint32).reshape(-1)
+        if idx is not None and idx.shape[0] != p.shape[0]:
+            raise ValueError("update_spheres: one id per sphere record")
+        check(L.rfx_renderer_update_spheres_host(self._h, int(first), p.shape[0], _lib.fptr(p),
+                                                 _lib.u32ptr(idx) if idx is not None else None),
+              "rfx_renderer_update_spheres_host")
+
+    def sph_records(self, first: int = 0, count: Optional[int] = None) -> np.ndarray:
+        """The uploaded spheres' words that follow their centres and radii, read back in insertion order (rfx.h
+        rfx_renderer_sph_records; synchronises): (count, RFX_SPH_RECORD_WORDS) uint32."""
+        n = self._scene_ref.counts()[0] - first if count is None else count
+        out = np.zeros((n, _lib.RFX_SPH_RECORD_WORDS), np.uint32)
+        check(_lib.load().rfx_renderer_sph_records(self._h, int(first), n, _lib.u32ptr(out)), "rfx_renderer_sph_records")
+        return out
+
+    def sph_bvh_nodes(self):
+        """The uploaded pair tree read back (rfx.h rfx_renderer_sph_bvh_nodes; synchronises): (boxes (nodes, 2, 6)
+        float32, children (nodes, 2) int32, mt (nodes, 2) float32), or None without a tree."""
+        L = _lib.load()
+        n = check(L.rfx_renderer_sph_bvh_nodes(self._h, None), "rfx_renderer_sph_bvh_nodes")
+        if n == 0:
+            return None
+        out = np.zeros((n, 16), np.float32)
+        check(L.rfx_renderer_sph_bvh_nodes(self._h, _lib.fptr(out)), "rfx_renderer_sph_bvh_nodes")
+        return out[:, :12].reshape(n, 2, 6).copy(), out[:, 12:14].copy().view(np.int32), out[:, 14:16].copy()
+
+    def sph_chunk_bounds(self) -> np.ndarray:
+        """The uploaded 64-sphere chunks' bounds read back (rfx.h rfx_renderer_sph_chunk_bounds; synchronises):
+        (chunks, 4) float32."""
+        L = _lib.load()
+        n = check(L.rfx_renderer_sph_chunk_bounds(self._h, None), "rfx_renderer_sph_chunk_bounds")
+        out = np.zeros((n, 4), np.float32)
+        if n:
+            check(L.rfx_renderer_sph_chunk_bounds(self._h, _lib.fptr(out)), "rfx_renderer_sph_chunk_bounds")
+        return out
+
+    def sph_padding(self) -> np.ndarray:
+        """The padding lanes of the uploaded pair records (rfx.h rfx_renderer_sph_padding; synchronises): (lanes, 4)
+        uint32 -- no update writes them."""
+        L = _lib.load()
+        n = check(L.rfx_renderer_sph_padding(self._h, None), "rfx_renderer_sph_padding")
+        out = np.zeros((n, 4), np.uint32)
+        if n:
+            check(L.rfx_renderer_sph_padding(self._h, _lib.u32ptr(out)), "rfx_renderer_sph_padding")
+        return out
 
     def set_rng(self, sphere_seed: int, jitter_seed: int):
         check(_lib.load().rfx_renderer_set_rng(self._h, sphere_seed & 0xFFFFFFFF, jitter_seed & 0xFFFFFFFF), "set_rng")
