@@ -16,6 +16,7 @@ from test_gpu_mesh_update import FRAMES, dev, frame, oracle_frame, rays_at_the_s
 pytestmark = pytest.mark.gpu
 
 _DESC, _BUILT = {}, {}
+COUNT_EDGES = (40, 64, 65, 128)
 
 
 def leaf_pairs():
@@ -26,6 +27,9 @@ def desc_of(key):
     if key not in _DESC:
         _DESC[key] = {"stress33": lambda: scenes.stress_scene(33), "stress100": lambda: scenes.stress_scene(100),
                       "stress300": lambda: scenes.stress_scene(300), "stress4600": lambda: scenes.stress_scene(4600),
+                      # the count edges: a full last leaf (no padding lane), a chunk exactly full, one sphere in the last
+                      # chunk (tests/test_gpu_tree_limits.py has the same arithmetic at the trees' largest size)
+                      **{f"stress{n}": (lambda n=n: scenes.stress_scene(n)) for n in COUNT_EDGES},
                       # more nodes than the bounce kernel's LDS holds (tests/test_gpu_parity.py
                       # test_regrouped_large_scene_equals_unregrouped): the global-memory bounce form
                       "stress_global": lambda: scenes.stress_scene(4400 * leaf_pairs()),
@@ -60,7 +64,7 @@ def same_state(got, want):
 
 
 # ------------------------------------------------------------------------------------------------ records and nodes
-@pytest.mark.parametrize("key", ["stress33", "stress100", "soup38s8"])
+@pytest.mark.parametrize("key", ["stress33", "stress100", "soup38s8"] + [f"stress{n}" for n in COUNT_EDGES])
 def test_words_follow_the_host_mirror_and_come_back(key):
     """A -> B -> C -> A (a jiggle, then a shuffle of another jiggle): after every update the records are the edited host
     scene's, the nodes the host refit's (widen = 1) and the chunk bounds the mirror's, bit for bit; the padding lanes
@@ -89,6 +93,25 @@ def test_words_follow_the_host_mirror_and_come_back(key):
         assert not same_state(got, state_a)
     rr.update_spheres(0, A)  # the host form
     assert same_state(device_state(rr), state_a)
+    rr.close()
+
+
+@pytest.mark.parametrize("n", COUNT_EDGES)
+def test_count_edge_frame_after_a_jiggle(n):
+    """40, 64, 65 and 128 spheres -- a last leaf with no padding lane, a chunk exactly full, a last chunk of one sphere --
+    jiggled: the padding lanes are as many as the count leaves over, and the 32x18 frame is the oracle's"""
+    key = f"stress{n}"
+    s, cam = built(key)
+    desc = desc_of(key)
+    S = jiggle(sph_data(desc))
+    rr = renderer(s, -1)
+    assert rr.sph_padding().shape == ((-n) % (2 * leaf_pairs()), 4) and len(rr.sph_chunk_bounds()) == (n + 63) // 64
+    assert rr.accel_info().sph_nodes == (n + 2 * leaf_pairs() - 1) // (2 * leaf_pairs()) - 1
+    rr.update_spheres(0, dev(S))
+    W, H = 32, 18
+    img = frame(rr, cam, W, H, 6)
+    ref = oracle_frame(key + "_jiggle", moved_desc(desc, S), W, H, 6)
+    assert img.tobytes() == ref.tobytes(), int((img != ref).any(axis=2).sum())
     rr.close()
 
 
